@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: DeepLabV3+/WRN38 training step (+ OOD-score throughput) on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,12 +13,15 @@ Default workload = BASELINE.json's metric configuration, per GPU: one (original,
 has the same amount of work (weak scaling); `value` is whole-job images/s. Inputs are generated on
 the device before the timed region; weights are synthetic (multishiftseg_amd.synth), fp32 throughout.
 
-One JSON line on rank 0 carries the step metric, the fp32-MFMA roofline of the dominant kernel
+A plain run sets up, warms up, times K steps and prints one JSON line on rank 0 with the step metric (`value`,
+`ms_per_step`, `config`); --dump-outputs DIR also writes what the last timed step handed its caller (dump_outputs).
+With --full the same line also carries the fp32-MFMA roofline of the dominant kernel
 (gemm_nt / conv_igemm: HIP events on the launch stream around every launch, in a SECOND pass of K steps right after the
 timed region so that the ~110 event records per step are not charged to `value`), `parity` (the default route against the
 reference's own outputs at this very configuration, argmax flips over all pixels), the OOD-score Mpix/s of the eval path
 (eager, score-only, hipGraph), at N = 1 the Mask2Former legs (`m2f`: MSDeformAttn op, pixel decoder, fused score, metric
-sweep) and a CPU baseline (stock-torch restatements on the host's cores, bounded samples), at N > 1 `comm`.
+sweep) and a CPU baseline (stock-torch restatements on the host's cores, bounded samples), at N > 1 `comm`; the
+--no-* switches leave out single legs of --full.
 """
 import argparse
 import json
@@ -148,6 +151,27 @@ def parity_check(model, H, W, pairs):
         model.train(was)
 
 
+DUMP_SAMPLE = 1 << 22      # entries kept of an output larger than this (16 MB of float32); three such outputs stay under 64 MB
+
+
+def dump_outputs(path, loss, score, logit, params):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files under `path`: loss.npy (the step's
+    loss), score.npy and logit.npy (the forward's OOD score [2p,H,W] and logits [2p,19,H,W]), params.npy (the trainable
+    parameters after the step's Adam update, flattened and concatenated in named_parameters order). An output of more than
+    DUMP_SAMPLE entries is written as the entries at DUMP_SAMPLE sorted flat positions drawn from a generator with a fixed
+    seed per output, so the sample depends only on the output and its size."""
+    os.makedirs(path, exist_ok=True)
+    outs = {"loss": loss.detach().reshape(1), "score": score, "logit": logit,
+            "params": torch.cat([p.detach().reshape(-1) for p in params])}
+    for seed, (name, t) in enumerate(outs.items()):
+        flat = t.reshape(-1)
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes through torch.distributed.run as a
     CHILD process (never exec: this image forbids replacing a process image once a GPU runtime is loaded, and the
@@ -250,6 +274,10 @@ def main():
     ap.add_argument("--stage", type=int, default=2, choices=[1, 2])
     ap.add_argument("--loss-sync", default="local", choices=["local", "global"],
                     help="local: per-rank loss (no loss collectives); global: reference semantics over all ranks' pairs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline pass, parity, split-bf16 co-headline, OOD-score, Mask2Former legs, CPU baseline, "
+                         "loss kernel, device peaks; at N > 1 `comm` (off: set up, warm up, time --steps steps, print the result line)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ood", action="store_true")
     ap.add_argument("--no-m2f", action="store_true", help="skip the Mask2Former legs (`m2f`, N=1 only, ~40 s)")
@@ -257,6 +285,8 @@ def main():
     ap.add_argument("--no-split", action="store_true",
                     help="skip the co-headline run on the split-bf16 GEMM route (`value_fp32_via_bf16x3`, N=1 only; never part of `value`)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -277,7 +307,7 @@ def main():
     pairs, H, W = {"c3": (1, 1024, 2048), "c2": (8, 768, 768), "c2_700": (8, 700, 700), "tiny": (1, 128, 256)}[args.workload]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline((H, W))
 
     params = synth.deepwv3plus_params(0)
@@ -299,7 +329,7 @@ def main():
         return step(img, target0.clone())      # the loss mutates its targets; a loader would hand over fresh ones
 
     parity = None
-    if rank == 0 and not args.no_parity and args.workload == "c3":
+    if args.full and rank == 0 and not args.no_parity and args.workload == "c3":
         try:                        # before any optimizer step: the weights are still the ones the fixture was made with
             parity = parity_check(model, H, W, pairs)
         except Exception as exc:    # never lose the measurement to the checker
@@ -315,13 +345,16 @@ def main():
         finally:
             K.set_gemm_route(None)
 
+    torch.manual_seed(4321 + rank)      # the Dropout2d masks of the train-mode trunk: the same inputs from run to run
+    dump = args.dump_outputs is not None and rank == 0
     for _ in range(args.warmup):
         one_step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        step.keep_outputs = dump and i == args.steps - 1
         loss = one_step()
     torch.cuda.synchronize()
     if world > 1:
@@ -332,6 +365,35 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump:
+        dump_outputs(args.dump_outputs, loss, *step.last_outputs, [p for p in model.parameters() if p.requires_grad])
+        step.keep_outputs, step.last_outputs = False, None
+
+    images = 2 * pairs * world * args.steps
+    value = images / elapsed
+    step_flops_alg = 2 * FWD_GMAC_1024x2048 * 1e9 * (H * W) / (1024 * 2048) * 2 * pairs * \
+        (STAGE2_STEP_OVER_FWD if args.stage == 2 else 1.0)
+    out = {
+        "metric": "train images/sec (DeepLabV3+ WRN38, fwd + RelContrastiveLoss + bwd + Adam)",
+        "value": round(value, 4), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {2 * pairs} images ({pairs} orig+aug pair(s)) of {H}x{W} per GPU, "
+                               f"stage-{args.stage} trainable set, train-mode BN/Dropout2d on the frozen trunk",
+                   "images_per_gpu": 2 * pairs, "height": H, "width": W, "stage": args.stage,
+                   "parallelism": f"dp{world}",
+                   "rccl_ranks": (dist.get_world_size() if world > 1 and dist.get_backend() == "nccl" else 0),
+                   "loss_pairing": "device", "loss_sync": args.loss_sync, "loss": round(loss_val, 4)},
+        "step_tflops_algorithmic": round(step_flops_alg / (elapsed / args.steps) / 1e12, 2),
+    }
+    if not args.full:
+        if rank == 0:
+            out["summary"] = {"ms_per_step": out["ms_per_step"], "img_s": out["value"]}
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # second, UNTIMED pass of the same K steps with a HIP event pair around every MFMA launch (the roofline leg)
     prof = K.ConvProfile()
@@ -377,8 +439,6 @@ def main():
             dist.destroy_process_group()
         return
 
-    images = 2 * pairs * world * args.steps
-    value = images / elapsed
     summ = prof.summary()
     # the two forward MFMA kernels (same 128x128x16 inner loop): gemm_nt_kernel takes the 1x1 / batched Winograd-domain
     # products, conv_igemm_kernel the implicit-GEMM shapes; the roofline object is the one with more time in the step
@@ -393,31 +453,15 @@ def main():
         if kind == dom:
             n, h, w, c, k, r, st, _d = tag
             alg_bytes += 4.0 * (n * h * w * c + n * (-(-h // st)) * (-(-w // st)) * k + r * r * c * k * (n if h == 1 else 1))
-    step_flops_alg = 2 * FWD_GMAC_1024x2048 * 1e9 * (H * W) / (1024 * 2048) * 2 * pairs * \
-        (STAGE2_STEP_OVER_FWD if args.stage == 2 else 1.0)
-
-    out = {
-        "metric": "train images/sec (DeepLabV3+ WRN38, fwd + RelContrastiveLoss + bwd + Adam)",
-        "value": round(value, 4), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {2 * pairs} images ({pairs} orig+aug pair(s)) of {H}x{W} per GPU, "
-                               f"stage-{args.stage} trainable set, train-mode BN/Dropout2d on the frozen trunk",
-                   "images_per_gpu": 2 * pairs, "height": H, "width": W, "stage": args.stage,
-                   "parallelism": f"dp{world}",
-                   "rccl_ranks": (dist.get_world_size() if world > 1 and dist.get_backend() == "nccl" else 0),
-                   "loss_pairing": "device", "loss_sync": args.loss_sync, "loss": round(loss_val, 4)},
-        "roofline": {"bound": "mfma", "kernel": dom + "_kernel (fp32 v_mfma_f32_32x32x2_f32)",
-                     "measured": f"HIP events on the launch stream around every launch, second (untimed) pass of the same {args.steps} steps "
-                                 f"({1e3 * elapsed_profiled / args.steps:.2f} ms/step with the event records)",
-                     "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": None,
-                     "algorithmic_bytes_per_launch": round(alg_bytes / max(conv["launches"], 1)),
-                     "launches_per_step": conv["launches"] // max(args.steps, 1),
-                     "avg_launch_ms": round(conv["ms"] / max(conv["launches"], 1), 4),
-                     "kernel_ms_per_step": round(conv["ms"] / max(args.steps, 1), 2)},
-        "step_tflops_algorithmic": round(step_flops_alg / (elapsed / args.steps) / 1e12, 2),
-    }
+    out["roofline"] = {"bound": "mfma", "kernel": dom + "_kernel (fp32 v_mfma_f32_32x32x2_f32)",
+                        "measured": f"HIP events on the launch stream around every launch, second (untimed) pass of the same {args.steps} steps "
+                                    f"({1e3 * elapsed_profiled / args.steps:.2f} ms/step with the event records)",
+                        "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": None,
+                        "algorithmic_bytes_per_launch": round(alg_bytes / max(conv["launches"], 1)),
+                        "launches_per_step": conv["launches"] // max(args.steps, 1),
+                        "avg_launch_ms": round(conv["ms"] / max(conv["launches"], 1), 4),
+                        "kernel_ms_per_step": round(conv["ms"] / max(args.steps, 1), 2)}
     out["mfma_kernels"] = {k + "_kernel": {"tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
                                            "frac": round(v["flops"] / (v["ms"] * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
                                            "launches_per_step": v["launches"] // max(args.steps, 1),

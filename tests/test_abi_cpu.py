@@ -59,11 +59,11 @@ def test_msda_binned_workspace_query_is_host_only(lib):
     assert q([(0, 5)], 1, 8, 32, 10, 4) == 0                        # degenerate level
 
 
-def test_struct_layout_matches_header(lib):
+def test_struct_layout_matches_header(lib, tmp_path):
     """sizeof(MssConvArgs)/sizeof(MssRclArgs) as the C compiler sees them."""
     import ctypes
     code = '#include <stdio.h>\n#include "mss_hip.h"\nint main(){printf("%zu %zu\\n", sizeof(MssConvArgs), sizeof(MssRclArgs));return 0;}'
-    exe = "/tmp/mss_sizeof"
+    exe = str(tmp_path / "mss_sizeof")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=code.encode(), check=True)
     a, b = (int(v) for v in subprocess.check_output([exe], text=True).split())
     assert ctypes.sizeof(lib.MssConvArgs) == a and ctypes.sizeof(lib.MssRclArgs) == b

@@ -11,7 +11,7 @@ O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R
 bash tools/profile_round.sh $1/round > $O/profile_round.log 2>&1
-(cd /tmp && export TMPDIR=/tmp && MSS_GEMM_SPLIT=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_split -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-ood --no-split --no-m2f --no-parity > $O/bench_split_under_rocprof.json 2> /dev/null)
+(cd /tmp && export TMPDIR=/tmp && MSS_GEMM_SPLIT=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_split -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-ood --no-split --no-m2f --no-parity > $O/bench_split_under_rocprof.json 2> /dev/null)
 find $O/stats_split -name "*kernel_trace.csv" -delete
 bash tools/pmc_split.sh $1/pmc_split_nt > $O/pmc_split_nt.log 2>&1
 PMC_SPLIT_TN=1 bash tools/pmc_split.sh $1/pmc_split_tn 64,2304,4096,256 1,162624,1024,256 64,29412,256,256 > $O/pmc_split_tn.log 2>&1
@@ -25,6 +25,6 @@ MSS_GEMM_SPLIT=1 python tools/prof_decoder.py 16 704 704 2 layers 2>&1 | grep -v
 python -c "
 import sys, json; sys.path.insert(0, 'tools')
 import peaks; print(json.dumps({k: round(v, 1) for k, v in peaks.measure().items()}))" 2>/dev/null > $O/measured_peaks.json
-python bench.py > $O/bench_c3_default.json 2> $O/bench_c3_default.err
-python bench.py --workload c2_700 --no-cpu-baseline --no-m2f --no-ood > $O/bench_c2_16x700.json 2> /dev/null
+python bench.py --full > $O/bench_c3_default.json 2> $O/bench_c3_default.err
+python bench.py --full --workload c2_700 --no-cpu-baseline --no-m2f --no-ood > $O/bench_c2_16x700.json 2> /dev/null
 ls -la $O

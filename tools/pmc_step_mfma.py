@@ -20,7 +20,7 @@ traffic = {}
 tp = os.path.join(out, "traffic.json")
 if os.path.exists(tp):
     traffic = json.load(open(tp)).get("families", {})
-print("# MFMA kernels of the 2 x 1024 x 2048 training step -- rocprofv3 --pmc over `bench.py --steps 2 --warmup 1` (SQ counters in one pass,\n"
+print("# MFMA kernels of the 2 x 1024 x 2048 training step -- rocprofv3 --pmc over `bench.py --full --steps 2 --warmup 1` (SQ counters in one pass,\n"
       "# FETCH_SIZE and WRITE_SIZE in their own passes); sums over all launches of a family\n")
 print("| kernel family | launches | matrix pipe busy, % of shader cycles | VALU (non-MFMA) / MFMA | LDS / MFMA | VMEM rd / MFMA | MB per launch, memory side |")
 print("|---|---|---|---|---|---|---|")

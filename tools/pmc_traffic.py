@@ -1,5 +1,5 @@
 """Summarise two `rocprofv3 --pmc` passes (FETCH_SIZE, WRITE_SIZE; separate runs, MI355X_MICROARCH.md HBM section)
-over `bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-ood` into profiles/conv_traffic_latest.json.
+over `bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-ood` into profiles/conv_traffic_latest.json.
 
     python tools/pmc_traffic.py <fetch_dir> <write_dir> [out.json]
 
@@ -45,7 +45,7 @@ def main():
     dom = max(cands, key=lambda k: fams[k]["launches"] * fams[k]["hbm_bytes_per_launch"])
     c = fams[dom]
     out = {"kernel": dom, "git_commit": os.environ.get("MSS_TREE", "unknown"),
-           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `bench.py --steps 2 --warmup 1 "
+           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `bench.py --full --steps 2 --warmup 1 "
                      "--no-cpu-baseline --no-ood`, summarised by tools/pmc_traffic.py",
            "launches": c["launches"], "fetch_size_avg_KB": c["fetch_size_avg_KB"], "write_size_avg_KB": c["write_size_avg_KB"],
            "correction": "FETCH_SIZE x2 (gfx950 counts 128-B read requests as 64 B for 16-B/lane streaming reads, "
