@@ -845,6 +845,7 @@ __global__ void rcl_finalize_kernel(MssRclArgs a, const double* __restrict__ cou
   // labels in [C, 99) or below 0: F.nll_loss raises on them (loss.py:59); here the loss turns NaN and the count is reported
   out[6] = (float)counters[CNT_BAD_TARGET];
   if (counters[CNT_BAD_TARGET] > 0) out[0] = __builtin_nanf("");
+  out[7] = 0.f;                                  // unused slot of the [8] result: written, not left as the allocator handed it over
 }
 
 inline int grid_for(long long work_items, int cap = 256 * 16) {

@@ -66,7 +66,7 @@ class RelContrastiveLoss(nn.Module):
             raise ValueError(pairing)
         self.pairing = pairing
         self._step = int(seed)
-        self.last_terms = None   # device tensor [8]: loss, ce_orig, ce_aug, c_orig, c_aug, c_in
+        self.last_terms = None   # device tensor [8]: loss, ce_orig, ce_aug, c_orig, c_aug, c_in, bad-target count, 0
 
     def forward(self, logits, anomaly_score, targets, perms=None):
         if not logits.is_cuda:
