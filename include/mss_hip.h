@@ -21,14 +21,15 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 8      /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 9      /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
                                   6 (late round 4, additive): mss_msda_forward_fused_ld_f32, mss_msda_prepare_ld_f32, mss_add_layernorm_q_f32, mss_add_layernorm_bwd_sum2_f32, mss_msda_forward_fused_save_f32, mss_msda_backward_binned_proj_f32, mss_gap_from_partials_f32;
                                   7 (round 5): MssConvArgs.w_split + mss_gemm_split_weights_bf16x3 (the split-bf16 GEMM route);
                                   8 (round 6): mss_msda_forward_window_f32 removed (the measured-slower LDS-window forward left the product); additive: the mss_oodm_*lanes* entry points,
-                                  mss_gemm_split_last_mfma */
+                                  mss_gemm_split_last_mfma;
+                                  9: mss_oodm_compact_f32, mss_oodm_compact_packed_f32, mss_add_layernorm_bwd_sum_f32 and mss_m2f_fused_score_f32 removed (uncalled) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -454,12 +455,10 @@ int mss_adam_step_f32(float* param, const float* grad, float* exp_avg, float* ex
  * low-resolution mask logits [B, hm, wm, ldq] (queries contiguous; produced by mss_conv2d_forward_f32 in batched 1x1
  * mode from mask_features and mask_embed = einsum("bqc,bchw->bqhw"), mask2former_transformer_decoder.py:544-548);
  * the kernel applies F.interpolate(size=(Hi,Wi), bilinear, align_corners=False) (maskformer_model.py:264-277), the
- * sigmoid, the class mix and 1 - max (train_m2f.py:387-407) and writes the crop [B,H,W]. Q % 4 == 0, C <= 20. */
-int mss_m2f_fused_score_f32(const float* cls, const float* logit, int B, int Q, int C, int hm, int wm, int ldq, int Hi,
-                            int Wi, int H, int W, float* score, void* stream);
-/* The same with a scratch of B * Q * 32 floats: the class mix then runs on the matrix cores (v_mfma_f32_32x32x2_f32: [classes x Q] x
+ * sigmoid, the class mix and 1 - max (train_m2f.py:387-407) and writes the crop [B,H,W]. Q % 4 == 0, C <= 20.
+ * prob_ws: a scratch of B * Q * 32 floats: the class mix then runs on the matrix cores (v_mfma_f32_32x32x2_f32: [classes x Q] x
  * [Q x pixels] per 32-pixel strip, one interpolation + sigmoid per lane and MFMA) instead of 20 multiply-adds per (pixel, query)
- * on the vector ALUs; results agree with the form above to fp32 summation order. prob_ws NULL = the form above. */
+ * on the vector ALUs; results agree with the all-VALU form to fp32 summation order. prob_ws NULL = the all-VALU form. */
 int mss_m2f_fused_score_ws_f32(const float* cls, const float* logit, int B, int Q, int C, int hm, int wm, int ldq, int Hi,
                                int Wi, int H, int W, float* score, float* prob_ws, void* stream);
 
@@ -468,20 +467,14 @@ int mss_m2f_fused_score_ws_f32(const float* cls, const float* logit, int B, int 
  * fpr_and_fdr_at_recall (lib/utils/metric.py:170-180, 130-153, 87-127; callers test_deeplab.py:94-102,
  * train_deeplab.py:236-241), which run sklearn on host copies of every score map.
  *   compact:  one pass over a batch of n pixels: order-preserving u32 keys of the id_in pixels' scores packed
- *             at the front of keys[0..n), those of the id_out pixels at the back; counts (device u64[2], zero on
- *             entry) = {#id_in, #id_out}. No host synchronisation per batch.
+ *             at the front of a key segment, those of the id_out pixels at the back, counted on the device
+ *             (mss_oodm_compact_lanes_f32 below). No host synchronisation per batch.
  *   sort:     ascending key sort (own 4-pass LSD radix sort, csrc/metric.hip; keys 4-byte aligned, n < 2^32), temp sized
  *             by mss_oodm_sort_temp_bytes
  *   measures: out[0..2] = {AUROC, AUPRC, FPR@recall_level} (device f64[3]); u2_part / ap_part: device scratch of
  *             mss_oodm_rank_blocks(P) elements each. P, N >= 1 (the host mirror returns None otherwise, as
  *             metric.py:176-180 does). */
-int mss_oodm_compact_f32(const float* score, const long long* label, long long n, long long id_in, long long id_out,
-                         unsigned int* keys, unsigned long long* counts, void* stream);
-/* The same with both totals in ONE counter: *packed_count (zero on entry) ends as #id_in | (#id_out << 32); n < 2^32. Half the
- * same-address atomics of the form above (they were most of the kernel's time on a 1024 x 2048 map). */
-int mss_oodm_compact_packed_f32(const float* score, const long long* label, long long n, long long id_in, long long id_out,
-                                unsigned int* keys, unsigned long long* packed_count, void* stream);
-/* Round 6: the same on EIGHT counters (the single counter is one address 512 workgroups of a 1024 x 2048 map add to one after the other:
+/* Compaction on EIGHT counters (a single counter is one address 512 workgroups of a 1024 x 2048 map add to one after the other:
  * the kernel's 20 us). The 4096-pixel chunks are dealt round-robin onto 8 lanes; lane L owns keys[L * cap, (L + 1) * cap) with
  * cap = mss_oodm_compact_lanes_cap(n) (keys: 8 * cap slots), its id_in keys from the front of the segment, its id_out keys from the
  * back; lane_counts (device u64[8], zero on entry)[L] = #id_in | (#id_out << 32) of the lane. n < 2^32. */
@@ -520,15 +513,12 @@ int mss_add_layernorm_f32(const float* x, const float* res, long long rows, int 
 long long mss_add_layernorm_bwd_workspace_floats(long long rows, int C);
 int mss_add_layernorm_bwd_f32(const float* gy, const float* x, const float* res, const float* stat, long long rows, int C,
                               const float* gamma, float* dz, float* dgamma, float* dbeta, float* ws, void* stream);
-/* the same, and dzsum [C] = per-channel sums of dz: the bias gradient of the Linear whose output was `res`
- * (msdeformattn.py:116-131: output_proj / linear2) without another pass over [rows][C]. ws: 3/2 of the floats above. */
-int mss_add_layernorm_bwd_sum_f32(const float* gy, const float* x, const float* res, const float* stat, long long rows, int C,
-                                  const float* gamma, float* dz, float* dgamma, float* dbeta, float* dzsum, float* ws,
-                                  void* stream);
 /* r04: the output of an encoder layer's second LayerNorm has two consumers in the next layer, the layer input `src` and the
  * query q = src + pos (msdeformattn.py:116-118 with_pos_embed). mss_add_layernorm_q_f32 also writes q = y + pos[row % pos_rows]
  * (pos: [pos_rows][C], one image's tokens when the batch shares them); mss_add_layernorm_bwd_sum2_f32 takes the two gradients
- * (gy2 may be NULL) and adds them while loading. Same bits as the separate elementwise passes they replace. */
+ * (gy2 may be NULL) and adds them while loading. Same bits as the separate elementwise passes they replace. It also writes
+ * dzsum [C] = per-channel sums of dz: the bias gradient of the Linear whose output was `res` (msdeformattn.py:116-131:
+ * output_proj / linear2) without another pass over [rows][C]. ws: 3/2 of mss_add_layernorm_bwd_workspace_floats. */
 int mss_add_layernorm_q_f32(const float* x, const float* res, long long rows, int C, const float* gamma, const float* beta,
                             float eps, float* y, float* stat, const float* pos, long long pos_rows, float* q, void* stream);
 int mss_add_layernorm_bwd_sum2_f32(const float* gy, const float* gy2, const float* x, const float* res, const float* stat, long long rows,

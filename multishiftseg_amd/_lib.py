@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 8          # include/mss_hip.h
+MSS_ABI_VERSION = 9          # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -152,10 +152,7 @@ SIGNATURES = {
     "mss_bn_stats_partials_f32": [P, L, I, P, P],
     "mss_wino_grad_output_transform_f32": [P, I, I, I, I, I, I, I, P, P],
     "mss_wino_weight_grad_transform_f32": [P, P, I, I, I, I, I, P],
-    "mss_m2f_fused_score_f32": [P, P, I, I, I, I, I, I, I, I, I, I, P, P],
     "mss_m2f_fused_score_ws_f32": [P, P, I, I, I, I, I, I, I, I, I, I, P, P, P],
-    "mss_oodm_compact_f32": [P, P, L, L, L, P, P, P],
-    "mss_oodm_compact_packed_f32": [P, P, L, L, L, P, P, P],
     "mss_oodm_compact_lanes_f32": [P, P, L, L, L, P, P, P],
     "mss_oodm_compact_lanes_batch_f32": [P, I, L, L, P],
     "mss_oodm_gather_lanes_u32": [P, L, P, P, P, P],
@@ -167,7 +164,6 @@ SIGNATURES = {
     "mss_add_layernorm_f32": [P, P, L, I, P, P, F, P, P, P],
     "mss_add_layernorm_bwd_workspace_floats": [L, I],
     "mss_add_layernorm_bwd_f32": [P, P, P, P, L, I, P, P, P, P, P, P],
-    "mss_add_layernorm_bwd_sum_f32": [P, P, P, P, L, I, P, P, P, P, P, P, P],
     "mss_add_layernorm_q_f32": [P, P, L, I, P, P, F, P, P, P, L, P, P],
     "mss_add_layernorm_bwd_sum2_f32": [P, P, P, P, P, L, I, P, P, P, P, P, P, P],
     "mss_groupnorm_workspace_floats": [I, I, I, I],

@@ -551,12 +551,11 @@ __global__ __launch_bounds__(NT) void conv_wgrad_kernel(MssConvArgs p, const flo
 // conv_wgrad_kernel computes the same thing with its convolution loader (pixel decode, tap geometry, per-row masks:
 // 5 VALU instructions per MFMA) and one tile per workgroup; here nothing of that is left: both operands are plain
 // row-major [T][channels] matrices, a PERSISTENT workgroup walks (position, k-tile, c-tile, T-range) work items, and the
-// loader runs two 16-row steps ahead with one register set, across work-item boundaries (gemm.hip, VARIANT 2).
+// loader runs one 16-row step ahead, across work-item boundaries.
 // MFMA rows = k, columns = c, contraction = t; LDS tiles [2][16][128+4]; fragments by ds_read_b32 (lane i reads column
 // i of row 2s + (lane >> 5): 32 consecutive floats, conflict-free).
 // Work item w = ((split * P + p) * ktiles + kt) * ctiles + ct; its 128x128 tile goes to slab `split` of dst.
 constexpr int TN_BK = 128, TN_BC = 128, TN_BT = 16, TN_LD = 132;
-template <bool TWO_AHEAD>
 __global__ __launch_bounds__(NT, 3) void gemm_tn_wgrad_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                               float* __restrict__ dst, int P, int T, int K, int C,
                                                               long long a_bs, long long b_bs, int Kpad, int Cp,
@@ -688,23 +687,15 @@ __global__ __launch_bounds__(NT, 3) void gemm_tn_wgrad_kernel(const float* __res
   issue_loads();
   finish_store(0);
   advance();
-  if (TWO_AHEAD) { issue_loads(); advance(); }
   zero_acc();
   __syncthreads();
   load_frags(0, 0, 0);
   int buf = 0;
   while (true) {
-    if (TWO_AHEAD) {
-      load_frags(1, buf, 1);
-      finish_store(buf ^ 1);                  // step +1, requested during the previous step
-      issue_loads();                          // step +2 (possibly of the next work item)
-      advance();
-    } else {
-      issue_loads();                          // step +1, stored in this step
-      load_frags(1, buf, 1);
-      finish_store(buf ^ 1);
-      advance();
-    }
+    issue_loads();                          // step +1, stored in this step
+    load_frags(1, buf, 1);
+    finish_store(buf ^ 1);
+    advance();
     mfma_chunk(0);
     __syncthreads();
     load_frags(0, buf ^ 1, 0);
@@ -731,35 +722,30 @@ __global__ __launch_bounds__(NT, 3) void gemm_tn_wgrad_kernel(const float* __res
 // consumed in the order (s, s + 4 | s + 8, s + 12), s = 0..3, instead of (2s, 2s + 1): sums over t are re-associated, results
 // differ from gemm_tn_wgrad_kernel in the last bits and are as deterministic (fixed order).
 constexpr int TN2_LDK = 20;
-// BC: c extent of a tile, 128 (3 workgroups per CU) or 256 (2x2 waves of 64 x 128, 2 workgroups per CU; every thread loads a
-// 4x4 block of B and threads 0-127 one of A as well).
-template <int BC>
-__global__ __launch_bounds__(NT, BC == 256 ? 2 : 3) void gemm_tn2_wgrad_kernel(
+// Tiles are 128 k x 256 c: 2x2 waves of 64 x 128, 2 workgroups per CU; every thread loads a 4x4 block of B and threads 0-127 one
+// of A as well.
+__global__ __launch_bounds__(NT, 2) void gemm_tn2_wgrad_kernel(
     const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ dst, int P, int T, int K, int C, long long a_bs,
     long long b_bs, int Kpad, int Cp, int ktiles, int ctiles, int splits, int t_per_split, long long total) {
-  constexpr int TNJ = BC / 64;                          // 32-column MFMA blocks per wave
-  constexpr bool WIDE = BC == 256;
+  constexpr int BC = 256, TNJ = BC / 64;                // c extent of a tile; 32-column MFMA blocks per wave
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                                   // [2][128][20]
   float* Bs = smem + 2 * 128 * TN2_LDK;               // [2][BC][20]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const long long stride = gridDim.x;
-  // unit 0: BC = 128: A for waves 0-1, B for waves 2-3; BC = 256: B for every thread. unit 1 (WIDE, threads 0-127): A.
-  const bool u0B = WIDE || tid >= 128;                  // wave-uniform
-  const int cq0 = WIDE ? (tid & 63) : (tid & 31), tg0 = WIDE ? (tid >> 6) : ((tid & 127) >> 5);
-  const int cols0 = u0B ? C : K;
-  const float* const base0 = u0B ? B : A;
+  // unit 0: B for every thread. unit 1 (threads 0-127): A.
+  const int cq0 = tid & 63, tg0 = tid >> 6;
   // chunk rotation (r >> 2) + (r >> 4) of row r = 4 cq + e: the 16 lanes of a ds_write_b128 group then cover all 64 banks
   // (with (r >> 2) alone, rows 16 apart met in the same banks: PMC showed 2/3 of the LDS cycles as bank conflicts)
-  float* const ldst0 = (u0B ? Bs : As) + (4 * cq0) * TN2_LDK + ((tg0 + cq0 + (cq0 >> 2)) & 3) * 4;
-  const bool has1 = WIDE && tid < 128;                  // wave-uniform
+  float* const ldst0 = Bs + (4 * cq0) * TN2_LDK + ((tg0 + cq0 + (cq0 >> 2)) & 3) * 4;
+  const bool has1 = tid < 128;                          // wave-uniform
   const int cq1 = tid & 31, tg1 = (tid >> 5) & 3;
   float* const ldst1 = As + (4 * cq1) * TN2_LDK + ((tg1 + cq1 + (cq1 >> 2)) & 3) * 4;
 
   const bool edge_free = K % 128 == 0 && C % BC == 0;   // no channel tile hangs over the edge: no per-lane column mask
   long long ld_w = mss_xcd_remap(blockIdx.x, gridDim.x);
-  const float* ptr0 = base0;
+  const float* ptr0 = B;
   const float* ptr1 = A;
   int ld_t = 0, ld_tend = 0;
   bool colok0 = false, colok1 = false;
@@ -770,24 +756,22 @@ __global__ __launch_bounds__(NT, BC == 256 ? 2 : 3) void gemm_tn2_wgrad_kernel(
     const int sp = (int)(w / P);
     ld_t = sp * t_per_split;
     ld_tend = min(T, ld_t + t_per_split);
-    const int col0 = (u0B ? ct * BC : kt * 128) + 4 * cq0;
-    colok0 = col0 < cols0;
-    ptr0 = base0 + (size_t)p * (u0B ? b_bs : a_bs) + (size_t)ld_t * cols0 + (colok0 ? col0 : 0);
-    if (WIDE) {
-      const int col1 = kt * 128 + 4 * cq1;
-      colok1 = col1 < K;
-      ptr1 = A + (size_t)p * a_bs + (size_t)ld_t * K + (colok1 ? col1 : 0);
-    }
+    const int col0 = ct * BC + 4 * cq0;
+    colok0 = col0 < C;
+    ptr0 = B + (size_t)p * b_bs + (size_t)ld_t * C + (colok0 ? col0 : 0);
+    const int col1 = kt * 128 + 4 * cq1;
+    colok1 = col1 < K;
+    ptr1 = A + (size_t)p * a_bs + (size_t)ld_t * K + (colok1 ? col1 : 0);
   };
-  f32x4 reg0[4], reg1[WIDE ? 4 : 1];
+  f32x4 reg0[4], reg1[4];
   auto issue_loads = [&]() {
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     if (edge_free && ld_t + 16 <= ld_tend) {        // workgroup-uniform: whole 16-row step inside, no ragged channel tile
 #pragma unroll
-      for (int e = 0; e < 4; ++e) reg0[e] = *reinterpret_cast<const f32x4*>(ptr0 + (size_t)(4 * tg0 + e) * cols0);
-      if (WIDE && has1) {
+      for (int e = 0; e < 4; ++e) reg0[e] = *reinterpret_cast<const f32x4*>(ptr0 + (size_t)(4 * tg0 + e) * C);
+      if (has1) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) reg1[WIDE ? e : 0] = *reinterpret_cast<const f32x4*>(ptr1 + (size_t)(4 * tg1 + e) * K);
+        for (int e = 0; e < 4; ++e) reg1[e] = *reinterpret_cast<const f32x4*>(ptr1 + (size_t)(4 * tg1 + e) * K);
       }
       return;
     }
@@ -795,41 +779,41 @@ __global__ __launch_bounds__(NT, BC == 256 ? 2 : 3) void gemm_tn2_wgrad_kernel(
     for (int e = 0; e < 4; ++e) {
       const int r = 4 * tg0 + e;
       const bool ok = ld_t + r < ld_tend;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? ptr0 + (size_t)r * cols0 : base0);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? ptr0 + (size_t)r * C : B);
       reg0[e] = (ok && colok0) ? v : z;
     }
-    if (WIDE && has1) {
+    if (has1) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int r = 4 * tg1 + e;
         const bool ok = ld_t + r < ld_tend;
         const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? ptr1 + (size_t)r * K : A);
-        reg1[WIDE ? e : 0] = (ok && colok1) ? v : z;
+        reg1[e] = (ok && colok1) ? v : z;
       }
     }
   };
   auto advance = [&]() {
     ld_t += 16;
     if (ld_t < ld_tend) {
-      ptr0 += (size_t)16 * cols0;
-      if (WIDE) ptr1 += (size_t)16 * K;
+      ptr0 += (size_t)16 * C;
+      ptr1 += (size_t)16 * K;
     } else {
       ld_w += stride;
       setup(ld_w < total ? ld_w : ld_w - stride);
     }
   };
   auto finish_store = [&](int buf) {
-    float* d = ldst0 + buf * (u0B ? BC : 128) * TN2_LDK;
+    float* d = ldst0 + buf * BC * TN2_LDK;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const f32x4 w = {reg0[0][e], reg0[1][e], reg0[2][e], reg0[3][e]};     // channel 4 cq + e, t = 4 tg .. 4 tg + 3
       *reinterpret_cast<f32x4*>(d + e * TN2_LDK) = w;
     }
-    if (WIDE && has1) {
+    if (has1) {
       float* d1 = ldst1 + buf * 128 * TN2_LDK;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const f32x4 w = {reg1[0][e], reg1[WIDE ? 1 : 0][e], reg1[WIDE ? 2 : 0][e], reg1[WIDE ? 3 : 0][e]};
+        const f32x4 w = {reg1[0][e], reg1[1][e], reg1[2][e], reg1[3][e]};
         *reinterpret_cast<f32x4*>(d1 + e * TN2_LDK) = w;
       }
     }
@@ -1063,21 +1047,18 @@ int launch_wgrad(MssConvArgs& p, const float* dy, int lddy, float* dwp, int Cp, 
 // A ring of TND row pairs is in flight per wave. Output: whole 128 x 128 tiles of the (split, position) slab, 16-byte stores.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ const float tn_zero_row[4096] = {0.f};              // the A operand of rows past the end of a split
-// KB: 32-column blocks of dy per wave. 4: a 128 x 128 tile, 256 accumulator registers, ONE wave per SIMD. 2: a 64 x 128 tile, 128
-// accumulators, TWO waves per SIMD (the second wave fills the matrix pipe while the first issues its loads and address arithmetic)
-// at 1.5x the operand traffic per MFMA.
 // AFFINE: x enters as relu(x * scale[c] + shift[c]) (the forward's BatchNorm + ReLU prologue, one affine for all rows), applied to the
 // registers at consume time -- bot_aspp's 1280 -> 256 weight gradient (deepv3.py:235-240 reads the BN+ReLU of the five ASPP branches)
-template <int KB, bool AFFINE = false>
-__global__ __launch_bounds__(256, KB == 4 ? 1 : 2) void gemm_tn_direct_kernel(const float* __restrict__ A, const float* __restrict__ B,
+template <bool AFFINE = false>
+__global__ __launch_bounds__(256, 1) void gemm_tn_direct_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                                 float* __restrict__ out, int P, int M, int K, int C, long long a_bs,
                                                                 long long b_bs, int Kpad, int Cp, int ktiles, int ctiles, int splits,
                                                                 int tps, long long total, long long full, float* __restrict__ tail_ws,
                                                                 const float* __restrict__ scale = nullptr,
                                                                 const float* __restrict__ shift = nullptr, int relu = 0, int lda = 0) {
-  typedef typename std::conditional<KB == 4, f32x4, f32x2>::type avec;
   if (lda <= 0) lda = K;               // row stride of A (dy): larger when dy is a channel slice of a wider buffer
-  constexpr int TND = KB == 4 ? 8 : 5;                         // row pairs per register block (two blocks: one consumed, one in flight)
+  constexpr int KB = 4;                                        // 32-column blocks of dy per wave
+  constexpr int TND = 8;                                       // row pairs per register block (two blocks: one consumed, one in flight)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long job = (long long)blockIdx.x * 4 + wave;
   if (job >= total) return;                                   // no barrier anywhere in this kernel
@@ -1121,14 +1102,14 @@ __global__ __launch_bounds__(256, KB == 4 ? 1 : 2) void gemm_tn_direct_kernel(co
   // VALU + hazard nops per 16 MFMAs). The loop body handles both blocks in straight-line code, so no
   // register of the ring is ever copied while its load is pending; the scheduling fences keep hipcc from sinking the loads down to
   // their uses (it does: shorter live ranges).
-  avec a0[TND], a1[TND];
+  f32x4 a0[TND], a1[TND];
   f32x4 b0[TND], b1[TND];
   const int last = r1 - 1;
   const float* az = tn_zero_row + (kt * (32 * KB) + KB * j);    // K <= 4096 (host check)
-  auto fetch = [&](int row, avec& va, f32x4& vb) {
+  auto fetch = [&](int row, f32x4& va, f32x4& vb) {
     const bool ok = row <= last;
     const size_t rr = (size_t)(ok ? row : last);
-    va = *reinterpret_cast<const avec*>(ok ? a + rr * lda : az);  // a row past the end contributes A = 0: the product is zero
+    va = *reinterpret_cast<const f32x4*>(ok ? a + rr * lda : az);  // a row past the end contributes A = 0: the product is zero
     vb = *reinterpret_cast<const f32x4*>(b + rr * C);
   };
   f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
@@ -1137,10 +1118,10 @@ __global__ __launch_bounds__(256, KB == 4 ? 1 : 2) void gemm_tn_direct_kernel(co
     if (shift) sh = *reinterpret_cast<const f32x4*>(shift + ct * 128 + 4 * j);
   }
   const float fl = relu ? 0.f : -__builtin_huge_valf();
-  auto compute = [&](const avec (&va)[TND], const f32x4 (&vb)[TND]) {
+  auto compute = [&](const f32x4 (&va)[TND], const f32x4 (&vb)[TND]) {
 #pragma unroll
     for (int d = 0; d < TND; ++d) {
-      const avec ca = va[d];
+      const f32x4 ca = va[d];
       f32x4 cb = vb[d];
       if (AFFINE) {
         cb = cb * sc + sh;
@@ -1352,11 +1333,20 @@ struct TnPlan { int ktiles, ctiles, splits, tps; long long total; long long full
 inline int tn_batch(const MssConvArgs& p) { return p.batch > 1 ? p.batch : 1; }
 inline long long tn_tail_bytes(const TnPlan& pl) { return pl.full >= 0 ? (pl.total - pl.full) * (128ll * 128 * 4) : 0; }
 inline bool tn_direct(const MssConvArgs& p);
-inline int tn_mode();
+// MSS_WGRAD_TN: 5 (default, r04) the LDS-free gemm_tn_direct_kernel wherever K and C are multiples of 128 and its one-wave jobs
+// fill at least 3/4 of the SIMDs -- measured against the LDS kernels (tools/bench_wgrad_tn.py): ASPP F(6x6) 64 x 2304 x 4096 -> 256
+// 116.9 -> 121.9 TFLOP/s, F(4x4) 36 x 5184 118.1 -> 123.9, decoder F(6x6) 64 x 29412 x 256 -> 256 119.9 -> 131.4, the pixel
+// decoder's Linears 162624 x 256 -> 256 / 1024 -> 256 / 256 -> 1024 107.9 / 121.5 / 121.8 -> 111.9 / 129.7 / 129.5, 1x1 65536 x
+// 4096 -> 256 123.5 -> 132.6 --; elsewhere gemm_tn2_wgrad_kernel where its 256-wide c tiles need no pixel split and fill their
+// rounds (C % 256 == 0 and at least 2 rounds of 512 slots: tn_wide), else gemm_tn_wgrad_kernel. The other values force one kernel
+// onto shapes the default would not give it (tests): 0 the convolution-loader kernel (no TN route), 1 gemm_tn_wgrad_kernel,
+// 4 gemm_tn2_wgrad_kernel whenever C % 256 == 0, 7 gemm_tn_direct_kernel at any size.
+inline int tn_mode() {
+  return MSS_ENV_INT("MSS_WGRAD_TN", 5);
+}
 inline bool tn_eligible(const MssConvArgs& p, int lddy) {
-  const bool off = MSS_ENV_INT("MSS_WGRAD_TN", 5) == 0;     // A/B switch
-  if (off || p.R * p.S != 1 || p.K % 4 || p.C % 4 || p.ldx != p.C || lddy < p.K || lddy % 4) return false;
-  if (lddy != p.K && (p.batch > 1 || !tn_direct(p) || tn_mode() == 6)) return false;      // a slice of a wider dy: the LDS-free kernel takes a row stride
+  if (tn_mode() == 0 || p.R * p.S != 1 || p.K % 4 || p.C % 4 || p.ldx != p.C || lddy < p.K || lddy % 4) return false;
+  if (lddy != p.K && (p.batch > 1 || !tn_direct(p))) return false;      // a slice of a wider dy: the LDS-free kernel takes a row stride
   if (p.in_scale || p.in_shift || p.in_relu) {
     // a prologue on x: only the LDS-free kernel applies one (a single affine for all rows, 16-byte aligned vectors), one position
     if (p.batch > 1 || p.in_ss_stride != 0 || !tn_direct(p) || MSS_ENV_INT("MSS_WGRAD_TN_AFFINE", 1) == 0) return false;
@@ -1390,52 +1380,34 @@ inline TnPlan tn_plan(const MssConvArgs& p, int bc = TN_BC, int slots = 768) {
   pl.total = base * pl.splits;
   return pl;
 }
-// MSS_WGRAD_TN: 5 (default, r04) the LDS-free gemm_tn_direct_kernel<4> wherever K and C are multiples of 128 -- measured against
-// the kernels below (tools/bench_wgrad_tn.py): ASPP F(6x6) 64 x 2304 x 4096 -> 256 116.9 -> 121.9 TFLOP/s, F(4x4) 36 x 5184 118.1 ->
-// 123.9, decoder F(6x6) 64 x 29412 x 256 -> 256 119.9 -> 131.4, the pixel decoder's Linears 162624 x 256 -> 256 / 1024 -> 256 /
-// 256 -> 1024 107.9 / 121.5 / 121.8 -> 111.9 / 129.7 / 129.5, 1x1 65536 x 4096 -> 256 123.5 -> 132.6 -- when its one-wave jobs fill at
-// least 3/4 of the SIMDs, and rule 3 elsewhere; 7: that kernel at any size (tests); 6: its 64 x 128-tile, two-waves-per-SIMD form
-// (102-120: slower everywhere, kept for the tests). Forcing the older kernels:
-// 0 the convolution-loader kernel, 1 gemm_tn_wgrad_kernel, 2 gemm_tn2_wgrad_kernel<128>, 3 (the round-3 default) tn2 with
-// 256-wide c tiles where they need no pixel split and fill their rounds (C % 256 == 0 and at least 2 rounds of 512 slots) and
-// gemm_tn_wgrad_kernel elsewhere (with unmasked loads it is 2 % ahead of tn2<128>: 119.5 / 122.2 against 117.3 / 119.9 TFLOP/s),
-// 4 the wide kernel whenever C % 256 == 0 (tests)
-inline int tn_mode() {
-  return MSS_ENV_INT("MSS_WGRAD_TN", 5);
-}
 inline bool tn_wide(const MssConvArgs& p) {
   if (tn_mode() == 4) return p.C % 256 == 0;            // tests: the wide kernel at any size, pixel splits included
-  if ((tn_mode() != 3 && tn_mode() < 5) || p.C % 256) return false;
+  if (tn_mode() < 5 || p.C % 256) return false;
   const TnPlan w = tn_plan(p, 256, 512);
   const double eff = (double)w.total / (double)(((w.total + 511) / 512) * 512);
   return w.splits == 1 && w.total >= 1024 && eff >= 0.9;
 }
-inline bool tn_direct(const MssConvArgs& p);
 inline TnPlan tn_plan_direct(const MssConvArgs& p);
 inline TnPlan tn_plan_for(const MssConvArgs& p) { return tn_direct(p) ? tn_plan_direct(p) : tn_wide(p) ? tn_plan(p, 256, 512) : tn_plan(p); }
-inline TnPlan tn_plan_direct(const MssConvArgs& p);
 inline bool tn_direct(const MssConvArgs& p) {
   const int mode = tn_mode();
-  if ((mode != 5 && mode != 6 && mode != 7) || p.K % 128 || p.C % 128 || p.K > 4096) return false;
-  if (mode != 5) return true;                                  // 6 / 7 (tests, A/B): the direct kernels at any size
+  if ((mode != 5 && mode != 7) || p.K % 128 || p.C % 128 || p.K > 4096) return false;
+  if (mode == 7) return true;                                  // tests: the direct kernel at any size
   // one wave per job and at least 256 rows per split: a product with few rows (the pixel decoder at ONE image: 10 164 tokens x
   // 256 -> 256 is 4 tiles x 39 splits = 156 waves for 1024 SIMDs; forward + backward 8.4 -> 9.2 ms) keeps the workgroup-tile kernels
   const TnPlan pl = tn_plan_direct(p);
-  const long long slots = tn_mode() == 6 ? 2048 : 1024;
-  return pl.total * 4 >= slots * 3;
+  return pl.total * 4 >= 1024 * 3;
 }
-// plan of the LDS-free kernel: one WAVE per (position, split, tile); mode 5: 128 x 128 tiles, 1024 wave slots (one per SIMD);
-// mode 6: 64 x 128 tiles, 2048 slots
+// plan of the LDS-free kernel: one WAVE per (position, split, 128 x 128 tile), 1024 wave slots (one per SIMD)
 inline TnPlan tn_plan_direct(const MssConvArgs& p) {
   TnPlan pl;
-  const int kb = tn_mode() == 6 ? 64 : 128;
-  pl.ktiles = p.K / kb; pl.ctiles = p.C / 128;
+  pl.ktiles = p.K / 128; pl.ctiles = p.C / 128;
   const long long base = (long long)tn_batch(p) * pl.ktiles * pl.ctiles;
-  const int slots = tn_mode() == 6 ? 2048 : 1024;
+  const int slots = 1024;
   int max_splits = mss_cdiv(p.M, 256);
   // more tiles than slots, and the last round mostly empty: whole tiles for the full rounds, the rest cut so that they fill one
   // short round (the ASPP F(4x4) product: 2304 tiles = 2048 whole + 256 x 4 quarter jobs; only the 256 tail tiles are reduced)
-  if (tn_mode() != 6 && MSS_ENV_INT("MSS_WGRAD_TN_TAIL", 1) != 0 && base > slots && base % slots != 0 &&
+  if (MSS_ENV_INT("MSS_WGRAD_TN_TAIL", 1) != 0 && base > slots && base % slots != 0 &&
       (double)base / (double)(((base + slots - 1) / slots) * slots) < 0.95) {
     const long long tail = base % slots;
     int ts = (int)(slots / tail);
@@ -1476,11 +1448,11 @@ int launch_wgrad_tn(const MssConvArgs& p, const float* dy, float* dwp, int Cp, f
       const long long ntail = (pl.total - pl.full) / pl.splits;
       if (!ws || ws_bytes < tn_tail_bytes(pl)) return MSS_ERR_BAD_ARG;
       if (p.in_scale || p.in_shift || p.in_relu)
-        hipLaunchKernelGGL((gemm_tn_direct_kernel<4, true>), dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, dwp, P, p.M,
+        hipLaunchKernelGGL(gemm_tn_direct_kernel<true>, dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, dwp, P, p.M,
                            p.K, p.C, a_bs, b_bs, p.Kpad, Cp, pl.ktiles, pl.ctiles, pl.splits, pl.tps, pl.total, pl.full, ws, p.in_scale,
                            p.in_shift, p.in_relu, lddy);
       else
-        hipLaunchKernelGGL(gemm_tn_direct_kernel<4>, dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, dwp, P, p.M, p.K,
+        hipLaunchKernelGGL(gemm_tn_direct_kernel<false>, dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, dwp, P, p.M, p.K,
                            p.C, a_bs, b_bs, p.Kpad, Cp, pl.ktiles, pl.ctiles, pl.splits, pl.tps, pl.total, pl.full, ws, (const float*)nullptr,
                            (const float*)nullptr, 0, lddy);
       hipLaunchKernelGGL(tn_tail_reduce_kernel, dim3((unsigned)(ntail * 16)), dim3(256), 0, stream, ws, dwp, pl.full, ntail, pl.splits,
@@ -1489,15 +1461,12 @@ int launch_wgrad_tn(const MssConvArgs& p, const float* dy, float* dwp, int Cp, f
     }
     if (pl.splits > 1 && (!ws || ws_bytes < (long long)pl.splits * slab * 4)) return MSS_ERR_BAD_ARG;
     float* out = pl.splits > 1 ? ws : dwp;
-    if (tn_mode() == 6)
-      hipLaunchKernelGGL(gemm_tn_direct_kernel<2>, dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, out, P, p.M, p.K,
-                         p.C, a_bs, b_bs, p.Kpad, Cp, pl.ktiles, pl.ctiles, pl.splits, pl.tps, pl.total, -1ll, (float*)nullptr);
-    else if (p.in_scale || p.in_shift || p.in_relu)
-      hipLaunchKernelGGL((gemm_tn_direct_kernel<4, true>), dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, out, P, p.M,
+    if (p.in_scale || p.in_shift || p.in_relu)
+      hipLaunchKernelGGL(gemm_tn_direct_kernel<true>, dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, out, P, p.M,
                          p.K, p.C, a_bs, b_bs, p.Kpad, Cp, pl.ktiles, pl.ctiles, pl.splits, pl.tps, pl.total, -1ll, (float*)nullptr,
                          p.in_scale, p.in_shift, p.in_relu, lddy);
     else
-      hipLaunchKernelGGL(gemm_tn_direct_kernel<4>, dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, out, P, p.M, p.K,
+      hipLaunchKernelGGL(gemm_tn_direct_kernel<false>, dim3((unsigned)((pl.total + 3) / 4)), dim3(256), 0, stream, dy, p.x, out, P, p.M, p.K,
                          p.C, a_bs, b_bs, p.Kpad, Cp, pl.ktiles, pl.ctiles, pl.splits, pl.tps, pl.total, -1ll, (float*)nullptr,
                          (const float*)nullptr, (const float*)nullptr, 0, lddy);
     if (pl.splits > 1) {
@@ -1517,23 +1486,18 @@ int launch_wgrad_tn(const MssConvArgs& p, const float* dy, float* dwp, int Cp, f
     int dev = 0, n = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_tn_wgrad_kernel<false>, NT, smem) != hipSuccess || n < 1) n = 3;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_tn_wgrad_kernel, NT, smem) != hipSuccess || n < 1) n = 3;
     per_cu = n > 3 ? 3 : n;
   }
   const long long slots = (long long)(wide ? 2 : per_cu) * cus;
   const int grid = (int)(pl.total < slots ? pl.total : slots);
   float* out = pl.splits > 1 ? ws : dwp;
-  const int mode = tn_mode();
   if (wide) {
     const size_t smem2 = (size_t)2 * (128 + 256) * TN2_LDK * sizeof(float);
-    hipLaunchKernelGGL(gemm_tn2_wgrad_kernel<256>, dim3(grid), dim3(NT), smem2, stream, dy, p.x, out, P, p.M, p.K, p.C, a_bs,
-                       b_bs, p.Kpad, Cp, pl.ktiles, pl.ctiles, pl.splits, pl.tps, pl.total);
-  } else if (mode == 2) {
-    const size_t smem2 = (size_t)4 * 128 * TN2_LDK * sizeof(float);
-    hipLaunchKernelGGL(gemm_tn2_wgrad_kernel<128>, dim3(grid), dim3(NT), smem2, stream, dy, p.x, out, P, p.M, p.K, p.C, a_bs,
+    hipLaunchKernelGGL(gemm_tn2_wgrad_kernel, dim3(grid), dim3(NT), smem2, stream, dy, p.x, out, P, p.M, p.K, p.C, a_bs,
                        b_bs, p.Kpad, Cp, pl.ktiles, pl.ctiles, pl.splits, pl.tps, pl.total);
   } else {
-    hipLaunchKernelGGL(gemm_tn_wgrad_kernel<false>, dim3(grid), dim3(NT), smem, stream, dy, p.x, out, P, p.M, p.K, p.C, a_bs,
+    hipLaunchKernelGGL(gemm_tn_wgrad_kernel, dim3(grid), dim3(NT), smem, stream, dy, p.x, out, P, p.M, p.K, p.C, a_bs,
                        b_bs, p.Kpad, Cp, pl.ktiles, pl.ctiles, pl.splits, pl.tps, pl.total);
   }
   if (pl.splits > 1) {
@@ -1573,11 +1537,8 @@ int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
   // K-step: 16 (41 KB LDS, 144 registers -> 3 workgroups/CU, 3 waves/SIMD) is the faster choice except
   // for the ASPP shape (4096 input channels, 256 output channels), where the 32-deep step wins
   // (measured: 128 vs 119 TFLOP/s).
+  if (p.K <= 64) return launch_conv<256, 64, 16, 4, 1>(p, s);
   const bool k32 = p.C % 32 == 0 && p.C >= 2048 && p.K <= 256;
-  if (p.K <= 64) {
-    (void)k32;
-    return launch_conv<256, 64, 16, 4, 1>(p, s);
-  }
   return k32 ? launch_conv<128, 128, 32, 2, 2>(p, s) : launch_conv<128, 128, 16, 2, 2>(p, s);
 }
 

@@ -35,11 +35,10 @@ constexpr int NKC = BK / 8;
 
 static_assert(NKC == 2, "the step body below is written for two 8-k chunks");
 
-// VARIANT (A/B, MSS_GEMM_VARIANT): 0 = loads for K-step k+1 issued at the top of step k and written to LDS in the same step
-// (round 1); 1 = the same with the issue pinned at the loop top (the compiler otherwise sinks the four global loads behind
-// the first 16 MFMAs and the LDS reads, 9 MFMAs ahead of their first use); 2 = the loader runs TWO steps ahead with one
-// register set: step k first stores the registers (step k+1's data, requested a whole step ago) to LDS and immediately
-// re-issues them for step k+2, so no wave waits on a load it has just issued.
+// VARIANT (MSS_GEMM_VARIANT): 2 = the loader runs TWO steps ahead with one register set: step k first stores the registers
+// (step k+1's data, requested a whole step ago) to LDS and immediately re-issues them for step k+2, so no wave waits on a load it
+// has just issued; 3 = the same with 32-bit operand offsets (below). (Variants 0 and 1, the loads one step ahead, were removed
+// after round 6.)
 // BN: output-channel extent of a tile. 128 (2x2 waves of 64x64, 4 workgroups per CU) or 256 (2x2 waves of 64x128: 64 MFMAs
 // per wave and barrier instead of 32, a quarter less operand traffic per FLOP and half the per-tile prologue/epilogue
 // share, at 2 workgroups per CU).
@@ -219,43 +218,31 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
   issue_loads();
   finish_store(0);
   advance();
-  if (VARIANT >= 2) { issue_loads(); advance(); }      // registers now hold K-step 1
+  issue_loads(); advance();              // registers now hold K-step 1
   zero_acc();
   __syncthreads();
   load_frags(0, 0, 0);
   int buf = 0, k = 0;
   while (true) {
-    if (VARIANT >= 2) {
-      load_frags(1, buf, 1);
-      finish_store(buf ^ 1);             // K-step k+1, requested during step k-1
-      issue_loads();                     // K-step k+2 (possibly of the next tile) into the registers just drained
-      advance();
-      mfma_chunk(0);
-      if (VARIANT == 3) {
-        // one fragment read / LDS write / global load / pair of VALU-SALU behind each of the first MFMAs of the chunk
+    load_frags(1, buf, 1);
+    finish_store(buf ^ 1);             // K-step k+1, requested during step k-1
+    issue_loads();                     // K-step k+2 (possibly of the next tile) into the registers just drained
+    advance();
+    mfma_chunk(0);
+    if (VARIANT == 3) {
+      // one fragment read / LDS write / global load / pair of VALU-SALU behind each of the first MFMAs of the chunk
 #pragma unroll
-        for (int i = 0; i < TM + TN; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
+      for (int i = 0; i < TM + TN; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
 #pragma unroll
-        for (int i = 0; i < A_LD + B_LD; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
+      for (int i = 0; i < A_LD + B_LD; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
 #pragma unroll
-        for (int i = 0; i < A_LD + B_LD; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x20, 1, 0); }
+      for (int i = 0; i < A_LD + B_LD; ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x20, 1, 0); }
 #pragma unroll
-        for (int i = 0; i < 4 * TM * TN - (TM + TN) - 2 * (A_LD + B_LD); ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x6, 2, 0); }
-      }
-      __syncthreads();
-      load_frags(0, buf ^ 1, 0);
-      mfma_chunk(1);
-    } else {
-      issue_loads();                       // K-step k+1 of this tile, or K-step 0 of the next one
-      if (VARIANT == 1) __builtin_amdgcn_sched_barrier(0);
-      load_frags(1, buf, 1);
-      finish_store(buf ^ 1);
-      mfma_chunk(0);
-      __syncthreads();
-      load_frags(0, buf ^ 1, 0);
-      mfma_chunk(1);
-      advance();
+      for (int i = 0; i < 4 * TM * TN - (TM + TN) - 2 * (A_LD + B_LD); ++i) { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x6, 2, 0); }
     }
+    __syncthreads();
+    load_frags(0, buf ^ 1, 0);
+    mfma_chunk(1);
     buf ^= 1;
     if (++k == n_it) {
       epilogue(cur);
@@ -397,22 +384,18 @@ int mss_gemm_nt_dispatch(MssConvArgs p, void* stream) {
   // r03: variant 3 (32-bit offsets, branch-free advance, loader instructions interleaved with the MFMAs) is +4-6 % from C = 256 up
   // (36 x 16384 x 256 -> 256: 125 -> 130, 512 -> 512: 128 -> 136, 1024 -> 2048: 133 -> 140, 1x1 2048 -> 4096: 139 -> 146 TFLOP/s) and
   // +0.5 % at C = 128, bit-identical results (tools/bench_gemm_variant.py, alternating A/B); shapes it does not take fall back to 2
-  int variant = 3;
-  variant = MSS_ENV_INT("MSS_GEMM_VARIANT", 3);
-  if (variant == 1) return p.in_scale ? launch_gemm<true, 1, 128>(p, s) : launch_gemm<false, 1, 128>(p, s);
-  // variant 3 addresses its operands with 32-bit byte offsets and needs >= 3 K-steps per tile (see the kernel)
+  // variant 3 addresses its operands with 32-bit byte offsets and needs >= 3 K-steps per tile (see the kernel); MSS_GEMM_VARIANT=2
+  // forces variant 2 everywhere (the reference of the bitwise test)
   const long long nb3 = p.batch > 1 ? p.batch : 1;
-  const bool v3 = variant == 3 && p.C / BK >= 3 &&
+  const bool v3 = MSS_ENV_INT("MSS_GEMM_VARIANT", 3) == 3 && p.C / BK >= 3 &&
                   (unsigned long long)((nb3 - 1) * p.x_bs + (long long)p.M * p.ldx) * 4ull < 0xffffffffull &&
                   (unsigned long long)((nb3 - 1) * p.w_bs + (long long)p.Kpad * p.C) * 4ull < 0xffffffffull;
-  if (variant == 0) return p.in_scale ? launch_gemm<true, 0, 128>(p, s) : launch_gemm<false, 0, 128>(p, s);
   // 256-wide tiles when the output channels split evenly, the reduction is long enough and there is work for two rounds of
   // the 512 slots. Measured (tools/bench_bgemm.py, bench_1x1.py): 1x1 2048 -> 4096
   // 127 -> 133, ASPP 4096 -> 256 123 -> 131, 1024 -> 2048 136 -> 138, C = 304 122 -> 126 TFLOP/s; C = 256: 122 -> 121 (not taken).
-  constexpr int bn = 0;                                  // (the A/B switch that forced one width went in round 6)
   const long long tiles256 = (long long)p.mtiles * (p.K / 256) * (p.batch > 1 ? p.batch : 1);
-  bool wide = p.K % 256 == 0 && (bn == 256 || (bn == 0 && tiles256 >= 1024 && p.C >= 256));
-  if (wide && bn == 0) {
+  bool wide = p.K % 256 == 0 && tiles256 >= 1024 && p.C >= 256;
+  if (wide) {
     // ... unless the last round of wide tiles is mostly idle while the narrow tiles fill theirs: 64 x 18 x 1 wide tiles (ASPP
     // dilation 12 / 24 through F(6x6): 2304 tiles x 4096 -> 256) are 2.25 rounds of the 512 slots but exactly 3 rounds of the
     // 768 narrow slots -- measured 119.5 (wide) against 133.4 TFLOP/s (narrow)
@@ -441,7 +424,7 @@ int mss_gemm_nt_dispatch(MssConvArgs p, void* stream) {
     const long long full = (tiles256 / 512) * 512, rem = tiles256 - full;
     const int nw = p.K / 256;
     const long long rem_max = tail_mode == 1 ? 384 : (tail_mode == -1 && p.batch <= 1 && full <= 4 * 512) ? 384 : 0;
-    if (bn == 0 && full > 0 && rem > 0 && rem <= rem_max) {
+    if (full > 0 && rem > 0 && rem <= rem_max) {
       MssConvArgs q = p;
       q.ntiles = nw;
       int rc = v3 ? (p.in_scale ? launch_gemm<true, 3, 256>(q, s, 0, full) : launch_gemm<false, 3, 256>(q, s, 0, full))

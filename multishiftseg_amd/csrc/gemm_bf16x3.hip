@@ -1100,11 +1100,10 @@ bool mss_gemm_nt_bf16x3_eligible(const MssConvArgs& p) {
 // route does.
 int mss_gemm_nt_bf16x3_launch(MssConvArgs p, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  constexpr int bn = 0;                                  // (the A/B switch that forced one width went in round 6)
   const long long nb = p.batch > 1 ? p.batch : 1;
   const long long tiles256 = (long long)p.mtiles * (p.K / 256) * nb;
-  bool wide = p.K % 256 == 0 && (bn == 256 || (bn == 0 && tiles256 >= 1024 && p.C >= 256));
-  if (wide && bn == 0) {
+  bool wide = p.K % 256 == 0 && tiles256 >= 1024 && p.C >= 256;
+  if (wide) {
     auto eff = [](long long total, long long slots) {
       const long long rounds = (total + slots - 1) / slots;
       return (double)total / (double)(rounds * slots);

@@ -252,9 +252,4 @@ int mss_m2f_fused_score_ws_f32(const float* cls, const float* logit, int B, int 
   return mss_launch_status();
 }
 
-int mss_m2f_fused_score_f32(const float* cls, const float* logit, int B, int Q, int C, int hm, int wm, int ldq, int Hi,
-                            int Wi, int H, int W, float* score, void* stream) {
-  return mss_m2f_fused_score_ws_f32(cls, logit, B, Q, C, hm, wm, ldq, Hi, Wi, H, W, score, nullptr, stream);
-}
-
 }  // extern "C"

@@ -347,14 +347,8 @@ int mss_add_layernorm_bwd_f32(const float* gy, const float* x, const float* res,
   return launch_add_layernorm_bwd<false>(gy, x, res, stat, rows, C, gamma, dz, dgamma, dbeta, nullptr, ws, stream);
 }
 
-// the same with dzsum [C] = per-channel sums of dz (ws: 3/2 of mss_add_layernorm_bwd_workspace_floats)
-int mss_add_layernorm_bwd_sum_f32(const float* gy, const float* x, const float* res, const float* stat, long long rows, int C,
-                                  const float* gamma, float* dz, float* dgamma, float* dbeta, float* dzsum, float* ws, void* stream) {
-  if (!dzsum) return MSS_ERR_BAD_ARG;
-  return launch_add_layernorm_bwd<true>(gy, x, res, stat, rows, C, gamma, dz, dgamma, dbeta, dzsum, ws, stream);
-}
-
-// the same for an output with TWO consumers: the gradient is gy + gy2 (gy2 may be NULL), added while it is loaded
+// the same with dzsum [C] = per-channel sums of dz (ws: 3/2 of mss_add_layernorm_bwd_workspace_floats), for an output with TWO
+// consumers: the gradient is gy + gy2 (gy2 may be NULL), added while it is loaded
 int mss_add_layernorm_bwd_sum2_f32(const float* gy, const float* gy2, const float* x, const float* res, const float* stat, long long rows,
                                    int C, const float* gamma, float* dz, float* dgamma, float* dbeta, float* dzsum, float* ws,
                                    void* stream) {

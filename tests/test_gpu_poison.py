@@ -258,7 +258,7 @@ def test_dgrad_and_wgrad(K, cin, cout, r, dil, n, h, w, gemm_route):
 
 WGRAD_ROUTES = [
     # mode (MSS_WGRAD_TN), P, T, C, Ko: the batched Winograd-domain weight-gradient kernels (test_batched_wgrad_routes_vs_float64)
-    ("0", 3, 700, 512, 128), ("1", 2, 1000, 256, 72), ("2", 4, 37, 768, 256), ("4", 3, 700, 512, 128), ("6", 2, 1000, 256, 72),
+    ("0", 3, 700, 512, 128), ("1", 2, 1000, 256, 72), ("1", 4, 37, 768, 256), ("4", 3, 700, 512, 128), ("4", 2, 1000, 256, 72),
     ("7", 4, 37, 768, 256), ("5", 36, 1100, 1024, 256),
 ]
 

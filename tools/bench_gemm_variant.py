@@ -1,5 +1,5 @@
-"""A/B of gemm_nt variants (MSS_GEMM_VARIANT=2 shipped in r02, 3 = r03 branch-free loader + interleave, 4 = 3 with swapped MFMA
-operands and 16-byte stores) on the step's products.  python tools/bench_gemm_variant.py [a,b]   (default 2,3)"""
+"""A/B of the two gemm_nt loader variants (MSS_GEMM_VARIANT=2: pointers, the r02 loader; 3: 32-bit offsets, branch-free advance
+and interleave, r03) on the step's products.  python tools/bench_gemm_variant.py [a,b]   (default 2,3)"""
 import sys, os, json, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
