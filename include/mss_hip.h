@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 9      /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 10     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -29,7 +29,9 @@ extern "C" {
                                   7 (round 5): MssConvArgs.w_split + mss_gemm_split_weights_bf16x3 (the split-bf16 GEMM route);
                                   8 (round 6): mss_msda_forward_window_f32 removed (the measured-slower LDS-window forward left the product); additive: the mss_oodm_*lanes* entry points,
                                   mss_gemm_split_last_mfma;
-                                  9: mss_oodm_compact_f32, mss_oodm_compact_packed_f32, mss_add_layernorm_bwd_sum_f32 and mss_m2f_fused_score_f32 removed (uncalled) */
+                                  9: mss_oodm_compact_f32, mss_oodm_compact_packed_f32, mss_add_layernorm_bwd_sum_f32 and mss_m2f_fused_score_f32 removed (uncalled);
+                                  10 (additive): MssConvArgs.k_steps / w_img_stride appended, mss_chan_compact_index, mss_chan_compact_act_f32,
+                                  mss_chan_compact_weights_f32 (Dropout2d-zeroed input channels skipped in the trunk's 1x1 products) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -161,9 +163,37 @@ typedef struct MssConvArgs {
                            /*   >= 48 input channels); other shapes run the native fp32 kernels on `w` (which must always be set).   */
   int route;               /* 0: native fp32 MFMA. 1: mss_conv2d_wgrad_f32 evaluates the TN product the same split-bf16 way (both    */
                            /*   operands split in the loader) where K % 128 == 0 and C % 256 == 0; other shapes stay native.         */
+  const int* k_steps;      /* optional (DEVICE, [N]): per-image reduction length of a 1x1 product over channel-compacted operands   */
+  long long w_img_stride;  /*   (mss_chan_compact_*): image n runs k_steps[n] 16-deep K-steps (>= 3, 16 * k_steps[n] <= C) over the  */
+                           /*   weights at w + n * w_img_stride floats. No prologue, no batch, OH * OW % 128 == 0, > 64 output       */
+                           /*   channels, native route only; MSS_ERR_UNSUPPORTED otherwise (there is no other kernel for it).         */
 } MssConvArgs;
 
 int mss_conv2d_forward_f32(MssConvArgs* args, void* stream);
+/* Per-sample channel compaction (csrc/chan_compact.hip) for a 1x1 product whose prologue is a Dropout2d-folded per-sample affine
+ * (wider_resnet.py:161-162: Dropout2d between bn3 and conv3 of the two bottleneck blocks): the dropped channels of a sample are exact
+ * zeros after the prologue, so sample n only multiplies its K_n kept channels. C % 16 == 0, 48 <= C (<= 2048 for the two row passes).
+ *   index:   mask [N][C] (any value != 0: kept) -> idx [N][C] int32, of which the first K_n entries of row n are written: the kept
+ *            channel numbers in ascending order; count [N] = K_n; k_steps [N] = max(3, ceil(K_n / 16)) (MssConvArgs.k_steps);
+ *            place [N][C] int32, written whole: place[n][p] = the channel whose values go to column p of sample n's compacted rows,
+ *            or -1. The kept channels occupy the first 8 * ceil(K_n / 8) columns in the order in which the GEMM kernel's chain of
+ *            fused multiply-adds visits them in the DENSE product (per 8-deep chunk: k = 0, 4, 1, 5, 2, 6, 3, 7), so that the
+ *            compacted product adds the same terms in the same order: bit-identical to the dense one for finite weights.
+ *            One launch, no atomics, deterministic.
+ *   act:     x rows [N * rows_per_image][ldx] -> out (pitch ldout >= C, out != x): out[row][p] = relu(x[row][c] * scale[n][c] +
+ *            shift[n][c]) with c = place[n][p], 0 where place[n][p] < 0, for p < 16 * k_steps[n]; later columns are not written.
+ *            The arithmetic is the prologue's of the persistent GEMM kernel, so the operand values are the ones the dense product sees.
+ *   weights: packed w [Kpad][C] -> out [N][Kpad][C]: out[n][k][p] = w[k][place[n][p]], same zero fill, later columns not written.
+ * idx entries from K_n on are never written or read. All float pointers 16-byte aligned. */
+/* 1 when a 1x1 product with these (dense) arguments -- per-sample prologue affine + ReLU as the Dropout2d fold builds it -- qualifies
+ * for the compacted form and MSS_DROPOUT_COMPACT (default 1) is not 0: stride 1, no padding, OH * OW % 128 == 0, 64 < K, Kpad % 128
+ * == 0, 48 <= C <= 2048, ldx == C, no batch, no epilogue affine, native route (w_split NULL), operands within 32-bit byte offsets. */
+int mss_chan_compact_wanted(const MssConvArgs* args);
+int mss_chan_compact_index(const float* mask, int N, int C, int* idx, int* place, int* count, int* k_steps, void* stream);
+int mss_chan_compact_act_f32(const float* x, int ldx, float* out, int ldout, int N, int rows_per_image, int C, const int* place,
+                             const int* k_steps, const float* scale, const float* shift, void* stream);
+int mss_chan_compact_weights_f32(const float* w, float* out, int N, int Kpad, int C, const int* place, const int* k_steps,
+                                 void* stream);
 int mss_conv2d_kpad(int K);
 /* 1 if mss_conv2d_forward_f32 runs these arguments on the persistent GEMM kernel (csrc/gemm.hip: 1x1, stride 1,
  * more than 64 output channels, or 33..64 of them over >= 16 384 rows), 2 for the few-rows kernel (1x1 over <= 8 pixels, nothing fused), 3 for the

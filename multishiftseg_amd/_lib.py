@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 9          # include/mss_hip.h
+MSS_ABI_VERSION = 10         # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -48,6 +48,7 @@ class MssConvArgs(Structure):
         ("res_mask", c_int),
         ("w_split", c_void_p),
         ("route", c_int),
+        ("k_steps", c_void_p), ("w_img_stride", c_longlong),
     ]
 
 
@@ -87,6 +88,10 @@ SIGNATURES = {
     "mss_msda_forward_fused_save_f32": [P, P, P, P, L, P, L, P, I, I, I, I, I, I, I, P, P, P, P],
     "mss_msda_prepare_ld_f32": [P, L, P, L, P, P, I, I, I, I, I, P, P, P],
     "mss_conv2d_forward_f32": [POINTER(MssConvArgs), P],
+    "mss_chan_compact_wanted": [POINTER(MssConvArgs)],
+    "mss_chan_compact_index": [P, I, I, P, P, P, P, P],
+    "mss_chan_compact_act_f32": [P, I, P, I, I, I, I, P, P, P, P, P],
+    "mss_chan_compact_weights_f32": [P, P, I, I, I, P, P, P],
     "mss_conv2d_kpad": [I],
     "mss_conv2d_forward_route": [POINTER(MssConvArgs)],
     "mss_gemm_split_last_mfma": [],
@@ -183,7 +188,7 @@ SIGNATURES = {
     "mss_peak_scatter_f32": [P, P, L, I, I, L, P],
 }
 # entry points that return a plain value rather than a status code
-_VALUE_RETURNING = {"mss_gemm_split_last_mfma", "mss_conv2d_wgrad_route", "mss_gemm_split_weights_bytes", "mss_abi_version", "mss_env_reset", "mss_env_generation", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_conv2d_kpad", "mss_conv2d_forward_route", "mss_rcl_num_compact_blocks", "mss_wino_num_tiles",
+_VALUE_RETURNING = {"mss_chan_compact_wanted", "mss_gemm_split_last_mfma", "mss_conv2d_wgrad_route", "mss_gemm_split_weights_bytes", "mss_abi_version", "mss_env_reset", "mss_env_generation", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_conv2d_kpad", "mss_conv2d_forward_route", "mss_rcl_num_compact_blocks", "mss_wino_num_tiles",
                     "mss_oodm_sort_temp_bytes", "mss_oodm_compact_lanes_cap", "mss_oodm_rank_blocks", "mss_wino_output_stats_parts",
                     "mss_conv2d_wgrad_workspace_bytes", "mss_col_reduce_accum_doubles", "mss_colsum_workspace_floats",
                     "mss_add_layernorm_bwd_workspace_floats", "mss_groupnorm_workspace_floats",

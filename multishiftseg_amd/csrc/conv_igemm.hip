@@ -1529,6 +1529,10 @@ int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
   // read per call (not cached): the parity tests switch routes inside one process (MSS_GEMM=0: every layer on the
   // implicit-GEMM kernel; tests/test_gpu_fullsize.py compares it with the GEMM/Winograd routes)
   const int use_gemm = MSS_ENV_INT("MSS_GEMM", 1);
+  if (p.k_steps) {                 // per-image reduction lengths (csrc/chan_compact.hip): gemm_nt_kernel is the only kernel that has them
+    const int rc = mss_gemm_nt_dispatch(p, stream);
+    return rc >= 0 ? rc : MSS_ERR_UNSUPPORTED;
+  }
   if (use_gemm) {
     const int rc = mss_gemm_nt_dispatch(p, stream);
     if (rc >= 0) return rc;
@@ -1547,6 +1551,7 @@ int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
 int mss_conv2d_forward_route(const MssConvArgs* args) {
   MssConvArgs p = *args;
   p.M = p.N * p.OH * p.OW;
+  if (p.k_steps) return 1;
   if (!MSS_ENV_INT("MSS_GEMM", 1)) return mss_conv_bf16x3_eligible(p) ? 4 : 0;      // as the forward: MSS_GEMM=0 only skips the NT dispatch
   if (mss_gemm_few_rows(p)) return 2;                  // (0 implicit-GEMM kernel, 1 gemm_nt_kernel, 2 gemm_few_rows_kernel)
   if (!mss_gemm_nt_eligible(p)) return mss_conv_bf16x3_eligible(p) ? 4 : 0;

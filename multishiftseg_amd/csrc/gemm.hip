@@ -42,9 +42,15 @@ static_assert(NKC == 2, "the step body below is written for two 8-k chunks");
 // BN: output-channel extent of a tile. 128 (2x2 waves of 64x64, 4 workgroups per CU) or 256 (2x2 waves of 64x128: 64 MFMAs
 // per wave and barrier instead of 32, a quarter less operand traffic per FLOP and half the per-tile prologue/epilogue
 // share, at 2 workgroups per CU).
-template <bool AFFINE, int VARIANT, int BN>
+// PERIMG (variant 3, no prologue): the reduction length and the weights belong to the IMAGE a row tile lies in -- p.k_steps[img]
+// K-steps over the weights at p.w + img * p.w_img_stride, img = (mt * BM) / p.H (p.H = rows per image; tiles never straddle images).
+// The product behind csrc/chan_compact.hip: Dropout2d-zeroed input channels are compacted away per sample, so image n multiplies
+// only its kept channels. Both numbers are uniform over a tile: k_steps[img] is read where the tile's offsets are formed (setup_off),
+// the K-step body gains one scalar select.
+template <bool AFFINE, int VARIANT, int BN, bool PERIMG = false>
 __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvArgs p, long long first_tile, long long total_tiles,
                                                                         int tiles_per_batch, int group_m) {
+  static_assert(!PERIMG || (VARIANT == 3 && !AFFINE), "the per-image mode exists on the variant-3 kernel without prologue only");
   constexpr int WTN = BN / 2, TN = WTN / 32, B_LD = BN / RPP;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                       // [2][BM][LDK]
@@ -54,6 +60,7 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
   const int chunk = tid % CPR, row0 = tid / CPR;
   const int wchunk = (chunk + (row0 >> 2)) & 3;          // RPP = 64 rows per pass: (row0 + j * 64) >> 2 has the same low bits
   const int n_it = p.C / BK;
+  int cur_nit = n_it, ld_nit = n_it, nit_nxt = n_it;   // PERIMG: K-steps of the tile being multiplied / the loader is in / enters next
   const long long stride = gridDim.x;
   const float relu_floor = p.in_relu ? 0.f : -__builtin_huge_valf();
 
@@ -70,7 +77,7 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
   const float* h_ptr = p.in_shift;
   long long ld_tile = first_tile + mss_xcd_remap(blockIdx.x, gridDim.x);   // this launch walks tiles [first_tile, total_tiles)
   int ld_k = 0;
-  auto setup_off = [&](long long t, unsigned* ao, unsigned* bo, unsigned& so) {
+  auto setup_off = [&](long long t, unsigned* ao, unsigned* bo, unsigned& so, int& nit) {
     const int b = (int)(t / tiles_per_batch);
     const int v = (int)(t - (long long)b * tiles_per_batch);
     int mt, nt; mss_tile_mn(v, p.mtiles, p.ntiles, group_m, mt, nt);
@@ -83,10 +90,17 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
 #pragma unroll
     for (int j = 0; j < B_LD; ++j)
       bo[j] = (unsigned)(((size_t)b * p.w_bs + (size_t)(nt * BN + row0 + j * RPP) * p.C + chunk * 4) * sizeof(float));
+    if (PERIMG) {
+      const int img = (mt * BM) / p.H;
+      nit = p.k_steps[img];
+      const unsigned wo = (unsigned)((size_t)img * (size_t)p.w_img_stride * sizeof(float));
+#pragma unroll
+      for (int j = 0; j < B_LD; ++j) bo[j] += wo;
+    }
     if (AFFINE) so = (unsigned)(((size_t)((mt * BM) / p.H) * p.in_ss_stride + chunk * 4) * sizeof(float));
   };
   auto setup = [&](long long t) {
-    if (VARIANT == 3) { setup_off(t, a_off, b_off, s_off); return; }
+    if (VARIANT == 3) { setup_off(t, a_off, b_off, s_off, ld_nit); return; }
     const int b = (int)(t / tiles_per_batch);
     const int v = (int)(t - (long long)b * tiles_per_batch);
     int mt, nt; mss_tile_mn(v, p.mtiles, p.ntiles, group_m, mt, nt);
@@ -108,7 +122,7 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
   };
   auto setup_next = [&]() {              // offsets of the tile the loader enters after its current one (past the end: the same)
     const long long t = ld_tile + stride;
-    setup_off(t < total_tiles ? t : ld_tile, a_nxt, b_nxt, s_nxt);
+    setup_off(t < total_tiles ? t : ld_tile, a_nxt, b_nxt, s_nxt, nit_nxt);
   };
   f32x4 areg[A_LD], breg[B_LD], sreg, hreg;
   auto issue_loads = [&]() {
@@ -136,13 +150,14 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
   };
   auto advance = [&]() {                 // next K-step of this tile, else first K-step of this workgroup's next tile
     if (VARIANT == 3) {
-      const bool wrap = ++ld_k == n_it;
+      const bool wrap = ++ld_k == (PERIMG ? ld_nit : n_it);
 #pragma unroll
       for (int j = 0; j < A_LD; ++j) a_off[j] = wrap ? a_nxt[j] : a_off[j] + BK * (unsigned)sizeof(float);
 #pragma unroll
       for (int j = 0; j < B_LD; ++j) b_off[j] = wrap ? b_nxt[j] : b_off[j] + BK * (unsigned)sizeof(float);
       if (AFFINE) s_off = wrap ? s_nxt : s_off + BK * (unsigned)sizeof(float);
       ld_k = wrap ? 0 : ld_k;
+      if (PERIMG) ld_nit = wrap ? nit_nxt : ld_nit;
       return;
     }
     if (++ld_k < n_it) {
@@ -214,6 +229,7 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
 
   long long cur = ld_tile;               // tile being multiplied (the launch guarantees cur < total_tiles)
   setup(ld_tile);
+  if (PERIMG) cur_nit = ld_nit;
   if (VARIANT == 3) setup_next();
   issue_loads();
   finish_store(0);
@@ -244,7 +260,7 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
     load_frags(0, buf ^ 1, 0);
     mfma_chunk(1);
     buf ^= 1;
-    if (++k == n_it) {
+    if (++k == (PERIMG ? cur_nit : n_it)) {
       epilogue(cur);
       cur += stride;
       if (cur >= total_tiles) break;
@@ -252,6 +268,7 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
       k = 0;
       if (VARIANT == 3) {                // the loader entered tile `cur` at least one K-step ago (n_it >= 3): prepare the one after it
         ld_tile = cur;
+        if (PERIMG) cur_nit = ld_nit;    // ... so ld_nit is tile `cur`'s
         setup_next();
       }
     }
@@ -287,7 +304,7 @@ __global__ __launch_bounds__(256) void gemm_few_rows_kernel(const float* __restr
   }
 }
 
-template <bool AFFINE, int VARIANT, int BN>
+template <bool AFFINE, int VARIANT, int BN, bool PERIMG = false>
 int launch_gemm(const MssConvArgs& p, hipStream_t stream, long long first = 0, long long end = -1) {
   const int batch = p.batch > 1 ? p.batch : 1;
   const int tiles_per_batch = p.mtiles * p.ntiles;
@@ -300,7 +317,7 @@ int launch_gemm(const MssConvArgs& p, hipStream_t stream, long long first = 0, l
     int dev = 0, n = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_nt_kernel<AFFINE, VARIANT, BN>, NT, smem) != hipSuccess || n < 1) n = 3;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_nt_kernel<AFFINE, VARIANT, BN, PERIMG>, NT, smem) != hipSuccess || n < 1) n = 3;
     per_cu_max = n;
   }
   // Every workgroup walks ceil(total / grid) tiles: pick the residency (per_cu_max or one less) whose last round is
@@ -316,7 +333,7 @@ int launch_gemm(const MssConvArgs& p, hipStream_t stream, long long first = 0, l
   }
   // the square-ish tile order only for whole launches: the hybrid wide + narrow split (MSS_GEMM_TAIL) relies on tile ranges
   const int group_m = (first == 0 && end == (long long)tiles_per_batch * batch) ? MSS_ENV_INT("MSS_GEMM_GROUP_M", GEMM_GROUP_M_DEFAULT) : 0;
-  hipLaunchKernelGGL((gemm_nt_kernel<AFFINE, VARIANT, BN>), dim3(grid), dim3(NT), smem, stream, p, first, end, tiles_per_batch, group_m);
+  hipLaunchKernelGGL((gemm_nt_kernel<AFFINE, VARIANT, BN, PERIMG>), dim3(grid), dim3(NT), smem, stream, p, first, end, tiles_per_batch, group_m);
   return mss_launch_status();
 }
 
@@ -363,6 +380,28 @@ int mss_gemm_nt_dispatch(MssConvArgs p, void* stream) {
     else if (p.M <= 16) hipLaunchKernelGGL(gemm_few_rows_kernel<16>, grid, dim3(256), 0, fs, p.x, p.ldx, p.w, p.y, p.ldy, p.M, p.C, p.K);
     else hipLaunchKernelGGL(gemm_few_rows_kernel<32>, grid, dim3(256), 0, fs, p.x, p.ldx, p.w, p.y, p.ldy, p.M, p.C, p.K);
     return mss_launch_status();
+  }
+  if (p.k_steps) {
+    // the per-image product behind csrc/chan_compact.hip: image n = rows [n * OH * OW, (n + 1) * OH * OW) runs k_steps[n] K-steps
+    // over its own weights w + n * w_img_stride. It exists on this kernel only (variant 3, no prologue: the compaction pass applied
+    // it), so a shape that does not qualify is an error, never another route.
+    if (!mss_gemm_nt_eligible(p) || p.in_scale || p.w_split || p.batch > 1 || p.K <= 64 || (p.OH * p.OW) % BM || p.C / BK < 3 ||
+        p.w_img_stride % 4 || p.w_img_stride < 0)
+      return MSS_ERR_UNSUPPORTED;
+    p.H = p.OH * p.OW;                                    // rows per image
+    p.mtiles = mss_cdiv(p.M, BM);
+    p.ntiles = mss_cdiv(p.K, 128);
+    if (p.Kpad < p.ntiles * 128) return MSS_ERR_BAD_ARG;
+    if ((unsigned long long)p.M * p.ldx * 4ull >= 0xffffffffull ||
+        (unsigned long long)((long long)(p.N - 1) * p.w_img_stride + (long long)p.Kpad * p.C) * 4ull >= 0xffffffffull)
+      return MSS_ERR_UNSUPPORTED;
+    hipStream_t ps = static_cast<hipStream_t>(stream);
+    // tile width: the dense rule below without its last-round refinements (the per-image step counts make rounds uneven anyway)
+    if (p.K % 256 == 0 && (long long)p.mtiles * (p.K / 256) >= 1024 && p.C >= 256) {
+      p.ntiles = p.K / 256;
+      return launch_gemm<false, 3, 256, true>(p, ps);
+    }
+    return launch_gemm<false, 3, 128, true>(p, ps);
   }
   if (!mss_gemm_nt_eligible(p)) return -1;
   p.H = (p.in_scale && p.in_ss_stride) ? p.OH * p.OW : (p.M > 0 ? p.M : 1);   // rows per affine group

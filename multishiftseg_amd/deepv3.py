@@ -184,16 +184,20 @@ class DeepWV3Plus(nn.Module):
                         "reference (exps/DeepLab.yaml:10-11) and has no backward kernels here")
 
     # ---- trunk ------------------------------------------------------------------------------------
-    def _dropout_affine(self, st, blk, name, n):
-        """Dropout2d on relu(bn(x)) == per-sample affine: relu(z)*m = relu(z*m) for m >= 0."""
+    def _dropout_affine(self, st, blk, name, n, want_mask=False):
+        """Dropout2d on relu(bn(x)) == per-sample affine: relu(z)*m = relu(z*m) for m >= 0. want_mask: (affine, mask [n, C] or None)."""
+        aff, mask = self._dropout_affine_mask(st, blk, name, n)
+        return (aff, mask) if want_mask else aff
+
+    def _dropout_affine_mask(self, st, blk, name, n):
         if blk.drop_p is None or not self.training:
-            return (st.scale, st.shift)
+            return (st.scale, st.shift), None
         if self.dropout_masks is not None:
             mask = self.dropout_masks[name].to(st.scale.device, torch.float32)
         else:
             keep = 1.0 - blk.drop_p
             mask = torch.bernoulli(torch.full((n, st.scale.numel()), keep, device=st.scale.device)) / keep
-        return ((st.scale[None, :] * mask).contiguous(), (st.shift[None, :] * mask).contiguous())
+        return ((st.scale[None, :] * mask).contiguous(), (st.shift[None, :] * mask).contiguous()), mask.contiguous()
 
     def _run_block(self, blk, a, name, out_stats=False):
         """out_stats: the block's output kernel leaves its per-64-row column sums even in eval mode (the trunk's last block: the ASPP
@@ -220,8 +224,12 @@ class DeepWV3Plus(nn.Module):
         o2 = K.conv3x3(o, c.conv2.weight, dil=d, in_affine=(st2.scale, st2.shift), in_relu=True, want_stats=train,
                        max_tile=cap)
         st3 = K.bn_fold(c.bn3[0], o2, train)
-        return K.conv2d(o2, K.packed(c.conv3.weight), in_affine=self._dropout_affine(st3, blk, name, a.N), in_relu=True,
-                        res=shortcut, want_stats=train or out_stats)
+        aff3, mask = self._dropout_affine(st3, blk, name, a.N, want_mask=True)
+        pw3 = K.packed(c.conv3.weight)
+        if mask is not None and K.dropout_compact_wanted(o2, pw3, aff3, shortcut):
+            # the dropped channels are exact zeros behind the prologue: each sample multiplies its kept channels only
+            return K.conv2d_dropped(o2, pw3, mask, aff3, res=shortcut, want_stats=train or out_stats)
+        return K.conv2d(o2, pw3, in_affine=aff3, in_relu=True, res=shortcut, want_stats=train or out_stats)
 
     def _run_trunk(self, inp):
         fused_stem = os.environ.get("MSS_STEM_FUSED", "1") != "0"

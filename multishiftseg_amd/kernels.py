@@ -320,6 +320,62 @@ def _conv_launch(x, pw, out, OH, OW, stride, dil, pad, in_affine, in_relu, out_a
         call("mss_conv2d_forward_f32", ctypes.byref(a))
 
 
+def dropout_compact_wanted(x, pw, in_affine, res=None):
+    """True where a 1x1 product with a Dropout2d-folded per-sample prologue takes the channel-compacted form (conv2d_dropped): the
+    library's gate -- MSS_DROPOUT_COMPACT (default 1), native route, per-sample affine + ReLU, 128-row tiles that cannot straddle
+    images, more than 64 output channels. Everything else keeps the dense per-sample prologue."""
+    if in_affine is None or in_affine[0].dim() != 2 or pw.tail is not None or x.ld != pw.Cp:
+        return False
+    a = _conv_args(x, pw, None, 1, 1, 0, in_affine, True, None, False, res)
+    a.OH, a.OW = x.H, x.W
+    return bool(_lib.value("mss_chan_compact_wanted", ctypes.byref(a)))
+
+
+def chan_compact_index(mask):
+    """mask [N][C] (device fp32, != 0: kept) -> (idx [N][C] int32: ascending kept channels in the first count[n] entries of row n,
+    count [N], k_steps [N] = max(3, ceil(count / 16)), place [N][C]: the channel that goes to each column of the compacted rows
+    or -1, in the order that makes the compacted product add its terms as the dense one does). One launch, nothing read back."""
+    N, C = mask.shape
+    assert mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous()
+    # int32 contents in float allocations: of `idx` only the first count[n] entries of a row are ever written or read
+    idx = torch.empty((N, C), device=mask.device, dtype=torch.float32).view(torch.int32)
+    place = torch.empty((N, C), device=mask.device, dtype=torch.float32).view(torch.int32)
+    meta = torch.empty((2, N), device=mask.device, dtype=torch.float32).view(torch.int32)
+    call("mss_chan_compact_index", ptr(mask), N, C, ptr(idx), ptr(place), ptr(meta[0]), ptr(meta[1]))
+    return idx, meta[0], meta[1], place
+
+
+def conv2d_dropped(x, pw, mask, in_affine, res=None, want_stats=False, out_relu=False):
+    """conv2d(x, pw, in_affine=(scale * mask, shift * mask) per sample, in_relu=True, res=res) with the products of the zeroed
+    channels left out: sample n's kept channels (mask[n] != 0) are compacted to the front of its rows (prologue applied on the way)
+    and of its own copy of the weights, and the GEMM kernel runs k_steps[n] K-steps on image n. The columns are ordered so that every
+    output element adds the kept terms in the dense product's order: the result is bit-identical to the dense form. Chosen on the device, per call:
+    no host synchronisation. in_affine: the mask-multiplied vectors the dense prologue would take."""
+    sc, sh = in_affine
+    N, C, dev = x.N, pw.Cp, x.buf.device
+    assert tuple(mask.shape) == (N, C) and tuple(sc.shape) == (N, C) and pw.R * pw.S == 1 and pw.tail is None
+    HW = x.H * x.W
+    _idx, count, k_steps, place = chan_compact_index(mask)
+    xc = Act.empty(N, x.H, x.W, C, dev, ld=x.ld)
+    wc = torch.empty((N, pw.Kpad, C), device=dev, dtype=torch.float32)
+    kept = float(count.sum().item()) if _profile is not None else 0.0       # profiling pass only: the EXECUTED work of this call
+    with _Timed("chan_compact", 4.0 * HW * (N * C + kept), ("act", N, x.H, x.W, C)):                # "flops" = algorithmic BYTES
+        call("mss_chan_compact_act_f32", x.ptr, x.ld, xc.ptr, xc.ld, N, HW, C, ptr(place), ptr(k_steps), ptr(sc), ptr(sh))
+    with _Timed("chan_compact", 4.0 * pw.Kpad * (C + kept), ("weights", N, pw.Kpad, C)):
+        call("mss_chan_compact_weights_f32", ptr(pw.t), ptr(wc), N, pw.Kpad, C, ptr(place), ptr(k_steps))
+    out = Act.empty(N, x.H, x.W, pw.K, dev, ld=_round_up(pw.K, 4))
+    a = _conv_args(xc, pw, out, 1, 1, 0, None, False, None, out_relu, res)
+    a.w, a.w_split = ptr(wc), None
+    a.k_steps, a.w_img_stride = ptr(k_steps), pw.Kpad * C
+    a.OH, a.OW, a.ldy = x.H, x.W, out.ld
+    if want_stats:
+        out.stats = torch.empty((-(-(N * HW) // 64), 2, pw.K), device=dev, dtype=torch.float32)
+        a.stats = ptr(out.stats)
+    with _Timed(_fwd_kind(a), 2.0 * HW * pw.K * kept, (N, x.H, x.W, int(kept / N), pw.K, 1, 1, 1)):
+        call("mss_conv2d_forward_f32", ctypes.byref(a))
+    return out
+
+
 def _wgrad_workspace(a, Cp, device):
     """Scratch for the partial slabs of a pixel-split weight gradient (deterministic two-stage sum)."""
     nbytes = _lib.value("mss_conv2d_wgrad_workspace_bytes", ctypes.byref(a), Cp)
