@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 10     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 11     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -31,7 +31,9 @@ extern "C" {
                                   mss_gemm_split_last_mfma;
                                   9: mss_oodm_compact_f32, mss_oodm_compact_packed_f32, mss_add_layernorm_bwd_sum_f32 and mss_m2f_fused_score_f32 removed (uncalled);
                                   10 (additive): MssConvArgs.k_steps / w_img_stride appended, mss_chan_compact_index, mss_chan_compact_act_f32,
-                                  mss_chan_compact_weights_f32 (Dropout2d-zeroed input channels skipped in the trunk's 1x1 products) */
+                                  mss_chan_compact_weights_f32 (Dropout2d-zeroed input channels skipped in the trunk's 1x1 products);
+                                  11 (additive): mss_m2f_attn_mask_bits_f32, mss_m2f_masked_attention_f32, mss_m2f_attn_workspace_bytes
+                                  (the masked cross-attention of the Mask2Former GMA transformer decoder) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -491,6 +493,32 @@ int mss_adam_step_f32(float* param, const float* grad, float* exp_avg, float* ex
  * on the vector ALUs; results agree with the all-VALU form to fp32 summation order. prob_ws NULL = the all-VALU form. */
 int mss_m2f_fused_score_ws_f32(const float* cls, const float* logit, int B, int Q, int C, int hm, int wm, int ldq, int Hi,
                                int Wi, int H, int W, float* score, float* prob_ws, void* stream);
+
+/* Masked attention of the Mask2Former GMA transformer decoder (mask2former_transformer_decoder.py:75-121, 438-542; csrc/m2f_attn.hip).
+ *
+ * mss_m2f_attn_mask_bits_f32: logit = pixel-major low-resolution mask logits [B, hm*wm, ldq] (queries contiguous, Q <= 128,
+ * ldq >= Q). Resamples them to (h, w) as F.interpolate(mode="bilinear", align_corners=False) does and writes
+ *   bits    [B][2][h*w][W] 32-bit words, W = ceil(Q / 32): bit q of row [b][0][key] set <=> logit < 0 (key masked for the
+ *           foreground attention: sigmoid(x) < 0.5), of row [b][1][key] set <=> logit > 0 (masked for the background attention);
+ *           a logit of exactly 0 is masked in neither;
+ *   allowed [B][2][W] words: bit q set <=> query q has at least one un-masked key (cleared by this call before the launch). A
+ *           query whose bit is clear ignores its mask in mss_m2f_masked_attention_f32: the reference's
+ *           attn_mask[where(attn_mask.sum(-1) == HW)] = False (:476-477) without the host round trip.
+ * The mask is shared by the 8 heads.
+ *
+ * mss_m2f_masked_attention_f32: out[b, q, a, head, :] = softmax_key(scale * <q, k> + mask) v for 8 heads of 32 channels and A
+ * attentions in one launch. q [B*Q, ldq], k [B*NK, ldk], v [B*NK, ldv], out [B*Q, ldo] row-major fp32; attention a, head hd use
+ * columns a*256 + hd*32 .. +31 of each (ld* >= A*256, multiples of 4, 16-byte aligned bases). bits / allowed: as written above
+ * with A attentions per image ([B][A][NK][W], [B][A][W]); NULL bits = no mask (the self-attention among the queries).
+ * The key range is split into `chunks` pieces (rounded to 8 keys; 1 = one pass, no workspace); each piece leaves numerators,
+ * maximum and denominator in `ws` (>= mss_m2f_attn_workspace_bytes(B, Q, A, chunks) bytes, contents irrelevant on entry) and a
+ * second kernel merges the pieces in index order: no float atomics, bit-reproducible for a given chunk count. Q <= 128. */
+int mss_m2f_attn_mask_bits_f32(const float* logit, int B, int Q, int ldq, int hm, int wm, int h, int w, uint32_t* bits,
+                               uint32_t* allowed, void* stream);
+long long mss_m2f_attn_workspace_bytes(int B, int Q, int A, int chunks);
+int mss_m2f_masked_attention_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const uint32_t* bits,
+                                 const uint32_t* allowed, int B, int Q, int NK, int A, float scale, int chunks, float* ws,
+                                 float* out, int ldo, void* stream);
 
 /* Pixel-level OOD metrics on the device (csrc/metric.hip): exact AUROC / average precision / FPR at `recall_level`
  * over all pixels with label id_out (positives) and id_in (negatives). Replaces eval_ood_measure, get_measures and

@@ -1,0 +1,12 @@
+"""multishiftseg_amd: the MultiShiftSeg networks on hand-written HIP kernels for the MI355X. Sub-modules are imported on demand
+(`from multishiftseg_amd import kernels`); the names below are the package's module-level mirrors of reference classes."""
+
+
+def __getattr__(name):
+    if name == "MultiScaleMaskedTransformerDecoder_GMA":
+        from .transformer_decoder import MultiScaleMaskedTransformerDecoder_GMA
+        return MultiScaleMaskedTransformerDecoder_GMA
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+__all__ = ["MultiScaleMaskedTransformerDecoder_GMA"]

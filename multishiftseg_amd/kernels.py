@@ -1121,19 +1121,80 @@ def m2f_mask_logits(mask_embed, mask_features):
     Bf, Cf, h, w = mask_features.shape
     if (B, C) != (Bf, Cf):
         raise ValueError(f"mask_embed {tuple(mask_embed.shape)} does not match mask_features {tuple(mask_features.shape)}")
-    x = Act.from_nchw(mask_features.float())
-    Kpad = _lib.value("mss_conv2d_kpad", Q)
+    return m2f_mask_logits_act(mask_embed, Act.from_nchw(mask_features.float()), Q)
+
+
+def m2f_mask_logits_act(mask_embed, x, ldq):
+    """m2f_mask_logits on mask features that are already an Act [B, h, w, C] (the transformer decoder converts them once for
+    its 10 mask predictions) -> [B, h, w, ldq]; ldq >= Q pads the query axis (columns Q .. ldq-1 are written as zeros)."""
+    B, Q, C = mask_embed.shape
+    h, w = x.H, x.W
+    if (B, C) != (x.N, x.C) or ldq < Q:
+        raise ValueError(f"mask_embed {tuple(mask_embed.shape)} does not match mask features [{x.N}, {h}, {w}, {x.C}] / ldq {ldq}")
+    Kpad = _lib.value("mss_conv2d_kpad", ldq)
     wp = torch.zeros((B, Kpad, C), device=x.buf.device, dtype=torch.float32)
     wp[:, :Q] = mask_embed.detach().float()
-    out = torch.empty((B, h, w, Q), device=x.buf.device, dtype=torch.float32)
+    out = torch.empty((B, h, w, ldq), device=x.buf.device, dtype=torch.float32)
     a = MssConvArgs()
     a.x, a.w, a.y = x.ptr, ptr(wp), ptr(out)
     a.N, a.H, a.W, a.C, a.ldx = 1, 1, h * w, C, x.ld
-    a.OH, a.OW, a.K, a.Kpad, a.ldy = 1, h * w, Q, Kpad, Q
+    a.OH, a.OW, a.K, a.Kpad, a.ldy = 1, h * w, ldq, Kpad, ldq
     a.R, a.S, a.stride, a.dil, a.pad = 1, 1, 1, 1, 0
-    a.batch, a.x_bs, a.w_bs, a.y_bs = B, h * w * x.ld, Kpad * C, h * w * Q
+    a.batch, a.x_bs, a.w_bs, a.y_bs = B, h * w * x.ld, Kpad * C, h * w * ldq
     with _Timed(_fwd_kind(a), 2.0 * B * h * w * C * Q, (B, 1, h * w, C, Q, 1, 1, 1)):
         call("mss_conv2d_forward_f32", ctypes.byref(a))
+    return out
+
+
+# ---- masked attention of the Mask2Former transformer decoder (csrc/m2f_attn.hip) ----------------------------------------------
+def m2f_attn_mask_bits(mask_logits_nhwc, Q, size):
+    """Pixel-major mask logits [B, hm, wm, ldq] -> (bits [B, 2, h*w, W], allowed [B, 2, W]) int32 views, W = ceil(Q / 32):
+    the foreground (logit < 0) / background (logit > 0) attention masks of a level of `size` = (h, w) as bit rows over the
+    queries, and per query the "some key is allowed" bits (include/mss_hip.h). Both live in one float32-typed buffer."""
+    B, hm, wm, ldq = mask_logits_nhwc.shape
+    h, w = size
+    if not mask_logits_nhwc.is_cuda or mask_logits_nhwc.dtype != torch.float32:
+        raise RuntimeError("m2f_attn_mask_bits runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    lg = mask_logits_nhwc.contiguous()
+    W = (Q + 31) // 32
+    words = torch.empty(B * 2 * (h * w + 1) * W, device=lg.device, dtype=torch.float32).view(torch.int32)
+    bits = words[:B * 2 * h * w * W].view(B, 2, h * w, W)
+    allowed = words[B * 2 * h * w * W:].view(B, 2, W)
+    call("mss_m2f_attn_mask_bits_f32", ptr(lg), B, Q, ldq, hm, wm, h, w, ptr(bits), ptr(allowed))
+    return bits, allowed
+
+
+def m2f_attn_chunks(B, A, NK):
+    """Pieces the key range is cut into so that 8 heads x A attentions x B images x pieces is ~2048 workgroups (two waves each:
+    ~4 waves per SIMD of the 256 CUs), never less than 64 keys a piece."""
+    return max(1, min(-(-NK // 64), 2048 // (8 * A * B)))
+
+
+def m2f_masked_attention(q, k, v, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, out=None, scale=None, ws=None):
+    """softmax(scale q k^T + mask) v for 8 heads of 32 channels and A attentions side by side: q [B*Q, >= A*256], k / v
+    [B*NK, >= A*256] (row-major 2-d, attention a in columns a*256 ...), -> out [B*Q, A*256]. bits / allowed: from
+    m2f_attn_mask_bits (or [B, A, NK, W] / [B, A, W] int32 made by hand); None = no mask. chunks: pieces of the key range
+    (default m2f_attn_chunks); ws: the float32 chunk workspace (allocated here when None; its contents do not matter)."""
+    for t in (q, k, v):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise RuntimeError("m2f_masked_attention takes row-major 2-d float32 CUDA tensors (there is no CPU path)")
+    if q.shape[0] != B * Q or k.shape[0] != B * NK or v.shape[0] != B * NK:
+        raise ValueError(f"rows {q.shape[0]} / {k.shape[0]} / {v.shape[0]} do not match B {B}, Q {Q}, NK {NK}")
+    if (bits is None) != (allowed is None):
+        raise ValueError("bits and allowed come together")
+    if bits is not None:
+        W = (Q + 31) // 32
+        if tuple(bits.shape) != (B, A, NK, W) or tuple(allowed.shape) != (B, A, W) or not bits.is_contiguous() or not allowed.is_contiguous() \
+                or bits.dtype != torch.int32 or allowed.dtype != torch.int32:
+            raise ValueError(f"bits {tuple(bits.shape)} / allowed {tuple(allowed.shape)} must be contiguous int32 [{B}, {A}, {NK}, {W}] / [{B}, {A}, {W}]")
+    if chunks is None:
+        chunks = m2f_attn_chunks(B, A, NK)
+    if out is None:
+        out = torch.empty((B * Q, A * 256), device=q.device, dtype=torch.float32)
+    if ws is None and chunks > 1:
+        ws = torch.empty(_lib.value("mss_m2f_attn_workspace_bytes", B, Q, A, chunks) // 4, device=q.device, dtype=torch.float32)
+    call("mss_m2f_masked_attention_f32", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(bits), ptr(allowed),
+         B, Q, NK, A, float(scale if scale is not None else 32 ** -0.5), chunks, ptr(ws), ptr(out), out.stride(0))
     return out
 
 
