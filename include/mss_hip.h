@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 11     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 12     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -33,7 +33,10 @@ extern "C" {
                                   10 (additive): MssConvArgs.k_steps / w_img_stride appended, mss_chan_compact_index, mss_chan_compact_act_f32,
                                   mss_chan_compact_weights_f32 (Dropout2d-zeroed input channels skipped in the trunk's 1x1 products);
                                   11 (additive): mss_m2f_attn_mask_bits_f32, mss_m2f_masked_attention_f32, mss_m2f_attn_workspace_bytes
-                                  (the masked cross-attention of the Mask2Former GMA transformer decoder) */
+                                  (the masked cross-attention of the Mask2Former GMA transformer decoder);
+                                  12: two entry points removed, one signature changed: mss_rcl_select_f32 is the 5-launch selection (scratch, scratch_zeroed) and
+                                  its 9-launch form and second name are gone; the two-launch Feistel pairs entry point that mss_rcl_pairs_device2_f32 replaced
+                                  in version 5 is gone */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -381,7 +384,7 @@ int mss_m2f_score_f32(const float* cls, const float* mask, int B, int Q, int C, 
 
 /* Fused RelContrastiveLoss (lib/loss.py:34-156): value AND both gradients in a few streaming passes.
  * The host side (multishiftseg_amd/loss.py) owns the workspaces and the call order:
- *   pass1 -> select -> pass2 -> compact -> cin_bwd -> pairs x2 -> finalize
+ *   pass1 -> select -> pass2 -> compact -> cin_bwd -> pairs x2 (device pairing: pairs_device2 once) -> finalize
  * Nothing here synchronises with the host; every normaliser is read from device counters. */
 typedef struct MssRclArgs {
   const float* logit;      /* [B,C,H,W] NCHW                                          */
@@ -404,18 +407,16 @@ typedef struct MssRclArgs {
 int mss_rcl_pass1_f32(const MssRclArgs* a, float* lse, float* ce_aug, uint8_t* kind, double* counters, float* dlogit,
                       void* stream);
 /* exact k-th smallest of ce_aug, k = int(float32(ratio) * float32(n_in_aug)) as torch computes
- * it (loss.py:98-99); replaces torch.topk (loss.py:102). hist_ws: uint32[256]; sel: uint32[8]
- * = {threshold key, n_less, k, n_equal_to_take, tie tickets, ...}. */
-int mss_rcl_select_f32(const float* ce_aug, long long n, const double* counters, float selection_ratio,
-                       uint32_t* hist_ws, uint32_t* sel, void* stream);
-/* the same selection, bit-identical sel[0..3], in 5 launches instead of 9 (each pick rides in front of the next byte's histogram
- * pass): what mss_rcl_loss_device_f32 runs. scratch: MSS_RCL_SELECT_SCRATCH_WORDS uint32 (four histograms + two state buffers),
- * cleared by the call unless scratch_zeroed != 0. */
+ * it (loss.py:98-99); replaces torch.topk (loss.py:102). sel: uint32[8]
+ * = {threshold key, n_less, k, n_equal_to_take, tie tickets, ...}. 5 launches (each digit's pick rides in front of the next byte's
+ * histogram pass): what mss_rcl_loss_device_f32 runs. scratch: MSS_RCL_SELECT_SCRATCH_WORDS uint32 (four histograms + two state
+ * buffers), cleared by the call unless scratch_zeroed != 0. */
 #define MSS_RCL_SELECT_SCRATCH_WORDS (4 * 256 + 16)
-int mss_rcl_select_merged_f32(const float* ce_aug, long long n, const double* counters, float selection_ratio,
-                              uint32_t* scratch, int scratch_zeroed, uint32_t* sel, void* stream);
-/* the same selection one radix pass at a time (shift = 24, 16, 8, 0): a data-parallel caller
- * all-reduces the 256-bin histogram between hist and pick -> exact GLOBAL k-th smallest. */
+int mss_rcl_select_f32(const float* ce_aug, long long n, const double* counters, float selection_ratio,
+                       uint32_t* scratch, int scratch_zeroed, uint32_t* sel, void* stream);
+/* the same selection (same histogram and pick code, bit-identical sel[0..3]) one radix pass at a time (shift = 24, 16, 8, 0): a
+ * data-parallel caller all-reduces the 256-bin histogram between hist and pick -> exact GLOBAL k-th smallest. hist_ws: uint32[256],
+ * zeroed by init and by every pick. */
 int mss_rcl_select_init_f32(const double* counters, float selection_ratio, uint32_t* hist_ws, uint32_t* sel,
                             void* stream);
 int mss_rcl_select_hist_f32(const float* ce_aug, long long n, const uint32_t* sel, int shift, uint32_t* hist_ws,
@@ -443,14 +444,10 @@ int mss_rcl_cin_bwd_f32(const MssRclArgs* a, const uint8_t* kind, const double* 
 int mss_rcl_pairs_f32(const float* score, const int32_t* idx_a, const int64_t* perm_a, const int32_t* idx_o,
                       const int64_t* perm_o, long long n, float margin, double* counters, int slot, float grad_w,
                       float* dscore, void* stream);
-/* same, but n = min(max_samples, n_out[0..2]) and the two permutations are keyed Feistel
- * bijections evaluated on the fly: no host round trip, no materialised randperm. */
-int mss_rcl_pairs_device_f32(const float* score, const int32_t* idx_a, const int32_t* idx_o, const uint32_t* n_out,
-                             int set_a, long long max_samples, uint32_t seed_a, uint32_t seed_o, float margin,
-                             double* counters, int slot, float grad_w, float* dscore, void* stream);
-/* Both hinge terms of the device-pairing mode in one launch: pair i of set `orig` (slot 0, margin_orig) and of set `aug` (slot 1,
- * margin_aug) against OOD element feistel(i, n_ood, seed_ood); same sums, same gradients as two mss_rcl_pairs_device_f32 calls
- * with (set 0, seed_orig) and (set 1, seed_aug). */
+/* Both hinge terms of the device-pairing mode in one launch: n = min(max_samples, n_out[0..2]) and the permutations are keyed
+ * Feistel bijections evaluated on the fly (no host round trip, no materialised randperm). Pair i of set `orig` (slot 0, margin_orig,
+ * element feistel(i, n_orig, seed_orig)) and of set `aug` (slot 1, margin_aug, seed_aug) meet OOD element feistel(i, n_ood, seed_ood);
+ * no atomics on dscore: thread i is the only writer of the three elements pair i touches. */
 int mss_rcl_pairs_device2_f32(const float* score, const int32_t* idx_orig, const int32_t* idx_aug, const int32_t* idx_ood,
                               const uint32_t* n_out, long long max_samples, uint32_t seed_orig, uint32_t seed_aug, uint32_t seed_ood,
                               float margin_orig, float margin_aug, double* counters, float grad_w, float* dscore, void* stream);

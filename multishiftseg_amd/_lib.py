@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 11         # include/mss_hip.h
+MSS_ABI_VERSION = 12         # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -126,14 +126,12 @@ SIGNATURES = {
     "mss_ood_score_bwd_f32": [P, I, P, P, I, I, I, I, I, I, P, I, P, I, P],
     "mss_m2f_score_f32": [P, P, I, I, I, I, I, I, I, P, P],
     "mss_rcl_pass1_f32": [POINTER(MssRclArgs), P, P, P, P, P, P],
-    "mss_rcl_select_f32": [P, L, P, F, P, P, P],
-    "mss_rcl_select_merged_f32": [P, L, P, F, P, I, P, P],
+    "mss_rcl_select_f32": [P, L, P, F, P, I, P, P],
     "mss_rcl_pass2_f32": [POINTER(MssRclArgs), P, P, P, P, P, F, P, P],
     "mss_rcl_num_compact_blocks": [I, I, I],
     "mss_rcl_compact_f32": [P, I, I, I, P, P, P, P, P, P],
     "mss_rcl_cin_bwd_f32": [POINTER(MssRclArgs), P, P, F, P, P],
     "mss_rcl_pairs_f32": [P, P, P, P, P, L, F, P, I, F, P, P],
-    "mss_rcl_pairs_device_f32": [P, P, P, P, I, L, U, U, F, P, I, F, P, P],
     "mss_rcl_pairs_device2_f32": [P, P, P, P, P, L, U, U, U, F, F, P, F, P, P],
     "mss_rcl_workspace_bytes": [I, I, I],
     "mss_rcl_loss_device_f32": [POINTER(MssRclArgs), P, L, L, U, P, P, P, P],

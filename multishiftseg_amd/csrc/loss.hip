@@ -6,7 +6,9 @@
 //           half's CE values for the selection, AND the gradient of every pixel whose weight is already known:
 //           the original half always, the augmented half when no selection is asked (loss.py:46-69,90-96)
 //   select  exact k-th smallest CE by 4 x 8-bit radix histograms on the fp32 bit pattern
-//           (replaces torch.topk over ~4 M values, loss.py:98-102)
+//           (replaces torch.topk over ~4 M values, loss.py:98-102). One histogram (rcl_hist_digit) and one pick
+//           (rcl_pick_digit) serve both forms: one process runs 5 launches (each pick rides in front of the next byte's
+//           histogram), data-parallel callers step through init + 4 x (hist, pick) with an all-reduce in between
 //   pass2   augmented half only (selection mode): softmax-minus-onehot gradient of the selected pixels (the logits of
 //           the ~20 % rejected pixels are not re-read), zeros elsewhere, target mutation (loss.py:103-111)
 //   compact ordered stream compaction of the three score sets              (loss.py:122-124)
@@ -227,116 +229,42 @@ __global__ void rcl_select_init_kernel(const double* __restrict__ counters, floa
   for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
 }
 
-__global__ __launch_bounds__(256) void rcl_hist_kernel(const float* __restrict__ v, long long n, const uint32_t* sel,
-                                                       int shift, uint32_t* __restrict__ hist) {
-  __shared__ uint32_t lh[256];
-  lh[threadIdx.x] = 0;
-  __syncthreads();
-  const uint32_t prefix = sel[0];
-  const uint32_t mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-  if (sel[2] != 0) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x) {
-      const uint32_t key = f2key(v[i]);
-      if ((key & mask) == (prefix & mask)) atomicAdd(&lh[(key >> shift) & 255], 1u);
-    }
-  }
-  __syncthreads();
-  if (lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[threadIdx.x]);
-}
-
-// Histogram of one radix digit for the local (single-process) selection. WAVE_AGG: the first pass looks at the sign +
-// exponent byte, which takes ~6 distinct values for CE values -- every lane of a wave hits the same few LDS words, so a
-// wave adds ONE count per distinct digit instead of 64 serialised atomics (41 us -> a few us on 2.1 M values).
+// Histogram of radix digit `shift` over the values whose bytes above it equal `prefix`, into the workgroup's LDS bins `lh`.
+// block_dim: blockDim.x, read in the kernel (there the compiler folds it into the launch's workgroup size; read in here it costs
+// a load and a select per workgroup).
+// WAVE_AGG: the first pass looks at the sign + exponent byte, which takes ~6 distinct values for CE values -- every lane of a wave
+// hits the same few LDS words, so a wave adds ONE count per distinct digit instead of 64 serialised atomics (41 us -> a few us on
+// 2.1 M values).
 // (A single-launch variant whose last workgroup also picked the digit was measured at 65 us per pass: the release
 // fence + returning ticket atomic of 1024 workgroups cost more than the second launch.)
 template <bool WAVE_AGG>
-__global__ __launch_bounds__(256) void rcl_hist2_kernel(const float* __restrict__ v, long long n, const uint32_t* sel,
-                                                        int shift, uint32_t* __restrict__ hist) {
-  __shared__ uint32_t lh[256];
-  lh[threadIdx.x] = 0;
-  __syncthreads();
-  const uint32_t prefix = sel[0];
+__device__ __forceinline__ void rcl_hist_digit(const float* __restrict__ v, long long n, unsigned block_dim, uint32_t prefix, int shift,
+                                               uint32_t* lh) {
   const uint32_t mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-  if (sel[2] != 0) {
-    const long long step = (long long)gridDim.x * blockDim.x;
-    const long long n_round = (n + step - 1) / step * step;     // whole waves stay converged through the ballot loop
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += step) {
-      uint32_t key = 0;
-      bool take = false;
-      if (i < n) { key = f2key(v[i]); take = (key & mask) == (prefix & mask); }
-      const uint32_t digit = (key >> shift) & 255u;
-      if (WAVE_AGG) {
-        unsigned long long todo = __ballot(take);
-        while (todo) {
-          const int leader = __ffsll((long long)todo) - 1;
-          const uint32_t d0 = (uint32_t)__shfl((int)digit, leader);
-          const unsigned long long same = __ballot(take && digit == d0) & todo;
-          if ((int)(threadIdx.x & 63) == leader) atomicAdd(&lh[d0], (uint32_t)__popcll(same));
-          todo &= ~same;
-        }
-      } else if (take) {
-        atomicAdd(&lh[digit], 1u);
+  const long long step = (long long)gridDim.x * block_dim;
+  const long long n_round = (n + step - 1) / step * step;     // whole waves stay converged through the ballot loop
+  for (long long i = (long long)blockIdx.x * block_dim + threadIdx.x; i < n_round; i += step) {
+    uint32_t key = 0;
+    bool take = false;
+    if (i < n) { key = f2key(v[i]); take = (key & mask) == (prefix & mask); }
+    const uint32_t digit = (key >> shift) & 255u;
+    if (WAVE_AGG) {
+      unsigned long long todo = __ballot(take);
+      while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t d0 = (uint32_t)__shfl((int)digit, leader);
+        const unsigned long long same = __ballot(take && digit == d0) & todo;
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&lh[d0], (uint32_t)__popcll(same));
+        todo &= ~same;
       }
+    } else if (take) {
+      atomicAdd(&lh[digit], 1u);
     }
   }
-  __syncthreads();
-  if (lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[threadIdx.x]);
 }
 
-// digit d with excl(d) < krem <= incl(d), by a 256-lane prefix sum (the serial scan of rcl_pick_kernel took 8 us)
-__global__ __launch_bounds__(256) void rcl_pick_par_kernel(uint32_t* sel, uint32_t* hist, int shift) {
-  __shared__ uint32_t scan[256];
-  const uint32_t cnt = hist[threadIdx.x];
-  scan[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const uint32_t t = threadIdx.x >= (unsigned)o ? scan[threadIdx.x - o] : 0u;
-    __syncthreads();
-    scan[threadIdx.x] += t;
-    __syncthreads();
-  }
-  if (sel[2] != 0) {
-    const uint32_t krem = sel[5], incl = scan[threadIdx.x], excl = incl - cnt;
-    const bool mine = excl < krem && krem <= incl;
-    const bool fallback = threadIdx.x == 255 && krem > incl;     // cannot happen for a consistent k; mirrors the serial pick
-    if (mine || fallback) {
-      sel[0] |= (uint32_t)threadIdx.x << shift;
-      sel[1] += excl;
-      sel[5] = krem - excl;
-      if (shift == 0) sel[3] = krem - excl;     // how many elements equal to the threshold are taken
-    }
-  }
-  hist[threadIdx.x] = 0;
-}
-
-__global__ void rcl_pick_kernel(uint32_t* sel, uint32_t* hist, int shift) {
-  if (threadIdx.x == 0 && sel[2] != 0) {
-    uint32_t krem = sel[5];  // 1-based rank of the wanted element inside the current bucket
-    uint32_t less = sel[1];
-    uint32_t d = 0;
-    for (; d < 256; ++d) {
-      const uint32_t c = hist[d];
-      if (krem <= c) break;
-      krem -= c;
-      less += c;
-    }
-    if (d > 255) d = 255;
-    sel[0] |= d << shift;
-    sel[1] = less;
-    sel[5] = krem;
-    if (shift == 0) sel[3] = krem;  // how many elements equal to the threshold are taken
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
-}
-
-// ---- the selection in 5 launches instead of 9 (round 5): the pick of digit d+1 rides in front of the histogram of digit d ----
-// Every workgroup of the histogram pass of byte `shift` first repeats the pick of the byte above it from the finished
-// histogram of that byte (a 256-lane scan: ~1 us, against a launch of its own), so the chain is hist(24) hist(16) hist(8)
-// hist(0) pick(0). The selection state travels through two alternating 8-word buffers (workgroup 0 writes the state AFTER
-// its pick for the next launch; the others may still be reading the state before it), each pass has its own histogram.
-// FIRST: no pick, the state is the initial one (k from the pass-1 counters, as rcl_select_init_kernel).
+// Pick of one digit from its finished 256-bin histogram: digit d with excl(d) < krem <= incl(d), by a 256-lane prefix sum. Returns
+// the selection state after the pick to every thread of the workgroup (256 threads; scan[256] and st[4] are LDS scratch).
 struct RclSelState { uint32_t prefix, less, k, krem; };
 __device__ __forceinline__ RclSelState rcl_pick_digit(const uint32_t* __restrict__ sel_in, const uint32_t* __restrict__ hist_prev,
                                                       int shift_prev, uint32_t* scan, uint32_t* st) {
@@ -355,7 +283,7 @@ __device__ __forceinline__ RclSelState rcl_pick_digit(const uint32_t* __restrict
   if (k != 0) {
     const uint32_t incl = scan[threadIdx.x], excl = incl - cnt;
     const bool mine = excl < krem && krem <= incl;
-    const bool fallback = threadIdx.x == 255 && krem > incl;     // cannot happen for a consistent k; mirrors rcl_pick_par_kernel
+    const bool fallback = threadIdx.x == 255 && krem > incl;     // cannot happen for a consistent k
     if (mine || fallback) { st[0] = prefix | ((uint32_t)threadIdx.x << shift_prev); st[1] = less + excl; st[3] = krem - excl; }
   }
   __syncthreads();
@@ -363,6 +291,12 @@ __device__ __forceinline__ RclSelState rcl_pick_digit(const uint32_t* __restrict
   return r;
 }
 
+// ---- the single-process selection in 5 launches: the pick of digit d+1 rides in front of the histogram of digit d ----
+// Every workgroup of the histogram pass of byte `shift` first repeats the pick of the byte above it from the finished
+// histogram of that byte (a 256-lane scan: ~1 us, against a launch of its own), so the chain is hist(24) hist(16) hist(8)
+// hist(0) pick(0). The selection state travels through two alternating 8-word buffers (workgroup 0 writes the state AFTER
+// its pick for the next launch; the others may still be reading the state before it), each pass has its own histogram.
+// FIRST: no pick, the state is the initial one (k from the pass-1 counters, as rcl_select_init_kernel).
 template <bool WAVE_AGG, bool FIRST>
 __global__ __launch_bounds__(256) void rcl_hist_pick_kernel(const float* __restrict__ v, long long n, const double* __restrict__ counters,
                                                             float ratio, const uint32_t* __restrict__ sel_in, uint32_t* __restrict__ sel_out,
@@ -381,30 +315,8 @@ __global__ __launch_bounds__(256) void rcl_hist_pick_kernel(const float* __restr
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     sel_out[0] = s.prefix; sel_out[1] = s.less; sel_out[2] = s.k; sel_out[3] = 0; sel_out[4] = 0; sel_out[5] = s.krem; sel_out[6] = 0;
   }
-  const uint32_t prefix = s.prefix;
-  const uint32_t mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-  if (s.k != 0) {
-    const long long step = (long long)gridDim.x * blockDim.x;
-    const long long n_round = (n + step - 1) / step * step;     // whole waves stay converged through the ballot loop
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += step) {
-      uint32_t key = 0;
-      bool take = false;
-      if (i < n) { key = f2key(v[i]); take = (key & mask) == (prefix & mask); }
-      const uint32_t digit = (key >> shift) & 255u;
-      if (WAVE_AGG) {
-        unsigned long long todo = __ballot(take);
-        while (todo) {
-          const int leader = __ffsll((long long)todo) - 1;
-          const uint32_t d0 = (uint32_t)__shfl((int)digit, leader);
-          const unsigned long long same = __ballot(take && digit == d0) & todo;
-          if ((int)(threadIdx.x & 63) == leader) atomicAdd(&lh[d0], (uint32_t)__popcll(same));
-          todo &= ~same;
-        }
-      } else if (take) {
-        atomicAdd(&lh[digit], 1u);
-      }
-    }
-  }
+  if (s.k != 0)
+    rcl_hist_digit<WAVE_AGG>(v, n, blockDim.x, s.prefix, shift, lh);
   __syncthreads();
   if (lh[threadIdx.x]) atomicAdd(&hist_cur[threadIdx.x], lh[threadIdx.x]);
 }
@@ -417,6 +329,32 @@ __global__ __launch_bounds__(256) void rcl_pick_final_kernel(const uint32_t* __r
   if (threadIdx.x == 0) {
     sel[0] = s.prefix; sel[1] = s.less; sel[2] = s.k; sel[3] = s.k != 0 ? s.krem : 0u; sel[4] = 0; sel[5] = s.krem; sel[6] = 0;
   }
+}
+
+// ---- the same selection one radix pass at a time (data-parallel callers all-reduce `hist` between the two) ----
+// Same histogram, same pick; the state lives in `sel` itself (rcl_select_init_kernel writes the initial one).
+template <bool WAVE_AGG>
+__global__ __launch_bounds__(256) void rcl_hist_step_kernel(const float* __restrict__ v, long long n, const uint32_t* __restrict__ sel,
+                                                            int shift, uint32_t* __restrict__ hist) {
+  __shared__ uint32_t lh[256];
+  lh[threadIdx.x] = 0;
+  __syncthreads();
+  if (sel[2] != 0)
+    rcl_hist_digit<WAVE_AGG>(v, n, blockDim.x, sel[0], shift, lh);
+  __syncthreads();
+  if (lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[threadIdx.x]);
+}
+
+// sel[0,1,5] updated in place (sel[3] = how many elements equal to the threshold are taken, after byte 0); `hist` is zeroed for
+// the next pass: the caller all-reduces it between the passes and relies on starting every one from zero.
+__global__ __launch_bounds__(256) void rcl_pick_step_kernel(uint32_t* sel, uint32_t* hist, int shift) {
+  __shared__ uint32_t scan[256], st[4];
+  const RclSelState s = rcl_pick_digit(sel, hist, shift, scan, st);
+  if (threadIdx.x == 0 && s.k != 0) {
+    sel[0] = s.prefix; sel[1] = s.less; sel[5] = s.krem;
+    if (shift == 0) sel[3] = s.krem;
+  }
+  hist[threadIdx.x] = 0;
 }
 
 // ---- pass 2 ---------------------------------------------------------------------------------
@@ -675,33 +613,20 @@ __device__ __forceinline__ uint32_t feistel_perm(uint32_t i, uint32_t n, uint32_
   return x;
 }
 
-template <bool FEISTEL>
+// hinge over n pairs given by explicit permutations (reference pairing / injected permutations), one launch per term; dscore is
+// accumulated with float atomics
 __global__ __launch_bounds__(256) void rcl_pairs_kernel(const float* __restrict__ score,
                                                         const int32_t* __restrict__ idx_a,
                                                         const int64_t* __restrict__ perm_a,
                                                         const int32_t* __restrict__ idx_o,
-                                                        const int64_t* __restrict__ perm_o, long long n_host,
-                                                        const uint32_t* __restrict__ n_out, int set_a,
-                                                        long long max_samples, uint32_t seed_a, uint32_t seed_o,
+                                                        const int64_t* __restrict__ perm_o, long long n,
                                                         float margin, double* __restrict__ counters, int slot,
                                                         float grad_w, float* __restrict__ dscore) {
-  long long n = n_host;
-  uint32_t na = 0, no = 0;
-  if (FEISTEL) {
-    na = n_out[set_a]; no = n_out[2];
-    n = max_samples;
-    if (n > (long long)n_out[0]) n = n_out[0];
-    if (n > (long long)n_out[1]) n = n_out[1];
-    if (n > (long long)n_out[2]) n = n_out[2];
-  }
   const float coef = n > 0 ? grad_w / (float)n : 0.f;
   float acc[1] = {0.f};
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x) {
-    long long ja, jo;
-    if (FEISTEL) { ja = feistel_perm((uint32_t)i, na, seed_a); jo = feistel_perm((uint32_t)i, no, seed_o); }
-    else { ja = perm_a[i]; jo = perm_o[i]; }
-    const int32_t pa = idx_a[ja], po = idx_o[jo];
+    const int32_t pa = idx_a[perm_a[i]], po = idx_o[perm_o[i]];
     const float v = score[pa] + margin - score[po];
     if (v > 0.f) {
       acc[0] += v;
@@ -715,8 +640,8 @@ __global__ __launch_bounds__(256) void rcl_pairs_kernel(const float* __restrict_
   if (blockIdx.x == 0 && threadIdx.x == 0) counters[CNT_N_PAIRS] = (double)n;
 }
 
-// r04: both hinge terms of the device-pairing mode in ONE launch and WITHOUT atomics. The two launches of rcl_pairs_kernel<true>
-// were 2 x 34 us of the 0.42 ms loss at 2 x 19 x 1024 x 2048, bound by ~4e5 scattered float atomics into dscore. Pair i of BOTH
+// r04: both hinge terms of the device-pairing mode in ONE launch and WITHOUT atomics. The two launches (one per term, float
+// atomics) it replaced were 2 x 34 us of the 0.42 ms loss at 2 x 19 x 1024 x 2048, bound by ~4e5 scattered float atomics into dscore. Pair i of BOTH
 // terms meets the same OOD element (the OOD permutation has one seed), the three permutations are bijections, and the three sets
 // are disjoint -- so thread i is the ONLY writer of dscore[orig_i], dscore[aug_i] and dscore[ood_i]: plain read-modify-writes, in
 // the order the two launches applied them (orig term, then aug term), hence the same bits, and no order dependence at all.
@@ -904,25 +829,11 @@ static int rcl_pass1_impl(const MssRclArgs* a, float* lse, float* ce_aug, uint8_
   return mss_launch_status();
 }
 
-int mss_rcl_select_f32(const float* ce_aug, long long n, const double* counters, float selection_ratio,
-                       uint32_t* hist_ws, uint32_t* sel, void* stream) {
-  if (!ce_aug || !counters || !hist_ws || !sel || n <= 0) return MSS_ERR_BAD_ARG;
-  hipLaunchKernelGGL(rcl_select_init_kernel, dim3(1), dim3(256), 0, S_(stream), counters, selection_ratio, sel,
-                     hist_ws);
-  const dim3 grid(grid_for(n, 1024));
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    if (shift == 24) hipLaunchKernelGGL(rcl_hist2_kernel<true>, grid, dim3(256), 0, S_(stream), ce_aug, n, sel, shift, hist_ws);
-    else hipLaunchKernelGGL(rcl_hist2_kernel<false>, grid, dim3(256), 0, S_(stream), ce_aug, n, sel, shift, hist_ws);
-    hipLaunchKernelGGL(rcl_pick_par_kernel, dim3(1), dim3(256), 0, S_(stream), sel, hist_ws, shift);
-  }
-  return mss_launch_status();
-}
-
-// The same selection in 5 launches (the picks ride in front of the next byte's histogram, see rcl_hist_pick_kernel). scratch:
+// The selection in 5 launches (the picks ride in front of the next byte's histogram, see rcl_hist_pick_kernel). scratch:
 // MSS_RCL_SELECT_SCRATCH_WORDS 32-bit words (four histograms + two state buffers), cleared here unless the caller says it already
 // is (scratch_zeroed != 0: mss_rcl_loss_device_f32 clears it together with the counters).
-int mss_rcl_select_merged_f32(const float* ce_aug, long long n, const double* counters, float selection_ratio, uint32_t* scratch,
-                              int scratch_zeroed, uint32_t* sel, void* stream) {
+int mss_rcl_select_f32(const float* ce_aug, long long n, const double* counters, float selection_ratio, uint32_t* scratch,
+                       int scratch_zeroed, uint32_t* sel, void* stream) {
   if (!ce_aug || !counters || !scratch || !sel || n <= 0) return MSS_ERR_BAD_ARG;
   if (!scratch_zeroed) {
     hipError_t e = hipMemsetAsync(scratch, 0, MSS_RCL_SELECT_SCRATCH_WORDS * sizeof(uint32_t), S_(stream));
@@ -955,13 +866,14 @@ int mss_rcl_select_init_f32(const double* counters, float selection_ratio, uint3
 int mss_rcl_select_hist_f32(const float* ce_aug, long long n, const uint32_t* sel, int shift, uint32_t* hist_ws,
                             void* stream) {
   if (!ce_aug || !sel || !hist_ws || n <= 0 || shift < 0 || shift > 24 || shift % 8) return MSS_ERR_BAD_ARG;
-  hipLaunchKernelGGL(rcl_hist_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, S_(stream), ce_aug, n, sel, shift,
-                     hist_ws);
+  const dim3 grid(grid_for(n, 2048));
+  if (shift == 24) hipLaunchKernelGGL(rcl_hist_step_kernel<true>, grid, dim3(256), 0, S_(stream), ce_aug, n, sel, shift, hist_ws);
+  else hipLaunchKernelGGL(rcl_hist_step_kernel<false>, grid, dim3(256), 0, S_(stream), ce_aug, n, sel, shift, hist_ws);
   return mss_launch_status();
 }
 int mss_rcl_select_pick_f32(uint32_t* sel, uint32_t* hist_ws, int shift, void* stream) {
   if (!sel || !hist_ws || shift < 0 || shift > 24 || shift % 8) return MSS_ERR_BAD_ARG;
-  hipLaunchKernelGGL(rcl_pick_kernel, dim3(1), dim3(256), 0, S_(stream), sel, hist_ws, shift);
+  hipLaunchKernelGGL(rcl_pick_step_kernel, dim3(1), dim3(256), 0, S_(stream), sel, hist_ws, shift);
   return mss_launch_status();
 }
 
@@ -1029,21 +941,8 @@ int mss_rcl_pairs_f32(const float* score, const int32_t* idx_a, const int64_t* p
   if (!score || !idx_a || !idx_o || !counters || n < 0) return MSS_ERR_BAD_ARG;
   if (n > 0 && (!perm_a || !perm_o)) return MSS_ERR_BAD_ARG;
   if (slot != 0 && slot != 1) return MSS_ERR_BAD_ARG;
-  hipLaunchKernelGGL(rcl_pairs_kernel<false>, dim3(grid_for(n > 0 ? n : 1, 2048)), dim3(256), 0, S_(stream), score,
-                     idx_a, perm_a, idx_o, perm_o, n, nullptr, 0, 0ll, 0u, 0u, margin, counters,
-                     slot == 0 ? CNT_SUM_CORIG : CNT_SUM_CAUG, grad_w, dscore);
-  return mss_launch_status();
-}
-
-int mss_rcl_pairs_device_f32(const float* score, const int32_t* idx_a, const int32_t* idx_o, const uint32_t* n_out,
-                             int set_a, long long max_samples, uint32_t seed_a, uint32_t seed_o, float margin,
-                             double* counters, int slot, float grad_w, float* dscore, void* stream) {
-  if (!score || !idx_a || !idx_o || !n_out || !counters) return MSS_ERR_BAD_ARG;
-  if ((slot != 0 && slot != 1) || (set_a != 0 && set_a != 1)) return MSS_ERR_BAD_ARG;
-  // 256 workgroups: the pair count is only known on the device, and each workgroup ends with one same-address atomic
-  hipLaunchKernelGGL(rcl_pairs_kernel<true>, dim3(256), dim3(256), 0, S_(stream), score, idx_a, nullptr, idx_o,
-                     nullptr, 0ll, n_out, set_a, max_samples, seed_a, seed_o, margin, counters,
-                     slot == 0 ? CNT_SUM_CORIG : CNT_SUM_CAUG, grad_w, dscore);
+  hipLaunchKernelGGL(rcl_pairs_kernel, dim3(grid_for(n > 0 ? n : 1, 2048)), dim3(256), 0, S_(stream), score, idx_a, perm_a,
+                     idx_o, perm_o, n, margin, counters, slot == 0 ? CNT_SUM_CORIG : CNT_SUM_CAUG, grad_w, dscore);
   return mss_launch_status();
 }
 
@@ -1077,7 +976,7 @@ static RclWs rcl_ws_layout(int B, int H, int W) {
   w.counters = up(w.kind + total);
   w.sel = up(w.counters + 16 * 8);
   w.hist = up(w.sel + 8 * 4);
-  w.idx = up(w.hist + MSS_RCL_SELECT_SCRATCH_WORDS * 4);     // the merged selection's scratch (four histograms + two state buffers)
+  w.idx = up(w.hist + MSS_RCL_SELECT_SCRATCH_WORDS * 4);     // the selection's scratch (four histograms + two state buffers)
   w.block_counts = up(w.idx + 3 * total * 4);
   w.n_out = up(w.block_counts + 3 * nb * 4);
   w.total = up(w.n_out + 4 * 4);
@@ -1117,7 +1016,7 @@ int mss_rcl_loss_device_f32(const MssRclArgs* a, void* workspace, long long work
   if ((rc = rcl_pass1_impl(a, lse, ce_aug, kind, counters, dlogit, stream, false))) return rc;
   const bool select = a->select != 0;
   if (select) {
-    rc = mss_rcl_select_merged_f32(ce_aug, (long long)(a->B / 2) * a->H * a->W, counters, a->selection_ratio, hist, 1, sel, stream);
+    rc = mss_rcl_select_f32(ce_aug, (long long)(a->B / 2) * a->H * a->W, counters, a->selection_ratio, hist, 1, sel, stream);
     if (rc) return rc;
     if ((rc = mss_rcl_pass2_f32(a, lse, ce_aug, kind, sel, counters, 1.0f, dlogit, stream))) return rc;
   } else {

@@ -24,6 +24,7 @@ Data parallelism (``sync``): the reference computes the loss once over the batch
     that DDP's gradient averaging yields exactly d(global loss)/d(theta).
 """
 import ctypes
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -68,11 +69,15 @@ class RelContrastiveLoss(nn.Module):
         self._step = int(seed)
         self.last_terms = None   # device tensor [8]: loss, ce_orig, ce_aug, c_orig, c_aug, c_in, bad-target count, 0
 
-    def forward(self, logits, anomaly_score, targets, perms=None):
+    @staticmethod
+    def _check_inputs(logits, targets):
         if not logits.is_cuda:
             raise RuntimeError("RelContrastiveLoss (multishiftseg_amd) runs on an MI355X only; there is no CPU path")
         if targets.dtype != torch.int64 or not targets.is_contiguous():
             raise RuntimeError("targets must be a contiguous int64 tensor (it is mutated in place, loss.py:110-111)")
+
+    def forward(self, logits, anomaly_score, targets, perms=None):
+        self._check_inputs(logits, targets)
         return _RclFn.apply(logits, anomaly_score, targets, self, perms)
 
     def value_and_grads(self, logits, anomaly_score, targets, perms=None):
@@ -81,18 +86,23 @@ class RelContrastiveLoss(nn.Module):
         anyway, and going through the autograd node costs `grad * upstream` -- a full extra read + write of the 318 MB logit
         gradient at 2x19x1024x2048 (0.13 ms per step) for an upstream gradient that is exactly 1 (train_deeplab.py:198-202:
         `loss.mean()` of a 0-dim tensor, `loss.backward()`). Same mutation of `targets`, same NaN behaviour as forward()."""
-        if not logits.is_cuda:
-            raise RuntimeError("RelContrastiveLoss (multishiftseg_amd) runs on an MI355X only; there is no CPU path")
-        if targets.dtype != torch.int64 or not targets.is_contiguous():
-            raise RuntimeError("targets must be a contiguous int64 tensor (it is mutated in place, loss.py:110-111)")
+        self._check_inputs(logits, targets)
         out, dlogit, dscore = self._run(logits.detach(), anomaly_score.detach(), targets, True, True, perms)
         return out[0], dlogit, dscore
 
     def _run(self, logits, score, targets, need_dl, need_ds, perms):
         import torch.distributed as dist
-        if self.sync == "global" and dist.is_initialized() and dist.get_world_size(self.group) > 1:
-            if perms is not None:
-                raise ValueError("explicit permutations are a single-process (parity) feature")
+        world = self.sync == "global" and dist.is_initialized() and dist.get_world_size(self.group) > 1
+        if world and perms is not None:
+            raise ValueError("explicit permutations are a single-process (parity) feature")
+        logits = logits.contiguous().float()
+        score = score.contiguous().float()
+        B = logits.shape[0]
+        if B < 2:
+            raise RuntimeError("RelContrastiveLoss needs an (original, augmented) pair: batch >= 2")
+        if B % 2:
+            raise RuntimeError(f"RelContrastiveLoss needs [orig...; aug...] pairs: batch {B} is odd")
+        if world:
             return self._run_global(logits, score, targets, need_dl, need_ds)
         return self._run_local(logits, score, targets, need_dl, need_ds, perms)
 
@@ -109,40 +119,55 @@ class RelContrastiveLoss(nn.Module):
         a.select, a.selection_ratio = int(select), float(self.selection_ratio)
         return a, select
 
+    def _pass1(self, a, logits, need_dl, kind):
+        """The float buffers of the two step-by-step routes and pass 1. The integer buffers (`kind` here) come from the route: every
+        such allocation site is listed by route in tests/poison.py."""
+        B, C, H, W = logits.shape
+        dev = logits.device
+        total, half = B * H * W, (B // 2) * H * W
+        lse = torch.empty(total, device=dev, dtype=torch.float32)
+        ce_aug = torch.empty(half, device=dev, dtype=torch.float32)
+        counters = torch.empty(16, device=dev, dtype=torch.float64)
+        sel = torch.zeros(8, device=dev, dtype=torch.int32)
+        dlogit = torch.empty_like(logits) if need_dl else None
+        call("mss_rcl_pass1_f32", ctypes.byref(a), ptr(lse), ptr(ce_aug), ptr(kind), ptr(counters), ptr(dlogit))
+        return SimpleNamespace(total=total, half=half, lse=lse, ce_aug=ce_aug, kind=kind, counters=counters, sel=sel, dlogit=dlogit)
+
+    def _sets(self, a, select, w, score, need_ds, cin_w, idx, block_counts, n_out):
+        """After the route's selection into `w.sel`: pass 2, the compaction of the three score sets into `idx` / `n_out`, and the
+        consistency term's `dscore` (returned)."""
+        ra = ctypes.byref(a)
+        if select:
+            call("mss_rcl_pass2_f32", ra, ptr(w.lse), ptr(w.ce_aug), ptr(w.kind), ptr(w.sel), ptr(w.counters), 1.0, ptr(w.dlogit))
+        call("mss_rcl_compact_f32", ptr(w.kind), a.B, a.H, a.W, ptr(idx[0]), ptr(idx[1]), ptr(idx[2]), ptr(block_counts), ptr(n_out))
+        dscore = torch.empty_like(score) if need_ds else None
+        if need_ds:
+            call("mss_rcl_cin_bwd_f32", ra, ptr(w.kind), ptr(w.counters), cin_w, ptr(dscore))
+        return dscore
+
     def _run_global(self, logits, score, targets, need_dl, need_ds):
         """Reference semantics over the union of all ranks' pairs (module docstring, sync="global")."""
         import torch.distributed as dist
         g = self.group
         Wn, rank = dist.get_world_size(g), dist.get_rank(g)
-        logits = logits.contiguous().float()
-        score = score.contiguous().float()
         B, C, H, W = logits.shape
-        if B < 2:
-            raise RuntimeError("RelContrastiveLoss needs an (original, augmented) pair: batch >= 2")
         dev = logits.device
-        total, half = B * H * W, (B // 2) * H * W
-        if B % 2:
-            raise RuntimeError(f"RelContrastiveLoss needs [orig...; aug...] pairs: batch {B} is odd")
+        total = B * H * W
         # Gradients come out multiplied by the world size (see docstring). With the easiest-k selection the kernel divides
         # by the GLOBAL k, so the factor goes into the weight; without it the kernel divides by the LOCAL half, which
         # already is (global half) / world, so no extra factor is needed (and none for the original half either way).
         select_on = bool(self.conduct_pixel_selection and 0.0 < self.selection_ratio < 1.0)
         a, select = self._args(logits, score, targets, w_aug_scale=float(Wn) if select_on else 1.0)
-        ra = ctypes.byref(a)
-        lse = torch.empty(total, device=dev, dtype=torch.float32)
-        ce_aug = torch.empty(half, device=dev, dtype=torch.float32)
         kind = torch.empty(total, device=dev, dtype=torch.uint8)
-        counters = torch.empty(16, device=dev, dtype=torch.float64)
-        sel = torch.zeros(8, device=dev, dtype=torch.int32)
-        hist = torch.empty(256, device=dev, dtype=torch.int32)
-        dlogit = torch.empty_like(logits) if need_dl else None
-        call("mss_rcl_pass1_f32", ra, ptr(lse), ptr(ce_aug), ptr(kind), ptr(counters), ptr(dlogit))
+        w = self._pass1(a, logits, need_dl, kind)
+        counters, sel = w.counters, w.sel
         dist.all_reduce(counters, group=g)                     # slots 0..6 and 12 are sums/counts; the rest still zero
         if select:
+            hist = torch.empty(256, device=dev, dtype=torch.int32)
             call("mss_rcl_select_init_f32", ptr(counters), float(self.selection_ratio), ptr(hist), ptr(sel))
             local_last = None
             for shift in (24, 16, 8, 0):
-                call("mss_rcl_select_hist_f32", ptr(ce_aug), half, ptr(sel), shift, ptr(hist))
+                call("mss_rcl_select_hist_f32", ptr(w.ce_aug), w.half, ptr(sel), shift, ptr(hist))
                 if shift == 0:
                     local_last = hist.clone()
                 dist.all_reduce(hist, group=g)
@@ -153,16 +178,12 @@ class RelContrastiveLoss(nn.Module):
             dist.all_gather(eqs, local_eq, group=g)
             before = torch.stack(eqs[:rank]).sum() if rank else torch.zeros((), device=dev, dtype=torch.int32)
             sel[3] = torch.clamp(sel[3] - before, min=0).minimum(local_eq[0])
-            call("mss_rcl_pass2_f32", ra, ptr(lse), ptr(ce_aug), ptr(kind), ptr(sel), ptr(counters), 1.0, ptr(dlogit))
         nb = _lib.value("mss_rcl_num_compact_blocks", B, H, W)
         idx = torch.empty((3, total), device=dev, dtype=torch.int32)
         block_counts = torch.empty(3 * nb, device=dev, dtype=torch.int32)
         n_out = torch.zeros(4, device=dev, dtype=torch.int32)
-        call("mss_rcl_compact_f32", ptr(kind), B, H, W, ptr(idx[0]), ptr(idx[1]), ptr(idx[2]), ptr(block_counts), ptr(n_out))
         wc = float(self.contras_weight)
-        dscore = torch.empty_like(score) if need_ds else None
-        if need_ds:
-            call("mss_rcl_cin_bwd_f32", ra, ptr(kind), ptr(counters), wc * Wn, ptr(dscore))
+        dscore = self._sets(a, select, w, score, need_ds, wc * Wn, idx, block_counts, n_out)
         # set sizes of every rank (the one host read of this mode; the reference syncs several times here)
         all_n = [torch.empty_like(n_out) for _ in range(Wn)]
         dist.all_gather(all_n, n_out, group=g)
@@ -198,36 +219,21 @@ class RelContrastiveLoss(nn.Module):
         fa, _ = self._args(logits, score, targets, batch_scale=Wn)   # true weights, global pixel count
         call("mss_rcl_finalize_f32", ctypes.byref(fa), ptr(counters), ptr(sel), ptr(out))
         self.last_terms = out
-        return out, dlogit, dscore
+        return out, w.dlogit, dscore
 
     def _run_local(self, logits, score, targets, need_dl, need_ds, perms):
-        logits = logits.contiguous().float()
-        score = score.contiguous().float()
         B, C, H, W = logits.shape
-        if B < 2:
-            raise RuntimeError("RelContrastiveLoss needs an (original, augmented) pair: batch >= 2")
-        if B % 2:
-            raise RuntimeError(f"RelContrastiveLoss needs [orig...; aug...] pairs: batch {B} is odd")
         dev = logits.device
-        h = B // 2
-        total, half = B * H * W, h * H * W
-        a = MssRclArgs()
-        a.logit, a.score, a.target = ptr(logits), ptr(score), ptr(targets)
-        a.B, a.C, a.H, a.W = B, C, H, W
-        a.w_ce_orig, a.w_ce_aug, a.w_contras = float(self.ce_weights[0]), float(self.ce_weights[1]), float(self.contras_weight)
-        m = self.inoutaug_contras_margins_tri
-        a.m0, a.m1, a.m2 = float(m[0]), float(m[1]), float(m[2])
-        select = bool(self.conduct_pixel_selection and 0.0 < self.selection_ratio < 1.0)
-        a.select, a.selection_ratio = int(select), float(self.selection_ratio)
+        total = B * H * W
+        a, select = self._args(logits, score, targets)
         ra = ctypes.byref(a)
-
-        dlogit = torch.empty_like(logits) if need_dl else None
         if perms is None and self.pairing == "device":
             # no host round trip anywhere in this mode: ONE call issues the whole launch sequence (pass 1, radix select, pass 2,
             # compaction, the three hinge terms, finalize) out of one workspace -- issued one by one through this binding the
             # ~17 launches were bound by the host (csrc/loss.hip, mss_rcl_loss_device_f32)
             nbytes = _lib.value("mss_rcl_workspace_bytes", B, H, W)
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            dlogit = torch.empty_like(logits) if need_dl else None
             dscore = torch.empty_like(score) if need_ds else None
             out = torch.empty(8, device=dev, dtype=torch.float32)
             self._step += 1
@@ -235,26 +241,19 @@ class RelContrastiveLoss(nn.Module):
                  ptr(dscore), ptr(out))
             self.last_terms = out
             return out, dlogit, dscore
-        lse = torch.empty(total, device=dev, dtype=torch.float32)
-        ce_aug = torch.empty(half, device=dev, dtype=torch.float32)
         kind = torch.empty(total, device=dev, dtype=torch.uint8)
-        counters = torch.empty(16, device=dev, dtype=torch.float64)
-        sel = torch.zeros(8, device=dev, dtype=torch.int32)
-        hist = torch.empty(256, device=dev, dtype=torch.int32)
-        call("mss_rcl_pass1_f32", ra, ptr(lse), ptr(ce_aug), ptr(kind), ptr(counters), ptr(dlogit))
+        w = self._pass1(a, logits, need_dl, kind)
+        counters = w.counters
         if select:
-            call("mss_rcl_select_f32", ptr(ce_aug), half, ptr(counters), float(self.selection_ratio), ptr(hist), ptr(sel))
-            call("mss_rcl_pass2_f32", ra, ptr(lse), ptr(ce_aug), ptr(kind), ptr(sel), ptr(counters), 1.0, ptr(dlogit))
+            hist = torch.empty(4 * 256 + 16, device=dev, dtype=torch.int32)      # MSS_RCL_SELECT_SCRATCH_WORDS: four histograms + state
+            call("mss_rcl_select_f32", ptr(w.ce_aug), w.half, ptr(counters), float(self.selection_ratio), ptr(hist), 0, ptr(w.sel))
         # contrastive part
         nb = _lib.value("mss_rcl_num_compact_blocks", B, H, W)
         idx = torch.empty((3, total), device=dev, dtype=torch.int32)
         block_counts = torch.empty(3 * nb, device=dev, dtype=torch.int32)
         n_out = torch.empty(4, device=dev, dtype=torch.int32)
-        call("mss_rcl_compact_f32", ptr(kind), B, H, W, ptr(idx[0]), ptr(idx[1]), ptr(idx[2]), ptr(block_counts), ptr(n_out))
-        dscore = torch.empty_like(score) if need_ds else None
         wc = float(self.contras_weight)
-        if need_ds:
-            call("mss_rcl_cin_bwd_f32", ra, ptr(kind), ptr(counters), wc, ptr(dscore))
+        dscore = self._sets(a, select, w, score, need_ds, wc, idx, block_counts, n_out)
         max_samples = int(total * self.sample_ratio)
         # reference pairing / injected permutations (the device-pairing mode returned above)
         n_orig, n_aug, n_ood = (int(v) for v in n_out[:3].tolist())      # host sync, as the reference's .sum()/int()
@@ -269,6 +268,6 @@ class RelContrastiveLoss(nn.Module):
             call("mss_rcl_pairs_f32", ptr(score), ptr(idx[set_a]), ptr(pa), ptr(idx[2]), ptr(p_ood), n, float(margin),
                  ptr(counters), slot, wc, ptr(dscore))
         out = torch.empty(8, device=dev, dtype=torch.float32)
-        call("mss_rcl_finalize_f32", ra, ptr(counters), ptr(sel), ptr(out))
+        call("mss_rcl_finalize_f32", ra, ptr(counters), ptr(w.sel), ptr(out))
         self.last_terms = out
-        return out, dlogit, dscore
+        return out, w.dlogit, dscore
