@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 12     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 13     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -36,7 +36,8 @@ extern "C" {
                                   (the masked cross-attention of the Mask2Former GMA transformer decoder);
                                   12: two entry points removed, one signature changed: mss_rcl_select_f32 is the 5-launch selection (scratch, scratch_zeroed) and
                                   its 9-launch form and second name are gone; the two-launch Feistel pairs entry point that mss_rcl_pairs_device2_f32 replaced
-                                  in version 5 is gone */
+                                  in version 5 is gone;
+                                  13 (additive): mss_m2f_match_workspace_bytes, mss_m2f_match_cost_f32, mss_m2f_match_assign_f32 (Hungarian matching) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -608,6 +609,33 @@ int mss_upsample_bilinear_add_nhwc_f32(const float* top, int ldt, long long top_
 /* NHWC (pixel stride ldx, sample stride x_sample_stride floats) -> contiguous NCHW: the decoder returns NCHW maps like
  * the reference. */
 int mss_nhwc_to_nchw_f32(const float* x, int ldx, long long x_sample_stride, int N, int HW, int C, float* y, void* stream);
+
+/* ---- Hungarian matching of Mask2Former (csrc/m2f_match.hip) ----
+ * replaces HungarianMatcher.memory_efficient_forward, lib/network/mask2former/modeling/matcher.py:95-156 (batch_dice_loss :15-30,
+ * batch_sigmoid_ce_loss :38-62), called from criterion.py:444,463 once per prediction step. A problem is one (step s, image b):
+ * all S*B problems of a train step go through one call = two launches, no float atomics, no host synchronisation.
+ *   masks_host / cls_host: HOST arrays of S device pointers (S <= 16), one per prediction step (the last output and the
+ *     aux_outputs are separate tensors): mask logits of B images, element (b, q, y, x) at b*img_stride + q*query_stride +
+ *     (y*w + x)*pixel_stride floats (NCHW [B,Q,h,w]: h*w*Q, h*w, 1; pixel-major [B,h,w,ldq]: h*w*ldq, 1, ldq); class logits
+ *     [B,Q,C1] contiguous, C1 = classes + 1.
+ *   tmask uint8 [total_t,H,W] (0/1), labels int32 [total_t], tstart int32 [B+1]: image b owns targets tstart[b] .. tstart[b+1]-1
+ *     (T_b <= Q <= 128, T_b <= Tmax <= 128); shared by all steps. points [S,B,P,2] = (x, y) in [0,1), shared by the masks of a problem
+ *     (matcher.py:119-132); point_sample = F.grid_sample(2u-1, bilinear, align_corners=False, zeros): pixel coordinate u*n - 0.5.
+ *   cost [S,B,Q,Tmax] fp32 = w_mask cost_mask + w_class cost_class + w_dice cost_dice (matcher.py:144-148), columns >= T_b
+ *     written as 0. ws: mss_m2f_match_workspace_bytes bytes of float scratch = 4 * S*B * NC * (2*Q*TP + 2*Q + TP) with
+ *     TP = Tmax rounded up to 16 and NC = min(16, ceil(P / 64)) point chunks, added in index order in float64 (bit-reproducible).
+ *   match / status (both or neither; NULL = cost only): the assignment is solved in the same second launch. */
+long long mss_m2f_match_workspace_bytes(int S, int B, int Q, int Tmax, int P);
+int mss_m2f_match_cost_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
+                           int h, int w, const float* const* cls_host, const uint8_t* tmask, const int* tstart, const int* labels,
+                           int total_t, int H, int W, const float* points, int S, int B, int Q, int C1, int P, int Tmax,
+                           float w_class, float w_mask, float w_dice, float* ws, float* cost, int* match, int* status, void* stream);
+/* linear_sum_assignment (matcher.py:151) of cost [S,B,Q,Tmax] fp32, tcount int32 [B] targets per image: one wave per problem,
+ * shortest augmenting paths (Crouse 2016, scipy's algorithm) in float64, every loop bounded by T_b or Q. match [S,B,Tmax] int32 =
+ * the query of target m (-1 in the padding); status [S,B] int32: 0 solved, 1 infeasible / NaN / -inf cost / bad count (scipy's
+ * ValueError; match is then all -1). Equal costs: the lowest column wins. */
+int mss_m2f_match_assign_f32(const float* cost, const int* tcount, int S, int B, int Q, int Tmax, int* match, int* status,
+                             void* stream);
 
 /* ---- on-device data path of the DeepLab trainer (csrc/data.hip) ----
  * One kernel for what DiverseCityscapes.__getitem__ + its transforms + the trainer's batch concat do per step

@@ -6,7 +6,10 @@ def __getattr__(name):
     if name == "MultiScaleMaskedTransformerDecoder_GMA":
         from .transformer_decoder import MultiScaleMaskedTransformerDecoder_GMA
         return MultiScaleMaskedTransformerDecoder_GMA
+    if name == "HungarianMatcher":
+        from .matcher import HungarianMatcher
+        return HungarianMatcher
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["MultiScaleMaskedTransformerDecoder_GMA"]
+__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher"]

@@ -1213,6 +1213,85 @@ def m2f_score_fused(class_logits, mask_logits_nhwc, image_size, size=None):
     return out
 
 
+# ---- Hungarian matching of Mask2Former (csrc/m2f_match.hip) ---------------------------------------------------------------------
+def _match_ints(S, B, Tmax, device):
+    """match [S,B,Tmax] and status [S,B] as views of ONE int32 buffer (one device-to-host copy brings both), pre-filled: integer
+    buffers are never handed out uninitialised (tests/poison.py)."""
+    buf = torch.full((S * B * (Tmax + 1),), -1, device=device, dtype=torch.int32)
+    return buf, buf[:S * B * Tmax].view(S, B, Tmax), buf[S * B * Tmax:].view(S, B)
+
+
+def m2f_match_cost(mask_logits, class_logits, tmask, tstart, labels, point_coords, weights=(1.0, 1.0, 1.0), Tmax=None,
+                   pixel_major=False, solve=False):
+    """The matching cost of matcher.py:105-148 for S prediction steps x B images in two launches. mask_logits / class_logits:
+    lists of S tensors (or one tensor = one step): NCHW [B,Q,h,w], or with pixel_major the decoder's [B,h,w,ldq]
+    (m2f_mask_logits_act; ldq >= Q) / [B,Q,C+1]. tmask uint8 [sum T,H,W], labels int32 [sum T], tstart int32 [B+1] (device);
+    point_coords [S,B,P,2] (x, y) in [0,1); weights = (cost_class, cost_mask, cost_dice); Tmax >= max T_b (host int, default
+    sum T). -> cost [S,B,Q,Tmax] fp32 (columns >= T_b are 0); with solve also (match [S,B,Tmax], status [S,B], their shared
+    int32 buffer) from the same second launch."""
+    masks = [mask_logits] if isinstance(mask_logits, torch.Tensor) else list(mask_logits)
+    clss = [class_logits] if isinstance(class_logits, torch.Tensor) else list(class_logits)
+    for t in masks + clss + [point_coords]:
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError("m2f_match_cost runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    if not (tmask.is_cuda and tstart.is_cuda and labels.is_cuda) or tmask.dtype != torch.uint8 or tstart.dtype != torch.int32 \
+            or labels.dtype != torch.int32:
+        raise RuntimeError("m2f_match_cost takes uint8 target masks and int32 tstart / labels on the device")
+    S = len(masks)
+    B, Q, C1 = clss[0].shape
+    masks = [m.contiguous() for m in masks]
+    clss = [c.contiguous() for c in clss]
+    if pixel_major:
+        _, h, w, ldq = masks[0].shape
+        strides = (h * w * ldq, 1, ldq)
+    else:
+        _, ldq, h, w = masks[0].shape
+        strides = (h * w * ldq, h * w, 1)
+    if len(clss) != S or ldq < Q or (not pixel_major and ldq != Q) or any(m.shape != masks[0].shape or m.shape[0] != B for m in masks) \
+            or any(c.shape != clss[0].shape for c in clss):
+        raise ValueError(f"{S} mask logits {tuple(masks[0].shape)} do not match {len(clss)} class logits {tuple(clss[0].shape)}")
+    total_t, H, W = tmask.shape
+    P = point_coords.shape[2]
+    if tuple(point_coords.shape) != (S, B, P, 2) or tstart.numel() != B + 1 or labels.numel() != total_t:
+        raise ValueError(f"point_coords {tuple(point_coords.shape)} / tstart {tuple(tstart.shape)} / labels {tuple(labels.shape)} "
+                         f"do not match S {S}, B {B}, sum T {total_t}")
+    Tmax = max(1, total_t if Tmax is None else int(Tmax))
+    dev = clss[0].device
+    nbytes = _lib.value("mss_m2f_match_workspace_bytes", S, B, Q, Tmax, P)
+    if nbytes <= 0:
+        raise _lib.MssError(f"m2f_match_cost: unsupported shape S {S}, Q {Q}, Tmax {Tmax} (S <= 16, T <= Q <= 128)")
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    cost = torch.empty((S, B, Q, Tmax), device=dev, dtype=torch.float32)
+    buf = match = status = None
+    if solve:
+        buf, match, status = _match_ints(S, B, Tmax, dev)
+    mp = (ctypes.c_void_p * S)(*[m.data_ptr() for m in masks])
+    cp = (ctypes.c_void_p * S)(*[c.data_ptr() for c in clss])
+    pts, tm, lb = point_coords.contiguous(), tmask.contiguous(), labels.contiguous()
+    call("mss_m2f_match_cost_f32", mp, strides[0], strides[1], strides[2], h, w, cp, ptr(tm) if total_t else None, ptr(tstart.contiguous()),
+         ptr(lb) if total_t else None, total_t, H, W, ptr(pts), S, B, Q, C1, P, Tmax, float(weights[0]), float(weights[1]), float(weights[2]),
+         ptr(ws), ptr(cost), ptr(match), ptr(status))
+    return (cost, match, status, buf) if solve else cost
+
+
+def m2f_match_assign(cost, tcount):
+    """linear_sum_assignment (matcher.py:151) of every [Q, T_b] block of cost [S,B,Q,Tmax] fp32 on the device, one wave per
+    problem, float64 shortest augmenting paths; tcount: T_b per image (int32 device tensor [B], or a list). -> (match [S,B,Tmax]
+    int32: the query of target m, -1 in the padding; status [S,B] int32: 0 solved, 1 = scipy's ValueError case)."""
+    if not cost.is_cuda or cost.dtype != torch.float32 or cost.dim() != 4:
+        raise RuntimeError("m2f_match_assign runs on an MI355X only (a float32 CUDA tensor [S,B,Q,Tmax]); there is no CPU path")
+    S, B, Q, Tmax = cost.shape
+    if not isinstance(tcount, torch.Tensor):
+        tcount = torch.tensor([int(t) for t in tcount], device=cost.device, dtype=torch.int32)
+    if not tcount.is_cuda or tcount.dtype != torch.int32 or tcount.numel() != B:
+        raise ValueError(f"tcount must be {B} int32 counts on the device")
+    if Q > 128 or Tmax > 128 or Tmax < 1:
+        raise NotImplementedError(f"m2f_match_assign: Q {Q} / Tmax {Tmax} outside 1..128")
+    _, match, status = _match_ints(S, B, Tmax, cost.device)
+    call("mss_m2f_match_assign_f32", ptr(cost.contiguous()), ptr(tcount.contiguous()), S, B, Q, Tmax, ptr(match), ptr(status))
+    return match, status
+
+
 # ---- Mask2Former pixel-decoder glue (csrc/norm.hip) --------------------------------------------------------------------
 def groupnorm(x, gn, relu=False, out=None, out_sample_stride=None, out_ld=None, want_stat=False):
     """nn.GroupNorm `gn` on an Act (NHWC). `out`: optional float tensor to write into (e.g. the encoder's token buffer

@@ -19,7 +19,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-QUICK = ["ops", "msda", "loss", "m2f", "metric", "datapath", "encoder"]
+QUICK = ["ops", "msda", "loss", "m2f", "matcher", "metric", "datapath", "encoder"]
 ALL = QUICK + ["deeplab", "train", "decoder"]
 
 

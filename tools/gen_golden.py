@@ -1024,8 +1024,133 @@ def gen_metric():
     save("ood_metrics", **out)
 
 
+# ------------------------------------------------------------------------------------------- matcher
+def import_reference_matcher():
+    """lib/network/mask2former/modeling/matcher.py imported by file path. detectron2 is absent: its point_sample is stubbed as
+    detectron2 defines it (projects/point_rend/point_features.py: grid_sample(input, 2 * coords - 1) with the unsqueeze of
+    3-d coordinates)."""
+    import importlib.util
+
+    def point_sample(input, point_coords, **kwargs):
+        add_dim = point_coords.dim() == 3
+        if add_dim:
+            point_coords = point_coords.unsqueeze(2)
+        output = F.grid_sample(input, 2.0 * point_coords - 1.0, **kwargs)
+        return output.squeeze(3) if add_dim else output
+
+    for name in ("detectron2", "detectron2.projects", "detectron2.projects.point_rend", "detectron2.projects.point_rend.point_features"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    sys.modules["detectron2.projects.point_rend.point_features"].point_sample = point_sample
+    spec = importlib.util.spec_from_file_location("ref_m2f_matcher", os.path.join(REF, "lib/network/mask2former/modeling/matcher.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod, point_sample
+
+
+def _matcher_case(rng, S, B, Q, C1, h, w, H, W, T, P):
+    """Blob targets, mask logits that follow some of them at low resolution plus noise, class logits leaning to the labels."""
+    tmasks, labels = [], []
+    yy, xx = np.mgrid[0:H, 0:W]
+    for b in range(B):
+        for _ in range(T[b]):
+            cy, cx = rng.uniform(0.15, 0.85) * H, rng.uniform(0.15, 0.85) * W
+            ry, rx = rng.uniform(0.08, 0.3) * H, rng.uniform(0.08, 0.3) * W
+            tmasks.append((((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1).astype(np.uint8))
+            labels.append(int(rng.integers(0, C1 - 1)))
+    tmasks, labels = np.stack(tmasks), np.array(labels, np.int32)
+    tstart = np.concatenate([[0], np.cumsum(T)]).astype(np.int32)
+    pred_masks = (rng.standard_normal((S, B, Q, h, w)) * 2).astype(np.float32)
+    pred_logits = (rng.standard_normal((S, B, Q, C1)) * 1.5).astype(np.float32)
+    for s in range(S):
+        for b in range(B):
+            qs = rng.permutation(Q)
+            for m in range(T[b]):
+                small = F.interpolate(torch.from_numpy(tmasks[tstart[b] + m][None, None].astype(np.float32)), size=(h, w), mode="bilinear",
+                                      align_corners=False)[0, 0].numpy()
+                for q in qs[2 * m:2 * m + 2]:                                # two candidate queries per target
+                    pred_masks[s, b, q] += ((small * 2 - 1) * rng.uniform(1.5, 4)).astype(np.float32)
+                    pred_logits[s, b, q, labels[tstart[b] + m]] += np.float32(rng.uniform(0.5, 3))
+    points = rng.random((S, B, P, 2), dtype=np.float32)
+    return pred_logits, pred_masks, tmasks, labels, tstart, points
+
+
+def gen_matcher():
+    """HungarianMatcher of the reference ITSELF (matcher.py:70-179) with its torch.rand draws replaced by recorded points:
+    inputs, points, its own fp32 cost matrix (captured on the way into linear_sum_assignment), the same cost functions on
+    float64 inputs, and its indices. A case is recorded only if its assignment is the same from the fp32 cost, from the float64
+    cost and from the float64 cost under 16 draws of +-1e-4 uniform noise; otherwise the next seed is tried."""
+    from scipy.optimize import linear_sum_assignment
+    mod, point_sample = import_reference_matcher()
+    weights = dict(cost_class=2.0, cost_mask=5.0, cost_dice=5.0)
+    cases = {"a": dict(S=3, B=2, Q=100, C1=20, h=12, w=10, H=96, W=80, T=[5, 3], P=300),
+             "b": dict(S=1, B=1, Q=100, C1=20, h=16, w=16, H=64, W=64, T=[19], P=12544)}
+    out = {"weights": np.array([weights["cost_class"], weights["cost_mask"], weights["cost_dice"]], np.float64)}
+    for tag, cfg in cases.items():
+        S, B, Q, T, P = cfg["S"], cfg["B"], cfg["Q"], cfg["T"], cfg["P"]
+        Tmax = max(T)
+        for seed in range(100):
+            rng = np.random.default_rng(7100 + 100 * ord(tag) + seed)
+            pred_logits, pred_masks, tmasks, labels, tstart, points = _matcher_case(rng, **cfg)
+            matcher = mod.HungarianMatcher(num_points=P, **weights)
+            targets = [{"labels": torch.from_numpy(labels[tstart[b]:tstart[b + 1]].astype(np.int64)),
+                        "masks": torch.from_numpy(tmasks[tstart[b]:tstart[b + 1]]).bool()} for b in range(B)]
+            c32 = np.zeros((S, B, Q, Tmax), np.float32)
+            c64 = np.zeros((S, B, Q, Tmax), np.float64)
+            match = np.full((S, B, Tmax), -1, np.int32)
+            stable = True
+            for s in range(S):
+                draws, seen = iter(range(B)), []
+                real_rand, real_lsa = torch.rand, mod.linear_sum_assignment
+
+                def fake_rand(*size, **kw):
+                    b = next(draws)
+                    assert tuple(size) == (1, P, 2)
+                    return torch.from_numpy(points[s, b])[None].clone()
+
+                def spy_lsa(C):
+                    seen.append(C.clone())
+                    return real_lsa(C)
+                torch.rand, mod.linear_sum_assignment = fake_rand, spy_lsa
+                try:
+                    idx = matcher({"pred_logits": torch.from_numpy(pred_logits[s]), "pred_masks": torch.from_numpy(pred_masks[s])}, targets)
+                finally:
+                    torch.rand, mod.linear_sum_assignment = real_rand, real_lsa
+                for b in range(B):
+                    assert seen[b].dtype == torch.float32 and tuple(seen[b].shape) == (Q, T[b])
+                    c32[s, b, :, :T[b]] = seen[b].numpy()
+                    # the same functions on float64 inputs
+                    pts = torch.from_numpy(points[s, b]).double()[None]
+                    om = torch.from_numpy(pred_masks[s, b]).double()[:, None]
+                    tm = targets[b]["masks"].double()[:, None]
+                    tm = point_sample(tm, pts.repeat(tm.shape[0], 1, 1), align_corners=False).squeeze(1)
+                    om = point_sample(om, pts.repeat(om.shape[0], 1, 1), align_corners=False).squeeze(1)
+                    prob = torch.from_numpy(pred_logits[s, b]).double().softmax(-1)
+                    C = weights["cost_mask"] * mod.batch_sigmoid_ce_loss(om, tm) + weights["cost_class"] * -prob[:, targets[b]["labels"]] \
+                        + weights["cost_dice"] * mod.batch_dice_loss(om, tm)
+                    c64[s, b, :, :T[b]] = C.numpy()
+                    i, j = idx[b]
+                    match[s, b, j.numpy()] = i.numpy()
+                    ref = (i.numpy().tolist(), j.numpy().tolist())
+                    noise = np.random.default_rng(seed * 1000 + s * 10 + b)
+                    trials = [c32[s, b, :, :T[b]].astype(np.float64), c64[s, b, :, :T[b]]] + \
+                             [c64[s, b, :, :T[b]] + noise.uniform(-1e-4, 1e-4, (Q, T[b])) for _ in range(16)]
+                    for Ct in trials:
+                        ti, tj = linear_sum_assignment(Ct)
+                        stable = stable and (ti.tolist(), tj.tolist()) == ref
+            if stable:
+                break
+            print(f"   case {tag}: seed {seed} is not stable under +-1e-4, next")
+        assert stable, tag
+        floor = float(np.abs(c32.astype(np.float64) - c64).max())
+        print(f"   case {tag}: seed {seed}, floor max|ref32 - ref64| {floor:.2e}, costs {c64[c64 != 0].min():.2f} .. {c64.max():.2f}")
+        out.update({f"{tag}_pred_logits": pred_logits, f"{tag}_pred_masks": pred_masks, f"{tag}_tmasks": tmasks, f"{tag}_labels": labels,
+                    f"{tag}_tstart": tstart, f"{tag}_points": points, f"{tag}_cost_ref32": c32, f"{tag}_cost_ref64": c64,
+                    f"{tag}_match": match, f"{tag}_floor": np.array(floor)})
+    save("m2f_matcher", **out)
+
+
 def main():
-    which = set(sys.argv[1:]) or {"ops", "deeplab", "train", "loss", "msda", "m2f", "encoder", "decoder", "metric", "datapath"}
+    which = set(sys.argv[1:]) or {"ops", "deeplab", "train", "loss", "msda", "m2f", "encoder", "decoder", "metric", "datapath", "matcher"}
     torch.set_num_threads(8)
     DeepWV3Plus, ref_loss, core, MSDeformAttn = import_reference()
     if "ops" in which:
@@ -1036,6 +1161,8 @@ def main():
         print("msda"); gen_msda(core, MSDeformAttn)
     if "m2f" in which:
         print("m2f"); gen_m2f()
+    if "matcher" in which:
+        print("matcher"); gen_matcher()
     if "encoder" in which:
         print("encoder"); gen_encoder()
     if "decoder" in which:
