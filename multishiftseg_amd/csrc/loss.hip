@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void rcl_pass1_kernel(MssRclArgs a, float* __r
       acc[1] += in ? 1.f : 0.f;
       // pair (i, i + half): in-distribution consistency term (loss.py:141-145)
       const int64_t t2 = a.target[i + half];
-      if (in && t2 < 99) {
+      if (in && t2 < 99 && t2 >= 0 && t2 < a.C) {  // a flagged label is no more in-distribution here than in its own `kind`
         acc[4] += fmaxf(a.score[i + half] - a.score[i] - a.m2, 0.f);
         acc[5] += 1.f;
       }
@@ -175,7 +175,8 @@ __global__ __launch_bounds__(256) void rcl_pass1_v4_kernel(MssRclArgs a, float* 
       for (int e = 0; e < 4; ++e) {
         acc[0] += ce[e];
         acc[1] += tt[e] >= 0 ? 1.f : 0.f;
-        if (tt[e] >= 0 && u[e] < 99) {          // pair (i, i + half): in-distribution consistency term (loss.py:141-145)
+        // a flagged label (below 0 or in [C, 99)) is no more in-distribution here than in its own `kind`
+        if (tt[e] >= 0 && u[e] < 99 && u[e] >= 0 && u[e] < C) {   // pair (i, i + half): in-distribution consistency term (loss.py:141-145)
           acc[4] += fmaxf(s1[e] - s0[e] - a.m2, 0.f);
           acc[5] += 1.f;
         }
