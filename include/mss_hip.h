@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 13     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 14     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -37,7 +37,8 @@ extern "C" {
                                   12: two entry points removed, one signature changed: mss_rcl_select_f32 is the 5-launch selection (scratch, scratch_zeroed) and
                                   its 9-launch form and second name are gone; the two-launch Feistel pairs entry point that mss_rcl_pairs_device2_f32 replaced
                                   in version 5 is gone;
-                                  13 (additive): mss_m2f_match_workspace_bytes, mss_m2f_match_cost_f32, mss_m2f_match_assign_f32 (Hungarian matching) */
+                                  13 (additive): mss_m2f_match_workspace_bytes, mss_m2f_match_cost_f32, mss_m2f_match_assign_f32 (Hungarian matching);
+                                  14 (additive): the six mss_m2f_loss_* entry points (SetCriterion: class and sampled-mask losses) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -636,6 +637,54 @@ int mss_m2f_match_cost_f32(const float* const* masks_host, long long img_stride,
  * ValueError; match is then all -1). Equal costs: the lowest column wins. */
 int mss_m2f_match_assign_f32(const float* cost, const int* tcount, int S, int B, int Q, int Tmax, int* match, int* status,
                              void* stream);
+
+/* ---- SetCriterion of Mask2Former: class and sampled-mask losses (csrc/m2f_loss.hip) ----
+ * replaces loss_labels (lib/network/mask2former/modeling/criterion.py:189-205), loss_masks (:312-363), loss_masks_aug (:244-310),
+ * get_clean_point_coords_with_randomness (:371-407) and detectron2's get_uncertain_point_coords_with_randomness for all S
+ * prediction steps of a train step (criterion.py:455-467) in a fixed number of launches: no float atomics, no host synchronisation.
+ * A row is one matched (step s, target g): r = s*total_t + g, g = tstart[b] + m; its source map is the mask logits of query
+ * match[s,b,m] of image b in step s (masks_host / strides / tmask / tstart / match [S,B,Tmax] as in mss_m2f_match_cost_f32), its
+ * target map tmask[g]. A row whose table entry is outside [0, Q) has no map: its points are written as 0 and its sums as NaN.
+ *
+ * select (criterion.py:335-341, :371-407): rows with g >= sel_start sample their K candidates cand[s, g - sel_start, :, :]
+ *   (cand [S, total_t - sel_start, K, 2], (x, y) in [0,1)), keep the k with the largest key (mode 1 "uncertain": -|x|; mode 2
+ *   "clean": -BCEWithLogits(x, t)) in ascending candidate index and append the first P - k points of rnd[r] (rnd [S*total_t, Pr, 2]);
+ *   rows with g < sel_start ("random", :365-369) take the first P points of rnd[r]. Ties at the k-th largest key: the lowest
+ *   candidate index wins; -0.0 == +0.0; a NaN key ranks below every number. The exact k-th largest comes from 4 x 8-bit radix
+ *   passes over the row's keys in ws (mss_m2f_loss_workspace_bytes(S*total_t, K, P) bytes). points [S*total_t, P, 2] is written whole.
+ * mask_forward (:343-358): rows [S*total_t, 4] double = sum_p BCEWithLogits(x,t), sum_p sigmoid(x) t, sum_p sigmoid(x), sum_p t
+ *   at the row's P points, one fixed summation order.
+ * finalize (:189-205, :301-306, :356-359): one workgroup per step. tclass [S,B,Q] int32 = labels[g] of the matched target, else
+ *   C1 - 1; loss[s,0] = sum w[c] (logsumexp - x[c]) / sum w[c]; rows with g < split belong to group 0, the others to group 1;
+ *   loss[s, 1 + 2 G] = scale_G sum_rows bce / P, loss[s, 2 + 2 G] = scale_G sum_rows (1 - (2 st + 1) / (sg + tt + 1)), in row order
+ *   in float64; ncols = 3 (one group: split = total_t) or 5. wsum [S] double = sum w[c]. A table entry outside [0, Q) of a real
+ *   target or a label outside [0, C1 - 1) sets bad[s] = 1 and every loss of the step to NaN.
+ * mask_backward: gloss [S,ncols] = the upstream gradient of loss. Per point (sigmoid(x) - t) a / P - ((2 t D - N) / D^2) sigmoid(x)
+ *   (1 - sigmoid(x)) d with a = gloss[s,1+2G] scale_G, d = gloss[s,2+2G] scale_G, N = 2 st + 1, D = sg + tt + 1, scattered through
+ *   the four bilinear taps into an int64 fixed-point window in LDS (quantum 2^(e-60), 2^e >= P (|a|/P + 2|d|)), converted once:
+ *   the map of a matched query is written whole by its row's workgroup, other maps are left as they are (the caller zeroes them).
+ *   grads_host: S device pointers in the layout of masks_host. ws: mss_m2f_loss_workspace_bytes(S*total_t, 0, P) bytes.
+ *   Rows of a bad step write nothing.
+ * label_backward: grads_host[s] [B,Q,C1] = w[c]/wsum (softmax - onehot) gloss[s,0], written whole (0 for a bad step). */
+long long mss_m2f_loss_workspace_bytes(long long R, int K, int P);
+int mss_m2f_loss_select_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride, int h,
+                            int w, const uint8_t* tmask, const int* tstart, const int* match, int total_t, int H, int W,
+                            const float* cand, const float* rnd, int S, int B, int Q, int Tmax, int K, int k, int P, int Pr, int mode,
+                            int sel_start, float* ws, float* points, void* stream);
+int mss_m2f_loss_mask_forward_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
+                                  int h, int w, const uint8_t* tmask, const int* tstart, const int* match, int total_t, int H, int W,
+                                  const float* points, int S, int B, int Q, int Tmax, int P, double* rows, void* stream);
+int mss_m2f_loss_finalize_f32(const float* const* cls_host, const int* labels, const int* tstart, const int* match, const float* weight,
+                              const double* rows, int total_t, int S, int B, int Q, int C1, int Tmax, int P, int split, double scale0,
+                              double scale1, int ncols, int* tclass, int* bad, double* wsum, float* loss, void* stream);
+int mss_m2f_loss_mask_backward_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
+                                   int h, int w, const uint8_t* tmask, const int* tstart, const int* match, const int* bad, int total_t,
+                                   int H, int W, const float* points, const double* rows, const float* gloss, int S, int B, int Q, int Tmax,
+                                   int P, int split, double scale0, double scale1, int ncols, float* ws, float* const* grads_host,
+                                   void* stream);
+int mss_m2f_loss_label_backward_f32(const float* const* cls_host, const int* tclass, const int* bad, const float* weight,
+                                    const double* wsum, const float* gloss, int S, int B, int Q, int C1, int ncols, float* const* grads_host,
+                                    void* stream);
 
 /* ---- on-device data path of the DeepLab trainer (csrc/data.hip) ----
  * One kernel for what DiverseCityscapes.__getitem__ + its transforms + the trainer's batch concat do per step

@@ -9,7 +9,10 @@ def __getattr__(name):
     if name == "HungarianMatcher":
         from .matcher import HungarianMatcher
         return HungarianMatcher
+    if name == "SetCriterion":
+        from .criterion import SetCriterion
+        return SetCriterion
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher"]
+__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion"]

@@ -1,0 +1,189 @@
+"""SetCriterion of Mask2Former (lib/network/mask2former/modeling/criterion.py:91-488) on the HIP kernels of csrc/m2f_loss.hip.
+
+The reference walks the prediction steps one by one and, per step, composes torch.rand, three grid_samples, a topk, a gather and two
+jit-scripted loss functions over the matched masks; its backward scatters through grid_sample with float atomics. Here the class
+loss and the sampled mask losses of ALL S steps (the last output and its aux_outputs), all images and all matched masks are five
+launches (three forward, two backward) after the matcher's two, with no device-to-host copy, and two runs give the same bits.
+There is no CPU path. `loss_ood` is not here: it needs the class-mix backward, which this package does not have yet.
+
+Deviations from the reference, all deliberate:
+  * the random numbers have the reference's distribution, not its draw order (one torch.rand per kind for all rows of all steps);
+  * ties at the k-th largest key go to the lowest candidate index (torch.topk leaves them unspecified);
+  * loss_masks_aug: a half of the batch without masks gives 0 for its two terms (the reference divides by zero: NaN);
+  * mask_loss_with_pixel_selection is a constructor argument (the reference reads a global config, criterion.py:424-426);
+  * weight_dict is stored and shown, not applied (the reference applies it in maskformer_model.py);
+  * a problem the matcher could not solve, or a label outside [0, num_classes), makes every loss of its step NaN and the step's
+    gradients 0, with no host synchronisation (the reference raises inside scipy / indexes out of range).
+"""
+import torch
+from torch import nn
+
+from . import kernels as K
+from .matcher import _steps_of
+
+CLEAN_OVERSAMPLE_RATIO = 1 / 0.8            # criterion.py:374-376: hard-coded in get_clean_point_coords_with_randomness
+CLEAN_IMPORTANCE_SAMPLE_RATIO = 0.95
+
+PLAIN_KEYS = ("loss_ce", "loss_mask", "loss_dice")
+AUG_KEYS = ("loss_ce", "loss_original_mask", "loss_original_dice", "loss_aug_mask", "loss_aug_dice")
+
+
+def selection_counts(num_points, oversample_ratio, importance_sample_ratio):
+    """(K candidates, k kept) of one row, the integers exactly as the reference writes them (criterion.py:382,387)."""
+    return int(num_points * oversample_ratio), int(importance_sample_ratio * num_points)
+
+
+class _Plan:
+    """Everything of one call that is not differentiated: the packed targets, the match table, the points and the row groups."""
+    __slots__ = ("tmask", "tstart", "labels", "match", "points", "weight", "scales", "split", "num_points", "pixel_major", "Q", "S",
+                 "want_masks")
+
+
+class _CriterionFunction(torch.autograd.Function):
+    """One function spans all steps: inputs = every step's mask logits, then every step's class logits; output = the loss table
+    [S, 3] (or [S, 5]); the dict entries of SetCriterion.forward are views of it."""
+
+    @staticmethod
+    def forward(ctx, plan, *tensors):
+        S = plan.S
+        masks, logits = list(tensors[:S]), list(tensors[S:])
+        rows = None
+        if plan.want_masks:
+            rows = K.m2f_mask_loss(masks, plan.tmask, plan.tstart, plan.match, plan.points, pixel_major=plan.pixel_major, Q=plan.Q)
+        loss, tclass, bad, wsum = K.m2f_label_loss(logits, plan.labels, plan.tstart, plan.match, plan.weight, rows, plan.num_points,
+                                                   plan.scales, plan.split)
+        ctx.plan = plan                 # the packed targets, the match table and the points: held until the graph is freed
+        ctx.save_for_backward(*tensors, tclass, bad, wsum, *([rows] if rows is not None else []))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss):
+        plan = ctx.plan
+        S = plan.S
+        saved = ctx.saved_tensors
+        masks, logits = list(saved[:S]), list(saved[S:2 * S])
+        tclass, bad, wsum = saved[2 * S:2 * S + 3]
+        gloss = gloss.contiguous().float()
+        gm = [None] * S
+        if plan.want_masks and any(ctx.needs_input_grad[1:1 + S]):
+            g = K.m2f_mask_loss_backward(masks, plan.tmask, plan.tstart, plan.match, bad, plan.points, saved[2 * S + 3], gloss, plan.scales,
+                                         plan.split, pixel_major=plan.pixel_major, Q=plan.Q)
+            gm = [g[s] for s in range(S)]
+        gl = [None] * S
+        if any(ctx.needs_input_grad[1 + S:]):
+            g = K.m2f_label_loss_backward(logits, tclass, bad, plan.weight, wsum, gloss)
+            gl = [g[s] for s in range(S)]
+        return (None, *gm, *gl)
+
+
+class SetCriterion(nn.Module):
+    """The loss of Mask2Former's stage 2 (criterion.py:91-96): the Hungarian assignment between targets and predictions, then the
+    class loss and the sampled mask losses of every matched pair. Constructor, set_extra_loss, forward()'s dict and __repr__ of
+    the reference; `mask_loss_with_pixel_selection` selects loss_masks_aug (:244-310) instead of loss_masks (:312-363)."""
+
+    def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio, importance_sample_ratio,
+                 ood_loss=None, margin=None, deep_supervision=False, mask_loss_with_pixel_selection: bool = False):
+        super().__init__()
+        self.num_classes, self.matcher, self.weight_dict, self.eos_coef, self.losses = num_classes, matcher, weight_dict, eos_coef, losses
+        self.num_points, self.oversample_ratio, self.importance_sample_ratio = num_points, oversample_ratio, importance_sample_ratio
+        self.ood_loss, self.margin, self.deep_supervision = ood_loss, margin, deep_supervision
+        self.extra_loss = None
+        weight = torch.ones(num_classes + 1)                # the class weights of F.cross_entropy: eos_coef for "no object"
+        weight[-1] = eos_coef
+        self.register_buffer("empty_weight", weight)
+        self.mask_loss_with_pixel_selection = mask_loss_with_pixel_selection
+        # Set keep_tables to have a call leave its point table [S * sum T, num_points, 2] and the matcher's table [S, B, Tmax] int32
+        # (both on the device) in last_points / last_match, for tests and diagnosis. Off by default: the point table is
+        # S * sum T * num_points * 8 bytes, about 190 MB at C4, and would stay allocated between calls.
+        self.keep_tables = False
+        self.last_points = None
+        self.last_match = None
+
+    def selection(self):
+        """(mode, K, k) of the rows that select their points (criterion.py:335-341; :374-387 for loss_masks_aug)."""
+        if self.mask_loss_with_pixel_selection:
+            return ("clean",) + selection_counts(self.num_points, CLEAN_OVERSAMPLE_RATIO, CLEAN_IMPORTANCE_SAMPLE_RATIO)
+        assert self.oversample_ratio >= 1 and 0 <= self.importance_sample_ratio <= 1
+        return ("uncertain",) + selection_counts(self.num_points, self.oversample_ratio, self.importance_sample_ratio)
+
+    def _check_losses(self):
+        for loss in self.losses:
+            if loss == "ood":
+                raise NotImplementedError("SetCriterion on HIP has no loss_ood (criterion.py:128-187): it needs the backward of the class mix "
+                                          "(einsum of class and mask probabilities), which this package does not have; compute it in the caller")
+            assert loss in ("labels", "masks"), f"do you really want to compute {loss} loss?"
+
+    def forward(self, outputs, targets, *, num_masks=None, point_candidates=None, random_points=None, matcher_points=None):
+        """The loss computation (criterion.py:432-469). outputs: {"pred_logits" [B,Q,C+1], "pred_masks" [B,Q,h,w] (or
+        "pred_masks_pixel_major" [B,h,w,ldq]), "aux_outputs": [the same per earlier step]}; targets: per image {"labels" [T_b],
+        "masks" [T_b,H,W]}. Returns {loss_ce, loss_mask, loss_dice} (or the four keys of loss_masks_aug), then `<key>_<i>` for
+        aux_outputs[i] when deep_supervision is set: 0-d float32 device tensors attached to autograd, weight_dict NOT applied.
+        num_masks: overrides max(sum T_b, 1). point_candidates [S, rows that select, K, 2], random_points [S * sum T, Pr, 2],
+        matcher_points [S,B,P,2]: inject the random numbers (see kernels.m2f_point_select / HungarianMatcher.match_steps)."""
+        self._check_losses()
+        steps = _steps_of(outputs) if self.deep_supervision else _steps_of({k: v for k, v in outputs.items() if k != "aux_outputs"})
+        S = len(steps)
+        pixel_major = "pred_masks" not in steps[0]
+        masks = [o["pred_masks_pixel_major" if pixel_major else "pred_masks"] for o in steps]
+        logits = [o["pred_logits"] for o in steps]
+        if not all(t.is_cuda for t in masks + logits):
+            raise RuntimeError("SetCriterion runs on an MI355X only (CUDA tensors); there is no CPU path")
+        dev = logits[0].device
+        B, Q, C1 = logits[0].shape
+        if C1 != self.num_classes + 1:
+            raise ValueError(f"pred_logits have {C1} classes, the criterion {self.num_classes} + 1")
+        packed = self.matcher._pack_targets(targets, dev)
+        tmask, tstart, labels, counts = packed
+        match = self.matcher.match_steps(steps, targets, point_coords=matcher_points, device_only=True, packed=packed)
+        total_t = sum(counts)
+        P = int(self.num_points)
+        masks = [m.float() for m in masks]
+        logits = [c.float() for c in logits]
+
+        plan = _Plan()
+        plan.tmask, plan.tstart, plan.labels, plan.match = tmask, tstart, labels, match
+        plan.weight = self.empty_weight.to(device=dev, dtype=torch.float32)
+        plan.num_points, plan.pixel_major, plan.Q, plan.S = P, pixel_major, Q, S
+        plan.want_masks = "masks" in self.losses
+        mode, n_cand, n_keep = self.selection()
+        if self.mask_loss_with_pixel_selection:
+            plan.split = sum(counts[:B // 2])                   # criterion.py:255: images b < B/2 are "original", the rest "aug"
+            n_orig, n_aug = plan.split, total_t - plan.split
+            plan.scales = (2.0 / n_orig if n_orig else 0.0, 1.0 / n_aug if n_aug else 0.0)
+            sel_start, keys = plan.split, AUG_KEYS
+        else:
+            if num_masks is None:
+                num_masks = max(total_t, 1)                     # criterion.py:447-453 (its all_reduce is dead code: one process per GPU group)
+            plan.split = None
+            plan.scales = (1.0 / float(num_masks),)
+            sel_start, keys = 0, PLAIN_KEYS
+        plan.points = None
+        if plan.want_masks:
+            with torch.no_grad():
+                n_random = P if (sel_start > 0 or n_keep == 0) else P - n_keep
+                if point_candidates is None and n_keep > 0:
+                    point_candidates = torch.rand((S, total_t - sel_start, n_cand, 2), device=dev)
+                if random_points is None:
+                    random_points = torch.rand((S * total_t, n_random, 2), device=dev)
+                plan.points = K.m2f_point_select([m.detach() for m in masks], tmask, tstart, match, point_candidates if n_keep > 0 else None,
+                                                 random_points, n_keep, P, mode=mode, sel_start=sel_start, pixel_major=pixel_major, Q=Q)
+        self.last_points, self.last_match = (plan.points, match) if self.keep_tables else (None, None)
+
+        table = _CriterionFunction.apply(plan, *masks, *logits)
+        cols = [j for j, key in enumerate(keys) if ("labels" in self.losses and j == 0) or (plan.want_masks and j > 0)]
+        order = [j for loss in self.losses for j in cols if (j == 0) == (loss == "labels")]
+        losses = {}
+        for s in range(S):
+            for j in order:
+                losses[keys[j] if s == 0 else f"{keys[j]}_{s - 1}"] = table[s, j]
+        return losses
+
+    def set_extra_loss(self, extra_loss):
+        self.extra_loss = extra_loss
+
+    def __repr__(self):
+        pad = " " * 4
+        shown = ("losses", "weight_dict", "num_classes", "eos_coef", "num_points", "oversample_ratio", "importance_sample_ratio")
+        return "\n".join([f"Criterion {type(self).__name__}", f"{pad}matcher: {self.matcher.__repr__(_repr_indent=8)}"]
+                         + [f"{pad}{k}: {getattr(self, k)}" for k in shown])

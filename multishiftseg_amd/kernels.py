@@ -1292,6 +1292,219 @@ def m2f_match_assign(cost, tcount):
     return match, status
 
 
+# ---- SetCriterion of Mask2Former: class and sampled-mask losses (csrc/m2f_loss.hip) -----------------------------------------------
+_LOSS_MODES = {"uncertain": 1, "clean": 2}
+
+
+def _loss_maps(name, mask_logits, pixel_major, Q):
+    """The S mask-logit tensors of a call -> (contiguous list, host pointer array, (image, query, pixel) strides, h, w, Q)."""
+    masks = [mask_logits] if isinstance(mask_logits, torch.Tensor) else list(mask_logits)
+    for t in masks:
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    masks = [m.contiguous() for m in masks]
+    if masks[0].dim() != 4 or any(m.shape != masks[0].shape for m in masks):
+        raise ValueError(f"{name}: the mask logits of all steps share one 4-d shape, got {[tuple(m.shape) for m in masks]}")
+    if pixel_major:
+        _, h, w, ldq = masks[0].shape
+        strides = (h * w * ldq, 1, ldq)
+        Q = ldq if Q is None else int(Q)
+    else:
+        _, ldq, h, w = masks[0].shape
+        strides = (h * w * ldq, h * w, 1)
+        Q = ldq if Q is None else int(Q)
+    if Q < 1 or Q > ldq or (not pixel_major and Q != ldq):
+        raise ValueError(f"{name}: Q {Q} does not fit mask logits {tuple(masks[0].shape)}")
+    return masks, (ctypes.c_void_p * len(masks))(*[m.data_ptr() for m in masks]), strides, h, w, Q
+
+
+def _loss_table(name, S, B, tmask, tstart, match, *more):
+    """Checks of the target pack and the [S,B,Tmax] match table shared by the wrappers below -> (total_t, H, W, Tmax)."""
+    for t in (tmask, tstart, match) + more:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on an MI355X only (CUDA tensors); there is no CPU path")
+    if tmask.dtype != torch.uint8 or tstart.dtype != torch.int32 or match.dtype != torch.int32:
+        raise RuntimeError(f"{name} takes uint8 target masks and an int32 tstart / match table on the device")
+    if tmask.dim() != 3 or match.dim() != 3 or tuple(match.shape[:2]) != (S, B) or tstart.numel() != B + 1 or match.shape[2] < 1:
+        raise ValueError(f"{name}: tmask {tuple(tmask.shape)} / tstart {tuple(tstart.shape)} / match {tuple(match.shape)} do not match S {S}, B {B}")
+    total_t, H, W = tmask.shape
+    return total_t, H, W, match.shape[2]
+
+
+def _loss_ws(R, K, P, device):
+    nbytes = _lib.value("mss_m2f_loss_workspace_bytes", R, K, P)
+    return torch.empty(max(1, nbytes // 4), device=device, dtype=torch.float32)
+
+
+def _loss_groups(name, scales, split, total_t):
+    """(scale0,) = one group of rows (loss_masks), (scale0, scale1) + split = two (loss_masks_aug) -> (split, scale0, scale1, ncols)."""
+    scales = tuple(float(v) for v in scales)
+    if len(scales) == 1:
+        return total_t, scales[0], 0.0, 3
+    if len(scales) != 2 or split is None or not 0 <= int(split) <= total_t:
+        raise ValueError(f"{name}: scales {scales} / split {split} for {total_t} targets")
+    return int(split), scales[0], scales[1], 5
+
+
+def m2f_point_select(mask_logits, tmask, tstart, match, candidates, random_points, k, num_points, mode="uncertain", sel_start=0,
+                     pixel_major=False, Q=None):
+    """The sampled points of every matched mask (criterion.py:335-341 = detectron2's get_uncertain_point_coords_with_randomness,
+    mode "uncertain": key -|x|; :371-407, mode "clean": key -BCEWithLogits(x, t); :365-369 for the rows before sel_start) in one
+    launch. mask_logits: list of S tensors, NCHW [B,Q,h,w] or with pixel_major [B,h,w,ldq] (then Q <= ldq); tmask uint8
+    [sum T,H,W], tstart int32 [B+1], match int32 [S,B,Tmax] (the matcher's device table). Row r = s * sum T + g (target g).
+    candidates [S, sum T - sel_start, K, 2] ((x, y) in [0,1); None where k == 0): a row with g >= sel_start keeps its k candidates
+    with the largest key, in ascending candidate index -- ties at the k-th largest go to the lowest index, -0.0 == +0.0, a NaN key
+    ranks last -- followed by the first num_points - k of random_points [S * sum T, Pr, 2]; a row before sel_start takes its
+    first num_points random points. -> points [S * sum T, num_points, 2]; all 0 for a row whose table entry is -1."""
+    name = "m2f_point_select"
+    masks, mp, strides, h, w, Q = _loss_maps(name, mask_logits, pixel_major, Q)
+    S, B = len(masks), masks[0].shape[0]
+    floats = [t for t in (candidates, random_points) if t is not None]
+    for t in floats:
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    total_t, H, W, Tmax = _loss_table(name, S, B, tmask, tstart, match)
+    P, k, sel_start = int(num_points), int(k), int(sel_start)
+    if mode not in _LOSS_MODES:
+        raise ValueError(f"{name}: mode {mode!r} is not one of {sorted(_LOSS_MODES)}")
+    R = S * total_t
+    K = 0
+    if k > 0:
+        if candidates is None or candidates.dim() != 4 or tuple(candidates.shape[:2]) != (S, total_t - sel_start) or candidates.shape[3] != 2:
+            raise ValueError(f"{name}: candidates {None if candidates is None else tuple(candidates.shape)} for S {S}, {total_t - sel_start} selecting targets")
+        K = candidates.shape[2]
+    need = P if (sel_start > 0 or k == 0) else P - k
+    Pr = 0
+    if random_points is not None:
+        if random_points.shape[-1] != 2 or random_points.numel() != R * random_points.shape[-2] * 2:
+            raise ValueError(f"{name}: random_points {tuple(random_points.shape)} for {R} rows")
+        Pr = random_points.shape[-2]
+    if P < 1 or k < 0 or k > min(K, P) or not 0 <= sel_start <= total_t or Pr < need:
+        raise ValueError(f"{name}: num_points {P}, k {k}, K {K}, sel_start {sel_start}, {Pr} random points per row ({need} needed)")
+    dev = masks[0].device
+    points = torch.empty((R, P, 2), device=dev, dtype=torch.float32)
+    ws = _loss_ws(R, K, P, dev)
+    cand = candidates.contiguous() if k > 0 else None
+    rnd = random_points.contiguous() if random_points is not None else None
+    call("mss_m2f_loss_select_f32", mp, strides[0], strides[1], strides[2], h, w, ptr(tmask.contiguous()), ptr(tstart.contiguous()),
+         ptr(match.contiguous()), total_t, H, W, ptr(cand), ptr(rnd), S, B, Q, Tmax, K, k, P, Pr, _LOSS_MODES[mode], sel_start, ptr(ws),
+         ptr(points))
+    return points
+
+
+def m2f_mask_loss(mask_logits, tmask, tstart, match, points, pixel_major=False, Q=None):
+    """The four sums both mask losses need (criterion.py:343-358, sigmoid_ce_loss :49-66, dice_loss :22-41) of every row at its
+    points [S * sum T, P, 2]: -> rows [S * sum T, 4] float64 = sum_p BCEWithLogits(x, t), sum_p sigmoid(x) t, sum_p sigmoid(x),
+    sum_p t (NaN for a row whose table entry is -1), x / t = the source / target map sampled bilinearly. One launch, one order."""
+    name = "m2f_mask_loss"
+    masks, mp, strides, h, w, Q = _loss_maps(name, mask_logits, pixel_major, Q)
+    S, B = len(masks), masks[0].shape[0]
+    total_t, H, W, Tmax = _loss_table(name, S, B, tmask, tstart, match, points)
+    R = S * total_t
+    if points.dtype != torch.float32 or points.dim() != 3 or points.shape[0] != R or points.shape[2] != 2 or points.shape[1] < 1:
+        raise ValueError(f"{name}: points {tuple(points.shape)} {points.dtype} for {R} rows")
+    rows = torch.empty((R, 4), device=masks[0].device, dtype=torch.float64)
+    call("mss_m2f_loss_mask_forward_f32", mp, strides[0], strides[1], strides[2], h, w, ptr(tmask.contiguous()), ptr(tstart.contiguous()),
+         ptr(match.contiguous()), total_t, H, W, ptr(points.contiguous()), S, B, Q, Tmax, points.shape[1], ptr(rows))
+    return rows
+
+
+def m2f_label_loss(class_logits, labels, tstart, match, weight, rows, num_points, scales, split=None):
+    """loss_labels (criterion.py:189-205) of S steps and the fold of the row table into the per-step mask losses (:301-306,
+    :356-359), one workgroup per step. class_logits: list of S [B,Q,C+1]; labels int32 [sum T]; weight [C+1] (empty_weight);
+    rows: m2f_mask_loss's table (None: no mask losses, their columns are 0). scales = (1 / num_masks,) -> loss [S,3] =
+    (loss_ce, loss_mask, loss_dice); scales = (2 / n_original, 1 / n_aug) with split = the first target of the aug half ->
+    loss [S,5] = (loss_ce, loss_original_mask, loss_original_dice, loss_aug_mask, loss_aug_dice). Also returns tclass [S,B,Q]
+    int32 (target_classes), bad [S] int32 (1: a table entry of -1 or a label outside the classes; the step's losses are NaN) and
+    wsum [S] float64 (sum of the class weights): what m2f_label_loss_backward / m2f_mask_loss_backward take."""
+    name = "m2f_label_loss"
+    clss = [class_logits] if isinstance(class_logits, torch.Tensor) else list(class_logits)
+    for t in clss + [weight]:
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    for t in (labels, tstart, match):
+        if not t.is_cuda or t.dtype != torch.int32:
+            raise RuntimeError(f"{name} takes int32 labels / tstart / match on the device")
+    clss = [c.contiguous() for c in clss]
+    S = len(clss)
+    if clss[0].dim() != 3 or any(c.shape != clss[0].shape for c in clss):
+        raise ValueError(f"{name}: the class logits of all steps share one [B,Q,C+1] shape, got {[tuple(c.shape) for c in clss]}")
+    B, Q, C1 = clss[0].shape
+    total_t = labels.numel()
+    if match.dim() != 3 or tuple(match.shape[:2]) != (S, B) or tstart.numel() != B + 1 or weight.numel() != C1 or C1 < 2:
+        raise ValueError(f"{name}: match {tuple(match.shape)} / tstart {tuple(tstart.shape)} / weight {tuple(weight.shape)} do not match "
+                         f"S {S}, B {B}, C+1 {C1}")
+    split, scale0, scale1, ncols = _loss_groups(name, scales, split, total_t)
+    dev = clss[0].device
+    if rows is None:
+        rows = torch.zeros((S * total_t, 4), device=dev, dtype=torch.float64)
+        scale0 = scale1 = 0.0
+    if not rows.is_cuda or rows.dtype != torch.float64 or tuple(rows.shape) != (S * total_t, 4):
+        raise ValueError(f"{name}: rows {tuple(rows.shape)} {rows.dtype} for {S * total_t} rows")
+    tclass = torch.full((S, B, Q), C1 - 1, device=dev, dtype=torch.int32)
+    bad = torch.zeros((S,), device=dev, dtype=torch.int32)
+    wsum = torch.empty((S,), device=dev, dtype=torch.float64)
+    loss = torch.empty((S, ncols), device=dev, dtype=torch.float32)
+    cp = (ctypes.c_void_p * S)(*[c.data_ptr() for c in clss])
+    call("mss_m2f_loss_finalize_f32", cp, ptr(labels.contiguous()) if total_t else None, ptr(tstart.contiguous()), ptr(match.contiguous()),
+         ptr(weight.contiguous()), ptr(rows.contiguous()) if total_t else None, total_t, S, B, Q, C1, match.shape[2], int(num_points), split,
+         scale0, scale1, ncols, ptr(tclass), ptr(bad), ptr(wsum), ptr(loss))
+    return loss, tclass, bad, wsum
+
+
+def m2f_mask_loss_backward(mask_logits, tmask, tstart, match, bad, points, rows, gloss, scales, split=None, pixel_major=False, Q=None):
+    """d / d mask_logits of m2f_label_loss's mask columns: gloss [S,ncols] fp32 is the upstream gradient of its loss table.
+    -> one tensor [S, *mask_logits[0].shape] (step s = its slice) in the layout of the input: the map of every matched query
+    is written whole by its row's workgroup from an int64 fixed-point window (no float atomics: bit-reproducible), every other
+    element -- unmatched queries, the padding columns of a pixel-major layout, the steps marked bad -- is 0."""
+    name = "m2f_mask_loss_backward"
+    masks, mp, strides, h, w, Q = _loss_maps(name, mask_logits, pixel_major, Q)
+    S, B = len(masks), masks[0].shape[0]
+    total_t, H, W, Tmax = _loss_table(name, S, B, tmask, tstart, match, bad, points, rows, gloss)
+    R = S * total_t
+    split, scale0, scale1, ncols = _loss_groups(name, scales, split, total_t)
+    if points.dtype != torch.float32 or points.dim() != 3 or points.shape[0] != R or points.shape[2] != 2 or points.shape[1] < 1 \
+            or rows.dtype != torch.float64 or tuple(rows.shape) != (R, 4) or gloss.dtype != torch.float32 or tuple(gloss.shape) != (S, ncols) \
+            or bad.dtype != torch.int32 or bad.numel() != S:
+        raise ValueError(f"{name}: points {tuple(points.shape)} / rows {tuple(rows.shape)} / gloss {tuple(gloss.shape)} / bad {tuple(bad.shape)} "
+                         f"do not match {R} rows, S {S}, {ncols} loss columns")
+    P = points.shape[1]
+    dev = masks[0].device
+    grads = torch.zeros((S,) + tuple(masks[0].shape), device=dev, dtype=torch.float32)
+    ws = _loss_ws(R, 0, P, dev)
+    gp = (ctypes.c_void_p * S)(*[grads[s].data_ptr() for s in range(S)])
+    call("mss_m2f_loss_mask_backward_f32", mp, strides[0], strides[1], strides[2], h, w, ptr(tmask.contiguous()), ptr(tstart.contiguous()),
+         ptr(match.contiguous()), ptr(bad.contiguous()), total_t, H, W, ptr(points.contiguous()), ptr(rows.contiguous()), ptr(gloss.contiguous()),
+         S, B, Q, Tmax, P, split, scale0, scale1, ncols, ptr(ws), gp)
+    return grads
+
+
+def m2f_label_loss_backward(class_logits, tclass, bad, weight, wsum, gloss):
+    """d loss_ce / d class_logits: -> [S,B,Q,C+1] = weight[c] / wsum (softmax - onehot) gloss[s,0] (0 for a step marked bad);
+    tclass / bad / wsum from m2f_label_loss, gloss [S,ncols] the upstream gradient of its loss table."""
+    name = "m2f_label_loss_backward"
+    clss = [class_logits] if isinstance(class_logits, torch.Tensor) else list(class_logits)
+    for t in clss + [weight, gloss]:
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    if not (tclass.is_cuda and bad.is_cuda and wsum.is_cuda):
+        raise RuntimeError(f"{name} runs on an MI355X only (CUDA tensors); there is no CPU path")
+    clss = [c.contiguous() for c in clss]
+    S = len(clss)
+    B, Q, C1 = clss[0].shape
+    if any(c.shape != clss[0].shape for c in clss) or tuple(tclass.shape) != (S, B, Q) or tclass.dtype != torch.int32 or bad.dtype != torch.int32 \
+            or bad.numel() != S or wsum.dtype != torch.float64 or wsum.numel() != S or weight.numel() != C1 or gloss.dim() != 2 \
+            or gloss.shape[0] != S or gloss.shape[1] not in (3, 5):
+        raise ValueError(f"{name}: tclass {tuple(tclass.shape)} / bad {tuple(bad.shape)} / wsum {tuple(wsum.shape)} / gloss {tuple(gloss.shape)} "
+                         f"do not match {S} class logits {tuple(clss[0].shape)}")
+    grads = torch.empty((S, B, Q, C1), device=clss[0].device, dtype=torch.float32)
+    cp = (ctypes.c_void_p * S)(*[c.data_ptr() for c in clss])
+    gp = (ctypes.c_void_p * S)(*[grads[s].data_ptr() for s in range(S)])
+    call("mss_m2f_loss_label_backward_f32", cp, ptr(tclass.contiguous()), ptr(bad.contiguous()), ptr(weight.contiguous()), ptr(wsum.contiguous()),
+         ptr(gloss.contiguous()), S, B, Q, C1, gloss.shape[1], gp)
+    return grads
+
+
 # ---- Mask2Former pixel-decoder glue (csrc/norm.hip) --------------------------------------------------------------------
 def groupnorm(x, gn, relu=False, out=None, out_sample_stride=None, out_ld=None, want_stat=False):
     """nn.GroupNorm `gn` on an Act (NHWC). `out`: optional float tensor to write into (e.g. the encoder's token buffer

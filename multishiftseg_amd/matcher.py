@@ -63,11 +63,13 @@ class HungarianMatcher(nn.Module):
         starts = [0]
         for n in counts:
             starts.append(starts[-1] + n)
-        tstart = torch.tensor(starts, dtype=torch.int32).to(device)
+        tstart = torch.tensor(starts, dtype=torch.int32)
+        if torch.device(device).type == "cuda":                # pinned + non_blocking: the copy does not stall the host
+            tstart = tstart.pin_memory().to(device, non_blocking=True)
         return tmask, tstart, labels, counts
 
     @torch.no_grad()
-    def match_steps(self, outputs_list, targets, *, point_coords=None, device_only=False):
+    def match_steps(self, outputs_list, targets, *, point_coords=None, device_only=False, packed=None):
         """The matching of S prediction steps (a list of {"pred_logits" [B,Q,C+1], "pred_masks" [B,Q,h,w]} dicts, or one output
         dict, taken with its "aux_outputs": the last output first) against the same targets in ONE call: two launches and one
         device-to-host copy. A step may give "pred_masks_pixel_major" [B,h,w,ldq] (the decoder's own layout) instead of
@@ -76,7 +78,8 @@ class HungarianMatcher(nn.Module):
 
         point_coords [S,B,P,2], (x, y) in [0,1): the sampled points. None draws them with one torch.rand((S,B,P,2)): the
         reference's distribution, NOT its draw order (it calls torch.rand(1,P,2) once per image, matcher.py:120), so the same
-        seed gives other points than the reference's."""
+        seed gives other points than the reference's. packed: the result of _pack_targets(targets, device), for a caller that
+        needs the packed targets itself (SetCriterion) and should not pack them twice."""
         steps = _steps_of(outputs_list)
         S = len(steps)
         B, Q = steps[0]["pred_logits"].shape[:2]
@@ -96,7 +99,7 @@ class HungarianMatcher(nn.Module):
             if self.num_points < 1:
                 raise ValueError("num_points must be positive to draw points")
             point_coords = torch.rand((S, B, self.num_points, 2), device=dev)
-        tmask, tstart, labels, counts = self._pack_targets(targets, dev)
+        tmask, tstart, labels, counts = self._pack_targets(targets, dev) if packed is None else packed
         _, match, status, buf = K.m2f_match_cost([m.float() for m in masks], [c.float() for c in logits], tmask, tstart, labels,
                                                  point_coords.to(device=dev, dtype=torch.float32),
                                                  (self.cost_class, self.cost_mask, self.cost_dice), Tmax=max(counts),
