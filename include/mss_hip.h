@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 14     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 15     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -38,7 +38,8 @@ extern "C" {
                                   its 9-launch form and second name are gone; the two-launch Feistel pairs entry point that mss_rcl_pairs_device2_f32 replaced
                                   in version 5 is gone;
                                   13 (additive): mss_m2f_match_workspace_bytes, mss_m2f_match_cost_f32, mss_m2f_match_assign_f32 (Hungarian matching);
-                                  14 (additive): the six mss_m2f_loss_* entry points (SetCriterion: class and sampled-mask losses) */
+                                  14 (additive): the six mss_m2f_loss_* entry points (SetCriterion: class and sampled-mask losses);
+                                  15 (additive): the five mss_m2f_mix_* entry points (SetCriterion.loss_ood: the class mix, forward and backward) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -685,6 +686,37 @@ int mss_m2f_loss_mask_backward_f32(const float* const* masks_host, long long img
 int mss_m2f_loss_label_backward_f32(const float* const* cls_host, const int* tclass, const int* bad, const float* weight,
                                     const double* wsum, const float* gloss, int S, int B, int Q, int C1, int ncols, float* const* grads_host,
                                     void* stream);
+
+/* ---- SetCriterion.loss_ood, RCL branch: the class mix, forward and backward (csrc/m2f_mix.hip) ----
+ * replaces, per prediction step, lib/network/mask2former/modeling/criterion.py:133-138 and :170-175 (softmax without the last
+ * column, sigmoid, einsum("bqc,bqhw->bchw") at the low resolution h x w), :166-168 and :177-179 (F.interpolate to (H, W), bilinear,
+ * align_corners=False, cropped to Ht x Wt), :181 (-max over the classes), and what autograd derives from them. fp32; Q <= 128,
+ * 1 <= C <= 32. masks / strides as in mss_m2f_match_cost_f32: NCHW [B,Q,h,w] (pixel_stride 1, any Q) or pixel-major [B,h,w,ldq]
+ * (query_stride 1, pixel_stride ldq, ldq % 4 == 0, Q <= ldq; the columns Q..ldq-1 are never read). No float atomics, no memset:
+ * every output element is written once, every sum runs in one fixed order, two runs give the same bits.
+ *
+ * forward (:135-138): prob [B,Q,C] = softmax(cls [B,Q,C+1])[..., :C]; mix [B,C,h,w] = sum_q prob[b,q,c] sigmoid(masks[b,q,p]),
+ *   the queries in index order.
+ * upsample (:166-168, :177-181): neg_max == 0: out [B,Cl,Ht,Wt], Cl = min(C,19), = the first Cl channels interpolated;
+ *   neg_max != 0: out [B,Ht,Wt] = -max over all C interpolated channels, which are never stored. The scale is h / H (w / W), not
+ *   h / Ht; the coordinate is src_coord of csrc/mss_bilinear.h and the blend h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11) as ATen.
+ * upsample_backward: dmix [B,C,h,w], written whole, from dlogits [B,Cl,Ht,Wt] and / or dscore [B,Ht,Wt] (either may be NULL; mix
+ *   is needed with dscore). A low-resolution pixel sums over the output pixels of the crop whose taps contain it, rows then columns
+ *   ascending. For dscore the C interpolated values of the output pixel are recomputed and -dscore goes to the largest; equal
+ *   values: the lowest class index (torch.max leaves that unspecified).
+ * backward: dmasks in the layout of masks (the pad columns of a pixel-major layout written as 0) = sigmoid'(x) sum_c prob dmix;
+ *   dcls [B,Q,C+1] = the softmax backward with the dropped column of dP[b,q,c] = sum_p dmix[b,c,p] sigmoid(x[b,q,p]), summed per
+ *   workgroup (mss_m2f_mix_backward_chunks(h*w) workgroups per image) into partial [B, chunks, Q, C] double and folded in index order. */
+int mss_m2f_mix_backward_chunks(long long hw);
+int mss_m2f_mix_forward_f32(const float* cls, const float* masks, long long img_stride, long long query_stride, long long pixel_stride,
+                            int B, int Q, int C, int h, int w, float* prob, float* mix, void* stream);
+int mss_m2f_mix_upsample_f32(const float* mix, int B, int C, int h, int w, int H, int W, int Ht, int Wt, int neg_max, float* out,
+                             void* stream);
+int mss_m2f_mix_upsample_backward_f32(const float* dlogits, const float* dscore, const float* mix, int B, int C, int h, int w, int H,
+                                      int W, int Ht, int Wt, float* dmix, void* stream);
+int mss_m2f_mix_backward_f32(const float* dmix, const float* prob, const float* cls, const float* masks, long long img_stride,
+                             long long query_stride, long long pixel_stride, int B, int Q, int C, int h, int w, double* partial,
+                             float* dmasks, float* dcls, void* stream);
 
 /* ---- on-device data path of the DeepLab trainer (csrc/data.hip) ----
  * One kernel for what DiverseCityscapes.__getitem__ + its transforms + the trainer's batch concat do per step

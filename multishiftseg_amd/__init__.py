@@ -12,7 +12,10 @@ def __getattr__(name):
     if name == "SetCriterion":
         from .criterion import SetCriterion
         return SetCriterion
+    if name == "class_mix_upsample":
+        from .criterion import class_mix_upsample
+        return class_mix_upsample
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion"]
+__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample"]

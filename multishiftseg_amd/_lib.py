@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 14         # include/mss_hip.h
+MSS_ABI_VERSION = 15         # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -168,6 +168,11 @@ SIGNATURES = {
     "mss_m2f_loss_finalize_f32": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, c_double, c_double, I, P, P, P, P, P],
     "mss_m2f_loss_mask_backward_f32": [P, L, L, L, I, I, P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, c_double, c_double, I, P, P, P],
     "mss_m2f_loss_label_backward_f32": [P, P, P, P, P, P, I, I, I, I, I, P, P],
+    "mss_m2f_mix_backward_chunks": [L],
+    "mss_m2f_mix_forward_f32": [P, P, L, L, L, I, I, I, I, I, P, P, P],
+    "mss_m2f_mix_upsample_f32": [P, I, I, I, I, I, I, I, I, I, P, P],
+    "mss_m2f_mix_upsample_backward_f32": [P, P, P, I, I, I, I, I, I, I, I, P, P],
+    "mss_m2f_mix_backward_f32": [P, P, P, P, L, L, L, I, I, I, I, I, P, P, P, P],
     "mss_oodm_compact_lanes_f32": [P, P, L, L, L, P, P, P],
     "mss_oodm_compact_lanes_batch_f32": [P, I, L, L, P],
     "mss_oodm_gather_lanes_u32": [P, L, P, P, P, P],
@@ -198,7 +203,7 @@ SIGNATURES = {
     "mss_peak_scatter_f32": [P, P, L, I, I, L, P],
 }
 # entry points that return a plain value rather than a status code
-_VALUE_RETURNING = {"mss_chan_compact_wanted", "mss_gemm_split_last_mfma", "mss_conv2d_wgrad_route", "mss_gemm_split_weights_bytes", "mss_abi_version", "mss_env_reset", "mss_env_generation", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_conv2d_kpad", "mss_conv2d_forward_route", "mss_rcl_num_compact_blocks", "mss_wino_num_tiles",
+_VALUE_RETURNING = {"mss_chan_compact_wanted", "mss_gemm_split_last_mfma", "mss_conv2d_wgrad_route", "mss_gemm_split_weights_bytes", "mss_abi_version", "mss_env_reset", "mss_env_generation", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_m2f_mix_backward_chunks", "mss_conv2d_kpad", "mss_conv2d_forward_route", "mss_rcl_num_compact_blocks", "mss_wino_num_tiles",
                     "mss_oodm_sort_temp_bytes", "mss_oodm_compact_lanes_cap", "mss_oodm_rank_blocks", "mss_wino_output_stats_parts",
                     "mss_conv2d_wgrad_workspace_bytes", "mss_col_reduce_accum_doubles", "mss_colsum_workspace_floats",
                     "mss_add_layernorm_bwd_workspace_floats", "mss_groupnorm_workspace_floats",

@@ -1,10 +1,17 @@
-"""SetCriterion of Mask2Former (lib/network/mask2former/modeling/criterion.py:91-488) on the HIP kernels of csrc/m2f_loss.hip.
+"""SetCriterion of Mask2Former (lib/network/mask2former/modeling/criterion.py:91-488) on the HIP kernels of csrc/m2f_loss.hip and
+csrc/m2f_mix.hip.
 
 The reference walks the prediction steps one by one and, per step, composes torch.rand, three grid_samples, a topk, a gather and two
 jit-scripted loss functions over the matched masks; its backward scatters through grid_sample with float atomics. Here the class
 loss and the sampled mask losses of ALL S steps (the last output and its aux_outputs), all images and all matched masks are five
 launches (three forward, two backward) after the matcher's two, with no device-to-host copy, and two runs give the same bits.
-There is no CPU path. `loss_ood` is not here: it needs the class-mix backward, which this package does not have yet.
+There is no CPU path.
+
+`loss_ood` (criterion.py:128-187) is here in its RCL branch, the one the entry scripts select. Per step it is two autograd nodes of
+`class_mix_upsample` -- the class mix of (pred_logits, pred_masks) upsampled and cropped to the 19 logit maps, and that of
+(pred_logits_ood, pred_masks_ood) reduced to -max over the classes at full size -- followed by `extra_loss(logits, score, target)`.
+The mix and the sigmoids stay at the low resolution, the backward gathers (no float atomics) and stores no argmax map: it
+recomputes it. The `margin` and `bce` branches, which no entry script selects, raise NotImplementedError.
 
 Deviations from the reference, all deliberate:
   * the random numbers have the reference's distribution, not its draw order (one torch.rand per kind for all rows of all steps);
@@ -13,8 +20,15 @@ Deviations from the reference, all deliberate:
   * mask_loss_with_pixel_selection is a constructor argument (the reference reads a global config, criterion.py:424-426);
   * weight_dict is stored and shown, not applied (the reference applies it in maskformer_model.py);
   * a problem the matcher could not solve, or a label outside [0, num_classes), makes every loss of its step NaN and the step's
-    gradients 0, with no host synchronisation (the reference raises inside scipy / indexes out of range).
+    gradients 0, with no host synchronisation (the reference raises inside scipy / indexes out of range);
+  * loss_ood: where two classes tie for the maximum of the interpolated mix, the gradient of the score goes to the lowest class
+    index (torch.max leaves that unspecified);
+  * loss_ood: when pred_masks_ood is pred_masks, the two nodes each compute their own sigmoids and autograd adds the two mask
+    gradients; the sum is the same as for two separate tensors;
+  * loss_ood: a pixel-major step reads "pred_masks_ood_pixel_major", or "pred_masks_pixel_major" where that key is absent (this
+    package's decoder shares the tensor); sem_seg may be a device tensor, which is then never copied to the host.
 """
+import numpy as np
 import torch
 from torch import nn
 
@@ -77,6 +91,42 @@ class _CriterionFunction(torch.autograd.Function):
         return (None, *gm, *gl)
 
 
+class _ClassMixUpsample(torch.autograd.Function):
+    """One node for softmax, sigmoid, einsum, interpolate, crop and (mode "neg_max") -max over the classes."""
+
+    @staticmethod
+    def forward(ctx, class_logits, mask_logits, size, crop, mode, pixel_major, Q):
+        mix, prob = K.m2f_class_mix(class_logits, mask_logits, pixel_major=pixel_major, Q=Q)
+        out = K.m2f_mix_upsample(mix, size, crop, mode)
+        ctx.save_for_backward(class_logits, mask_logits, mix, prob)
+        ctx.cfg = (size, crop, mode, pixel_major, Q)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        class_logits, mask_logits, mix, prob = ctx.saved_tensors
+        size, crop, mode, pixel_major, Q = ctx.cfg
+        g = g.contiguous().float()
+        dmix = K.m2f_mix_upsample_backward(mix, size, crop, **{"dlogits" if mode == "logits" else "dscore": g})
+        dmasks, dcls = K.m2f_class_mix_backward(dmix, prob, class_logits, mask_logits, pixel_major=pixel_major, Q=Q)
+        return dcls, dmasks, None, None, None, None, None
+
+
+def class_mix_upsample(class_logits, mask_logits, size, crop=None, mode="logits", pixel_major=False, Q=None):
+    """interpolate(einsum("bqc,bqhw->bchw", softmax(class_logits, -1)[..., :-1], sigmoid(mask_logits)), size, bilinear,
+    align_corners=False)[:, :, :crop[0], :crop[1]] as ONE differentiable op (criterion.py:133-138, :166-168, :170-181).
+    mode "logits": its first min(C, 19) channels [B,Cl,Ht,Wt]; "neg_max": -max over all C channels [B,Ht,Wt]. class_logits
+    [B,Q,C+1], mask_logits [B,Q,h,w] or, with pixel_major, [B,h,w,ldq]; float32 on the device. Gradients reach both inputs; where
+    classes tie for the maximum, the lowest class index takes the gradient."""
+    if mode not in ("logits", "neg_max"):
+        raise ValueError(f"class_mix_upsample: mode {mode!r} is not 'logits' or 'neg_max'")
+    size = (int(size[0]), int(size[1]))
+    crop = size if crop is None else (int(crop[0]), int(crop[1]))
+    return _ClassMixUpsample.apply(class_logits.float().contiguous(), mask_logits.float().contiguous(), size, crop, mode, bool(pixel_major),
+                                   None if Q is None else int(Q))
+
+
 class SetCriterion(nn.Module):
     """The loss of Mask2Former's stage 2 (criterion.py:91-96): the Hungarian assignment between targets and predictions, then the
     class loss and the sampled mask losses of every matched pair. Constructor, set_extra_loss, forward()'s dict and __repr__ of
@@ -107,18 +157,60 @@ class SetCriterion(nn.Module):
         assert self.oversample_ratio >= 1 and 0 <= self.importance_sample_ratio <= 1
         return ("uncertain",) + selection_counts(self.num_points, self.oversample_ratio, self.importance_sample_ratio)
 
+    def _check_ood(self):
+        """Which loss_ood this is (criterion.py:140-185), before anything is computed."""
+        if self.ood_loss == "RCL":
+            if self.extra_loss is None:                         # the reference asserts (criterion.py:163)
+                raise NotImplementedError("loss_ood with ood_loss 'RCL' needs an extra_loss: call set_extra_loss(RelContrastiveLoss(...)) first")
+        elif self.ood_loss in ("margin", "bce"):
+            raise NotImplementedError(f"SetCriterion on HIP has loss_ood for ood_loss 'RCL' only (criterion.py:162-183); {self.ood_loss!r} "
+                                      "(:140-161) is selected by no entry script")
+        else:
+            raise ValueError("define_ood_loss")
+
     def _check_losses(self):
         for loss in self.losses:
             if loss == "ood":
-                raise NotImplementedError("SetCriterion on HIP has no loss_ood (criterion.py:128-187): it needs the backward of the class mix "
-                                          "(einsum of class and mask probabilities), which this package does not have; compute it in the caller")
+                self._check_ood()
+                continue
             assert loss in ("labels", "masks"), f"do you really want to compute {loss} loss?"
+
+    def loss_ood(self, outputs, targets):
+        """criterion.py:128-138, 162-187 for one prediction step: outputs holds pred_logits, pred_masks (or pred_masks_pixel_major),
+        pred_logits_ood and pred_masks_ood; targets per image "ood_mask" (only its shape (H, W) is used) and "sem_seg" [Ht,Wt]
+        (numpy array or tensor). extra_loss gets a fresh int64 copy of the stacked sem_seg, as the reference's torch.tensor(target):
+        RelContrastiveLoss changes it in place. -> {"loss_ood": 0-d tensor}."""
+        self._check_ood()
+        pixel_major = "pred_masks" not in outputs
+        cls, cls_ood = outputs["pred_logits"], outputs["pred_logits_ood"]
+        if pixel_major:
+            masks = outputs["pred_masks_pixel_major"]
+            masks_ood = outputs.get("pred_masks_ood_pixel_major", masks)
+        else:
+            masks, masks_ood = outputs["pred_masks"], outputs["pred_masks_ood"]
+        if not all(t.is_cuda for t in (cls, cls_ood, masks, masks_ood)):
+            raise RuntimeError("SetCriterion.loss_ood runs on an MI355X only (CUDA tensors); there is no CPU path")
+        dev = cls.device
+        size = tuple(int(v) for v in targets[0]["ood_mask"].shape[-2:])
+        sem = [t["sem_seg"] for t in targets]
+        if all(isinstance(t, torch.Tensor) for t in sem):
+            target = torch.stack([t.to(dev) for t in sem]).to(torch.int64)          # stack: a new tensor even where nothing converts
+        else:
+            sem = [t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in sem]
+            target = torch.from_numpy(np.stack(sem)).to(dev).to(torch.int64)       # np.stack and the upload: a new tensor
+        crop = tuple(int(v) for v in target.shape[-2:])
+        Q = cls.shape[1]
+        logits = class_mix_upsample(cls, masks, size, crop, "logits", pixel_major=pixel_major, Q=Q)
+        score = class_mix_upsample(cls_ood, masks_ood, size, crop, "neg_max", pixel_major=pixel_major, Q=Q)
+        return {"loss_ood": self.extra_loss(logits, score, target)}
 
     def forward(self, outputs, targets, *, num_masks=None, point_candidates=None, random_points=None, matcher_points=None):
         """The loss computation (criterion.py:432-469). outputs: {"pred_logits" [B,Q,C+1], "pred_masks" [B,Q,h,w] (or
         "pred_masks_pixel_major" [B,h,w,ldq]), "aux_outputs": [the same per earlier step]}; targets: per image {"labels" [T_b],
         "masks" [T_b,H,W]}. Returns {loss_ce, loss_mask, loss_dice} (or the four keys of loss_masks_aug), then `<key>_<i>` for
         aux_outputs[i] when deep_supervision is set: 0-d float32 device tensors attached to autograd, weight_dict NOT applied.
+        With "ood" in losses every step also needs "pred_logits_ood" / "pred_masks_ood" and every target "ood_mask" / "sem_seg"
+        (see loss_ood), and "loss_ood" / "loss_ood_<i>" take their place in the order of `losses`.
         num_masks: overrides max(sum T_b, 1). point_candidates [S, rows that select, K, 2], random_points [S * sum T, Pr, 2],
         matcher_points [S,B,P,2]: inject the random numbers (see kernels.m2f_point_select / HungarianMatcher.match_steps)."""
         self._check_losses()
@@ -146,6 +238,7 @@ class SetCriterion(nn.Module):
         plan.weight = self.empty_weight.to(device=dev, dtype=torch.float32)
         plan.num_points, plan.pixel_major, plan.Q, plan.S = P, pixel_major, Q, S
         plan.want_masks = "masks" in self.losses
+        want_labels = "labels" in self.losses
         mode, n_cand, n_keep = self.selection()
         if self.mask_loss_with_pixel_selection:
             plan.split = sum(counts[:B // 2])                   # criterion.py:255: images b < B/2 are "original", the rest "aug"
@@ -170,13 +263,17 @@ class SetCriterion(nn.Module):
                                                  random_points, n_keep, P, mode=mode, sel_start=sel_start, pixel_major=pixel_major, Q=Q)
         self.last_points, self.last_match = (plan.points, match) if self.keep_tables else (None, None)
 
-        table = _CriterionFunction.apply(plan, *masks, *logits)
-        cols = [j for j, key in enumerate(keys) if ("labels" in self.losses and j == 0) or (plan.want_masks and j > 0)]
-        order = [j for loss in self.losses for j in cols if (j == 0) == (loss == "labels")]
+        table = _CriterionFunction.apply(plan, *masks, *logits) if (want_labels or plan.want_masks) else None
         losses = {}
         for s in range(S):
-            for j in order:
-                losses[keys[j] if s == 0 else f"{keys[j]}_{s - 1}"] = table[s, j]
+            suffix = "" if s == 0 else f"_{s - 1}"
+            for loss in self.losses:                            # criterion.py:455-467: per step, the losses in the order of self.losses
+                if loss == "ood":
+                    losses["loss_ood" + suffix] = self.loss_ood(steps[s], targets)["loss_ood"]
+                    continue
+                for j, key in enumerate(keys):
+                    if (j == 0) == (loss == "labels"):
+                        losses[key + suffix] = table[s, j]
         return losses
 
     def set_extra_loss(self, extra_loss):

@@ -10,24 +10,14 @@
 // probabilities in LDS, then every thread interpolates, applies the sigmoid and mixes the classes for 4 output
 // pixels. HBM traffic: the low-resolution logits once + 4 B per output pixel.
 #include "mss_common.h"
+#include "mss_bilinear.h"
 #include "../../include/mss_hip.h"
 
 namespace {
 
 constexpr int TX = 64, NT = 256, CP = 20, PPT = 4;   // tile width, threads, padded classes, pixels per thread
 
-struct SrcCoord { int i0, i1; float l; };
-// F.interpolate(mode="bilinear", align_corners=False): src = (dst + 0.5) * in/out - 0.5, clamped at 0
-__device__ __forceinline__ SrcCoord src_coord(int dst, float scale, int in_size) {
-  float s = ((float)dst + 0.5f) * scale - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  SrcCoord c;
-  c.i0 = (int)s;
-  if (c.i0 > in_size - 1) c.i0 = in_size - 1;
-  c.i1 = c.i0 + (c.i0 < in_size - 1 ? 1 : 0);
-  c.l = s - (float)c.i0;
-  return c;
-}
+// SrcCoord / src_coord (align_corners=False) live in mss_bilinear.h
 
 __global__ __launch_bounds__(NT) void m2f_fused_score_kernel(const float* __restrict__ cls, const float* __restrict__ logit,
                                                              int Q, int C, int hm, int wm, int ldq, int H, int W, int TY,

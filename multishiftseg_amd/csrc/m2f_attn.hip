@@ -13,6 +13,7 @@
 //   * the key range is split into chunks so that 8 heads x 2 attentions x B fill the chip; a chunk leaves (numerator, maximum,
 //     denominator) in a workspace and m2f_attn_merge_kernel folds the chunks in fixed order -- no float atomics, bit-reproducible.
 #include "mss_common.h"
+#include "mss_bilinear.h"
 #include "../../include/mss_hip.h"
 
 namespace {
@@ -22,18 +23,7 @@ constexpr int NH = 8;         // heads
 constexpr int KB = 8;         // keys per online-softmax step (one rescale of the accumulators per KB keys)
 constexpr int WSROWS = HD + 2;  // workspace rows of one (chunk, head): 32 numerators, maximum (log2 domain), denominator
 
-struct SrcCoord { int i0, i1; float l; };
-// F.interpolate(mode="bilinear", align_corners=False): src = max(0, (dst + 0.5) * in/out - 0.5) (as csrc/m2f.hip)
-__device__ __forceinline__ SrcCoord src_coord(int dst, float scale, int in_size) {
-  float s = ((float)dst + 0.5f) * scale - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  SrcCoord c;
-  c.i0 = (int)s;
-  if (c.i0 > in_size - 1) c.i0 = in_size - 1;
-  c.i1 = c.i0 + (c.i0 < in_size - 1 ? 1 : 0);
-  c.l = s - (float)c.i0;
-  return c;
-}
+// SrcCoord / src_coord: F.interpolate(mode="bilinear", align_corners=False), mss_bilinear.h
 
 // bits [B][2][h*w][W] (W = ceil(Q/32) words; bit q of a row set = query q may NOT attend to that key), allowed [B][2][W]
 // (zeroed before the launch; bit q set = query q has at least one allowed key). A wave takes one key at a time: lane = query.

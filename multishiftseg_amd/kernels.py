@@ -1505,6 +1505,127 @@ def m2f_label_loss_backward(class_logits, tclass, bad, weight, wsum, gloss):
     return grads
 
 
+# ---- SetCriterion.loss_ood, RCL branch: the class mix, forward and backward (csrc/m2f_mix.hip) ----------------------------------------
+_MIX_MODES = {"logits": 0, "neg_max": 1}
+MIX_LOGIT_CHANNELS = 19             # criterion.py:166: logits[:, :19]
+MIX_MAX_QUERIES, MIX_MAX_CLASSES = 128, 32
+
+
+def _mix_inputs(name, class_logits, mask_logits, pixel_major, Q):
+    """Class logits [B,Q,C+1] and mask logits (NCHW [B,Q,h,w], or pixel-major [B,h,w,ldq]) -> (both contiguous, the (image,
+    query, pixel) strides, B, Q, C, h, w)."""
+    for t in (class_logits, mask_logits):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    cls, x = class_logits.contiguous(), mask_logits.contiguous()
+    if cls.dim() != 3 or x.dim() != 4 or x.shape[0] != cls.shape[0]:
+        raise ValueError(f"{name}: class logits {tuple(cls.shape)} / mask logits {tuple(x.shape)}")
+    B, Qc, C1 = cls.shape
+    if pixel_major:
+        _, h, w, ldq = x.shape
+        strides = (h * w * ldq, 1, ldq)
+        Q = Qc if Q is None else int(Q)
+        if ldq % 4:
+            raise ValueError(f"{name}: the pitch {ldq} of pixel-major mask logits is no multiple of 4")
+    else:
+        _, ldq, h, w = x.shape
+        strides = (h * w * ldq, h * w, 1)
+        Q = ldq if Q is None else int(Q)
+        if Q != ldq:
+            raise ValueError(f"{name}: Q {Q} does not fit NCHW mask logits {tuple(x.shape)}")
+    C = C1 - 1
+    if Q != Qc or Q > ldq or not 1 <= Q <= MIX_MAX_QUERIES or not 1 <= C <= MIX_MAX_CLASSES or h < 1 or w < 1:
+        raise ValueError(f"{name}: {Qc} queries x {C} classes of class logits, Q {Q} of mask logits {tuple(x.shape)} "
+                         f"(Q <= {MIX_MAX_QUERIES}, 1 <= C <= {MIX_MAX_CLASSES})")
+    return cls, x, strides, B, Q, C, h, w
+
+
+def _mix_sizes(name, mix, size, crop):
+    if not mix.is_cuda or mix.dtype != torch.float32:
+        raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    if mix.dim() != 4:
+        raise ValueError(f"{name}: mix {tuple(mix.shape)} is not [B,C,h,w]")
+    (H, W), (Ht, Wt) = (int(v) for v in size), (int(v) for v in (size if crop is None else crop))
+    if not (1 <= Ht <= H and 1 <= Wt <= W):
+        raise ValueError(f"{name}: crop {(Ht, Wt)} does not lie inside size {(H, W)}")
+    return H, W, Ht, Wt
+
+
+def m2f_class_mix(class_logits, mask_logits, pixel_major=False, Q=None):
+    """The class mix of loss_ood at the low resolution (criterion.py:133-138): -> (mix [B,C,h,w] = einsum("bqc,bqhw->bchw",
+    softmax(class_logits, -1)[..., :-1], sigmoid(mask_logits)), prob [B,Q,C] = that softmax, which m2f_class_mix_backward reuses).
+    class_logits [B,Q,C+1]; mask_logits NCHW [B,Q,h,w], or with pixel_major [B,h,w,ldq] (ldq % 4 == 0; the columns Q..ldq-1 are
+    never read). Q <= 128, 1 <= C <= 32. The queries are summed in index order: both layouts give the same bits."""
+    name = "m2f_class_mix"
+    cls, x, strides, B, Q, C, h, w = _mix_inputs(name, class_logits, mask_logits, pixel_major, Q)
+    prob = torch.empty((B, Q, C), device=x.device, dtype=torch.float32)
+    mix = torch.empty((B, C, h, w), device=x.device, dtype=torch.float32)
+    call("mss_m2f_mix_forward_f32", ptr(cls), ptr(x), strides[0], strides[1], strides[2], B, Q, C, h, w, ptr(prob), ptr(mix))
+    return mix, prob
+
+
+def m2f_mix_upsample(mix, size, crop=None, mode="logits"):
+    """F.interpolate(mix, size=(H, W), mode="bilinear", align_corners=False)[:, :, :Ht, :Wt] (criterion.py:166-168, :177-179) without
+    the uncropped tensor. mode "logits": the first min(C, 19) channels -> [B,Cl,Ht,Wt] contiguous, what RelContrastiveLoss takes;
+    "neg_max": -max over all C channels (:181) -> [B,Ht,Wt]; the C full-size channels are never stored. The scale is h / H."""
+    name = "m2f_mix_upsample"
+    H, W, Ht, Wt = _mix_sizes(name, mix, size, crop)
+    if mode not in _MIX_MODES:
+        raise ValueError(f"{name}: mode {mode!r} is not one of {sorted(_MIX_MODES)}")
+    mix = mix.contiguous()
+    B, C, h, w = mix.shape
+    shape = (B, Ht, Wt) if mode == "neg_max" else (B, min(C, MIX_LOGIT_CHANNELS), Ht, Wt)
+    out = torch.empty(shape, device=mix.device, dtype=torch.float32)
+    call("mss_m2f_mix_upsample_f32", ptr(mix), B, C, h, w, H, W, Ht, Wt, _MIX_MODES[mode], ptr(out))
+    return out
+
+
+def m2f_mix_upsample_backward(mix, size, crop=None, dlogits=None, dscore=None):
+    """d / d mix of m2f_mix_upsample: dlogits [B,Cl,Ht,Wt] is the upstream gradient of its "logits" output, dscore [B,Ht,Wt] that of
+    "neg_max"; either or both. -> dmix [B,C,h,w], written whole: a low-resolution pixel sums, rows then columns ascending, over the
+    output pixels of the crop whose taps contain it. For dscore the C interpolated values are recomputed per output pixel and
+    -dscore goes to the largest; among equal values the lowest class index takes it (torch.max leaves that unspecified)."""
+    name = "m2f_mix_upsample_backward"
+    H, W, Ht, Wt = _mix_sizes(name, mix, size, crop)
+    mix = mix.contiguous()
+    B, C, h, w = mix.shape
+    Cl = min(C, MIX_LOGIT_CHANNELS)
+    for t, shape in ((dlogits, (B, Cl, Ht, Wt)), (dscore, (B, Ht, Wt))):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: an upstream gradient {tuple(t.shape)} where {shape} belongs")
+    if dlogits is None and dscore is None:
+        raise ValueError(f"{name}: neither dlogits nor dscore")
+    dmix = torch.empty_like(mix)
+    call("mss_m2f_mix_upsample_backward_f32", ptr(dlogits.contiguous() if dlogits is not None else None),
+         ptr(dscore.contiguous() if dscore is not None else None), ptr(mix), B, C, h, w, H, W, Ht, Wt, ptr(dmix))
+    return dmix
+
+
+def m2f_class_mix_backward(dmix, prob, class_logits, mask_logits, pixel_major=False, Q=None):
+    """d / d (mask_logits, class_logits) of m2f_class_mix from dmix [B,C,h,w]; prob is its second result. -> (dmasks in the layout
+    of mask_logits, every pad column Q..ldq-1 of a pixel-major layout 0; dcls [B,Q,C+1]). dmasks = sigmoid'(x) sum_c prob dmix;
+    dcls = the softmax backward, with the dropped column, of dP[b,q,c] = sum_p dmix[b,c,p] sigmoid(x[b,q,p]): per-workgroup partial
+    sums folded in index order, no float atomics -- two runs give the same bits, and so do the two layouts."""
+    name = "m2f_class_mix_backward"
+    cls, x, strides, B, Q, C, h, w = _mix_inputs(name, class_logits, mask_logits, pixel_major, Q)
+    for t in (dmix, prob):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    if tuple(dmix.shape) != (B, C, h, w) or tuple(prob.shape) != (B, Q, C):
+        raise ValueError(f"{name}: dmix {tuple(dmix.shape)} / prob {tuple(prob.shape)} for B {B}, Q {Q}, C {C}, {h} x {w}")
+    chunks = _lib.value("mss_m2f_mix_backward_chunks", h * w)
+    partial = torch.empty((B, chunks, Q, C), device=x.device, dtype=torch.float64)
+    dmasks = torch.empty_like(x)
+    dcls = torch.empty((B, Q, C + 1), device=x.device, dtype=torch.float32)
+    call("mss_m2f_mix_backward_f32", ptr(dmix.contiguous()), ptr(prob.contiguous()), ptr(cls), ptr(x), strides[0], strides[1], strides[2],
+         B, Q, C, h, w, ptr(partial), ptr(dmasks), ptr(dcls))
+    return dmasks, dcls
+
+
 # ---- Mask2Former pixel-decoder glue (csrc/norm.hip) --------------------------------------------------------------------
 def groupnorm(x, gn, relu=False, out=None, out_sample_stride=None, out_ld=None, want_stat=False):
     """nn.GroupNorm `gn` on an Act (NHWC). `out`: optional float tensor to write into (e.g. the encoder's token buffer
