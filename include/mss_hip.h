@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 15     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 16     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -39,7 +39,9 @@ extern "C" {
                                   in version 5 is gone;
                                   13 (additive): mss_m2f_match_workspace_bytes, mss_m2f_match_cost_f32, mss_m2f_match_assign_f32 (Hungarian matching);
                                   14 (additive): the six mss_m2f_loss_* entry points (SetCriterion: class and sampled-mask losses);
-                                  15 (additive): the five mss_m2f_mix_* entry points (SetCriterion.loss_ood: the class mix, forward and backward) */
+                                  15 (additive): the five mss_m2f_mix_* entry points (SetCriterion.loss_ood: the class mix, forward and backward);
+                                  16 (additive): mss_m2f_masked_attention_lse_f32, mss_m2f_attn_bwd_workspace_bytes, mss_m2f_masked_attention_bwd_f32
+                                  (the masked attention's training forward and backward) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -519,6 +521,29 @@ long long mss_m2f_attn_workspace_bytes(int B, int Q, int A, int chunks);
 int mss_m2f_masked_attention_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const uint32_t* bits,
                                  const uint32_t* allowed, int B, int Q, int NK, int A, float scale, int chunks, float* ws,
                                  float* out, int ldo, void* stream);
+
+/* The masked attention for training.
+ *
+ * mss_m2f_masked_attention_lse_f32: mss_m2f_masked_attention_f32 (the same kernels: `out` is bit-identical for the same arguments and
+ * chunk count) that also writes lse [B][A][8][Q], per (image, attention, head, query) the log-sum-exp of the scaled, masked scores
+ * in the LOG2 domain: lse = log2(sum over the allowed keys of 2^(scale * log2(e) * <q, k>)) = natural lse * log2(e).
+ *
+ * mss_m2f_masked_attention_bwd_f32: with P = 2^(scale * log2(e) * <q, k> - lse) (0 where masked) and D = <dout, out> per query and head,
+ *   dv = P^T dout,  dS = P o (dout v^T - D),  dq = scale * dS k,  dk = scale * dS^T q.
+ * q / k / v / bits / allowed / out / lse as given to / returned by the forward, dout [B*Q, lddo]; row strides >= A*256, multiples of 4,
+ * 16-byte aligned bases. dq [B*Q, A*256], dk / dv [B*NK, A*256] dense; any of the three may be NULL (not computed). Every element of a
+ * non-NULL output is assigned exactly once (nothing needs zeroing); a key no query may attend to gets exact zeros. `chunks` cuts the
+ * key range of the dq sum as in the forward (it need not be the forward's count); ws >= mss_m2f_attn_bwd_workspace_bytes(B, Q, A,
+ * chunks) bytes (host arithmetic; 0 = unsupported shape), always needed (it holds D), contents irrelevant on entry. No float atomics:
+ * bit-reproducible for a given chunk count. Q <= 128, A <= 16. */
+int mss_m2f_masked_attention_lse_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const uint32_t* bits,
+                                     const uint32_t* allowed, int B, int Q, int NK, int A, float scale, int chunks, float* ws,
+                                     float* out, int ldo, float* lse, void* stream);
+long long mss_m2f_attn_bwd_workspace_bytes(int B, int Q, int A, int chunks);
+int mss_m2f_masked_attention_bwd_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const uint32_t* bits,
+                                     const uint32_t* allowed, const float* out, int ldo, const float* lse, const float* dout, int lddo,
+                                     int B, int Q, int NK, int A, float scale, int chunks, float* ws, float* dq, float* dk, float* dv,
+                                     void* stream);
 
 /* Pixel-level OOD metrics on the device (csrc/metric.hip): exact AUROC / average precision / FPR at `recall_level`
  * over all pixels with label id_out (positives) and id_in (negatives). Replaces eval_ood_measure, get_measures and

@@ -15,7 +15,10 @@ def __getattr__(name):
     if name == "class_mix_upsample":
         from .criterion import class_mix_upsample
         return class_mix_upsample
+    if name == "masked_attention":
+        from .kernels import masked_attention
+        return masked_attention
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample"]
+__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention"]

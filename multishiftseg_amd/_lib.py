@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 15         # include/mss_hip.h
+MSS_ABI_VERSION = 16         # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -159,6 +159,9 @@ SIGNATURES = {
     "mss_m2f_attn_mask_bits_f32": [P, I, I, I, I, I, I, I, P, P],
     "mss_m2f_attn_workspace_bytes": [I, I, I, I],
     "mss_m2f_masked_attention_f32": [P, I, P, I, P, I, P, P, I, I, I, I, F, I, P, P, I],
+    "mss_m2f_masked_attention_lse_f32": [P, I, P, I, P, I, P, P, I, I, I, I, F, I, P, P, I, P],
+    "mss_m2f_attn_bwd_workspace_bytes": [I, I, I, I],
+    "mss_m2f_masked_attention_bwd_f32": [P, I, P, I, P, I, P, P, P, I, P, P, I, I, I, I, I, F, I, P, P, P, P],
     "mss_m2f_match_workspace_bytes": [I, I, I, I, I],
     "mss_m2f_match_cost_f32": [P, L, L, L, I, I, P, P, P, P, I, I, I, P, I, I, I, I, I, I, F, F, F, P, P, P, P, P],
     "mss_m2f_match_assign_f32": [P, P, I, I, I, I, P, P, P],
@@ -203,12 +206,12 @@ SIGNATURES = {
     "mss_peak_scatter_f32": [P, P, L, I, I, L, P],
 }
 # entry points that return a plain value rather than a status code
-_VALUE_RETURNING = {"mss_chan_compact_wanted", "mss_gemm_split_last_mfma", "mss_conv2d_wgrad_route", "mss_gemm_split_weights_bytes", "mss_abi_version", "mss_env_reset", "mss_env_generation", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_m2f_mix_backward_chunks", "mss_conv2d_kpad", "mss_conv2d_forward_route", "mss_rcl_num_compact_blocks", "mss_wino_num_tiles",
+_VALUE_RETURNING = {"mss_chan_compact_wanted", "mss_gemm_split_last_mfma", "mss_conv2d_wgrad_route", "mss_gemm_split_weights_bytes", "mss_abi_version", "mss_env_reset", "mss_env_generation", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_attn_bwd_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_m2f_mix_backward_chunks", "mss_conv2d_kpad", "mss_conv2d_forward_route", "mss_rcl_num_compact_blocks", "mss_wino_num_tiles",
                     "mss_oodm_sort_temp_bytes", "mss_oodm_compact_lanes_cap", "mss_oodm_rank_blocks", "mss_wino_output_stats_parts",
                     "mss_conv2d_wgrad_workspace_bytes", "mss_col_reduce_accum_doubles", "mss_colsum_workspace_floats",
                     "mss_add_layernorm_bwd_workspace_floats", "mss_groupnorm_workspace_floats",
                     "mss_groupnorm_stat_offset", "mss_groupnorm_bwd_workspace_floats"}
-_RETURNS_LONGLONG = {"mss_oodm_compact_lanes_cap", "mss_gemm_split_weights_bytes", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_wino_num_tiles", "mss_oodm_sort_temp_bytes", "mss_conv2d_wgrad_workspace_bytes",
+_RETURNS_LONGLONG = {"mss_oodm_compact_lanes_cap", "mss_gemm_split_weights_bytes", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_attn_bwd_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_wino_num_tiles", "mss_oodm_sort_temp_bytes", "mss_conv2d_wgrad_workspace_bytes",
                      "mss_col_reduce_accum_doubles", "mss_colsum_workspace_floats",
                      "mss_add_layernorm_bwd_workspace_floats", "mss_groupnorm_workspace_floats",
                      "mss_groupnorm_stat_offset", "mss_groupnorm_bwd_workspace_floats"}

@@ -1198,6 +1198,171 @@ def m2f_masked_attention(q, k, v, B, Q, NK, A=1, bits=None, allowed=None, chunks
     return out
 
 
+def _attn_check(name, q, k, v, B, Q, NK, A, bits, allowed):
+    for t in (q, k, v):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise RuntimeError(f"{name} takes row-major 2-d float32 CUDA tensors (there is no CPU path)")
+    if q.shape[0] != B * Q or k.shape[0] != B * NK or v.shape[0] != B * NK:
+        raise ValueError(f"rows {q.shape[0]} / {k.shape[0]} / {v.shape[0]} do not match B {B}, Q {Q}, NK {NK}")
+    if (bits is None) != (allowed is None):
+        raise ValueError("bits and allowed come together")
+    if bits is not None:
+        W = (Q + 31) // 32
+        if tuple(bits.shape) != (B, A, NK, W) or tuple(allowed.shape) != (B, A, W) or not bits.is_contiguous() or not allowed.is_contiguous() \
+                or bits.dtype != torch.int32 or allowed.dtype != torch.int32:
+            raise ValueError(f"bits {tuple(bits.shape)} / allowed {tuple(allowed.shape)} must be contiguous int32 [{B}, {A}, {NK}, {W}] / [{B}, {A}, {W}]")
+
+
+def m2f_masked_attention_lse(q, k, v, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, out=None, scale=None, ws=None):
+    """m2f_masked_attention for training: the same kernels (`out` has the same bits for the same arguments and chunk count) ->
+    (out [B*Q, A*256], lse [B, A, 8, Q]); lse is the log-sum-exp of the scaled, masked scores in the log2 domain
+    (include/mss_hip.h), which m2f_masked_attention_backward takes."""
+    _attn_check("m2f_masked_attention_lse", q, k, v, B, Q, NK, A, bits, allowed)
+    if chunks is None:
+        chunks = m2f_attn_chunks(B, A, NK)
+    if out is None:
+        out = torch.empty((B * Q, A * 256), device=q.device, dtype=torch.float32)
+    lse = torch.empty((B, A, 8, Q), device=q.device, dtype=torch.float32)
+    if ws is None and chunks > 1:
+        ws = torch.empty(_lib.value("mss_m2f_attn_workspace_bytes", B, Q, A, chunks) // 4, device=q.device, dtype=torch.float32)
+    call("mss_m2f_masked_attention_lse_f32", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(bits), ptr(allowed),
+         B, Q, NK, A, float(scale if scale is not None else 32 ** -0.5), chunks, ptr(ws), ptr(out), out.stride(0), ptr(lse))
+    return out, lse
+
+
+def m2f_masked_attention_backward(q, k, v, out, lse, dout, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, scale=None, ws=None,
+                                  need=(True, True, True), grads=None):
+    """Gradients of m2f_masked_attention_lse -> (dq [B*Q, A*256], dk, dv [B*NK, A*256]); an entry of `need` that is False is not
+    computed (None). out / lse: what the forward returned; dout: the cotangent of out. grads: optional (dq, dk, dv) buffers to
+    write into; ws: the float32 workspace (mss_m2f_attn_bwd_workspace_bytes). Neither needs zeroing: every element is assigned.
+    No float atomics: the same bits every run for a given chunk count."""
+    _attn_check("m2f_masked_attention_backward", q, k, v, B, Q, NK, A, bits, allowed)
+    for t in (out, dout):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or tuple(t.shape) != (B * Q, A * 256):
+            raise RuntimeError("m2f_masked_attention_backward takes row-major 2-d float32 CUDA tensors (there is no CPU path)")
+    if tuple(lse.shape) != (B, A, 8, Q) or not lse.is_contiguous() or lse.dtype != torch.float32:
+        raise ValueError(f"lse {tuple(lse.shape)} must be contiguous float32 [{B}, {A}, 8, {Q}]")
+    if chunks is None:
+        chunks = m2f_attn_chunks(B, A, NK)
+    shapes = ((B * Q, A * 256), (B * NK, A * 256), (B * NK, A * 256))
+    res = []
+    for i in range(3):
+        g = None
+        if need[i]:
+            g = grads[i] if grads is not None and grads[i] is not None else torch.empty(shapes[i], device=q.device, dtype=torch.float32)
+            if tuple(g.shape) != shapes[i] or not g.is_contiguous() or g.dtype != torch.float32:
+                raise ValueError(f"gradient buffer {i} must be contiguous float32 {shapes[i]}")
+        res.append(g)
+    if ws is None:
+        ws = torch.empty(_lib.value("mss_m2f_attn_bwd_workspace_bytes", B, Q, A, chunks) // 4, device=q.device, dtype=torch.float32)
+    call("mss_m2f_masked_attention_bwd_f32", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(bits), ptr(allowed),
+         ptr(out), out.stride(0), ptr(lse), ptr(dout), dout.stride(0), B, Q, NK, A, float(scale if scale is not None else 32 ** -0.5),
+         chunks, ptr(ws), ptr(res[0]), ptr(res[1]), ptr(res[2]))
+    return tuple(res)
+
+
+class _MaskedAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, B, Q, NK, A, bits, allowed, chunks, scale):
+        out, lse = m2f_masked_attention_lse(q, k, v, B, Q, NK, A=A, bits=bits, allowed=allowed, chunks=chunks, scale=scale)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.masks = (bits, allowed)
+        ctx.geom = (B, Q, NK, A, chunks, scale)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        q, k, v, out, lse = ctx.saved_tensors
+        B, Q, NK, A, chunks, scale = ctx.geom
+        bits, allowed = ctx.masks
+        dq, dk, dv = m2f_masked_attention_backward(q, k, v, out, lse, gout.contiguous(), B, Q, NK, A=A, bits=bits, allowed=allowed,
+                                                   chunks=chunks, scale=scale, need=ctx.needs_input_grad[:3])
+        return (dq, dk, dv) + (None,) * 8
+
+
+def masked_attention(q, k, v, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, scale=None):
+    """Differentiable m2f_masked_attention: softmax(scale q k^T + mask) v for 8 heads of 32 channels and A attentions side by
+    side, forward and backward on csrc/m2f_attn.hip. Gradients go to q, k and v (each computed only where asked for); bits /
+    allowed are not differentiated. q / k / v may be column slices of wider row-major tensors."""
+    return _MaskedAttentionFn.apply(q, k, v, B, Q, NK, A, bits, allowed, chunks, scale)
+
+
+class _MaskLogitsFn(torch.autograd.Function):
+    """logits[b] = feat[b] mask_embed[b]^T, pixel-major (m2f_mask_logits_act); backward: d mask_embed[b] = dlogits[b]^T feat[b] on the
+    weight-gradient kernel, d feat[b] = dlogits[b] mask_embed[b] on the forward GEMM. The cotangent's padded query columns
+    Q .. ldq-1 are dropped before either product."""
+
+    @staticmethod
+    def forward(ctx, mask_embed, feat, C, ldq):
+        x = Act(feat, C=C)
+        out = m2f_mask_logits_act(mask_embed, x, ldq)
+        ctx.save_for_backward(mask_embed, feat)
+        ctx.C = C
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        me, feat = ctx.saved_tensors
+        B, Q, C = me.shape
+        _, h, w, ld = feat.shape
+        Qp = max(32, _round_up(Q, 16))
+        dl = torch.zeros((B, h, w, Qp), device=g.device, dtype=torch.float32)
+        dl[..., :Q] = g[..., :Q]
+        dme = dfeat = None
+        if ctx.needs_input_grad[0]:
+            dme = torch.empty((B, Q, C), device=g.device, dtype=torch.float32)
+            for b in range(B):
+                gw = conv2d_wgrad(Act(feat[b:b + 1], C=C), Act(dl[b:b + 1]), Qp, C, 1, 1)
+                dme[b] = gw.view(Qp, C)[:Q]
+        if ctx.needs_input_grad[1]:
+            dfeat = torch.empty_like(feat) if ld == C else torch.zeros_like(feat)
+            mt = torch.zeros((B, C, Qp), device=g.device, dtype=torch.float32)
+            mt[:, :, :Q] = me.detach().transpose(1, 2)
+            for b in range(B):
+                conv2d(Act(dl[b:b + 1]), pack_weight(mt[b].view(C, Qp, 1, 1)), out=Act(dfeat[b:b + 1], C=C))
+        return dme, dfeat, None, None
+
+
+def mask_logits(mask_embed, feat, ldq):
+    """Differentiable m2f_mask_logits_act: mask_embed [B, Q, C] x feat (an Act [B, h, w, C] over a tensor that may require grad) ->
+    pixel-major logits [B, h, w, ldq], with the forward's bits. Both gradients run on the MFMA GEMM / weight-gradient kernels."""
+    if not mask_embed.is_cuda or not feat.buf.is_cuda:
+        raise RuntimeError("mask_logits runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    if feat.c0 != 0:
+        raise ValueError("mask_logits takes an Act that starts at channel 0 of its buffer")
+    return _MaskLogitsFn.apply(mask_embed, feat.buf, feat.C, ldq)
+
+
+class _NchwToRowsFn(torch.autograd.Function):
+    """nchw_to_act as an autograd node -> the Act's buffer [N, H, W, Cp]; backward: nhwc_to_nchw of the first C channels."""
+
+    @staticmethod
+    def forward(ctx, t):
+        ctx.c = t.shape[1]
+        return nchw_to_act(t).buf
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return nhwc_to_nchw(Act(g.contiguous(), C=ctx.c))
+
+
+class _RowsToNchwFn(torch.autograd.Function):
+    """nhwc_to_nchw of the first C channels of [N, H, W, ld] as an autograd node; backward: the zero-padded inverse."""
+
+    @staticmethod
+    def forward(ctx, buf, C):
+        ctx.ld = buf.shape[-1]
+        return nhwc_to_nchw(Act(buf, C=C))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return nchw_to_act(g, Cp=ctx.ld).buf, None
+
+
 def m2f_score_fused(class_logits, mask_logits_nhwc, image_size, size=None):
     """Anomaly score from LOW-resolution pixel-major mask logits [B,hm,wm,Q]: bilinear upsample to `image_size`
     (align_corners=False, maskformer_model.py:264-277) + train_m2f.py:387-407, cropped to `size` -> [B,H,W]."""

@@ -1,4 +1,4 @@
-"""Mask2Former's GMA transformer decoder, forward only.
+"""Mask2Former's GMA transformer decoder: forward only by default, trainable on request.
 
 Host-side mirror of ``MultiScaleMaskedTransformerDecoder_GMA``
 (lib/network/mask2former/modeling/transformer_decoder/mask2former_transformer_decoder.py:280-573): same constructor
@@ -20,13 +20,15 @@ What runs (all in libmss_hip.so; tokens are batch-major [B, rows, 256] inside, t
 
 Supported: pre_norm=False, hidden_dim=256, nheads=8, mask_dim a multiple of 16, <= 128 queries, float32 CUDA inputs. Eval and
 "stage 1" training, where only class_embed2 receives a gradient (train_m2f.py, M2F.yaml:9); every other trainable parameter
-under an enabled grad mode raises, as does anything else outside this list. There is no CPU path and no torch fallback.
+under an enabled grad mode raises, as does anything else outside this list. set_trainable() opts in to the differentiable path
+of stage 2 (_forward_train: the same arithmetic on autograd nodes, the attention's backward in csrc/m2f_attn.hip). There is no CPU
+path and no torch fallback.
 """
 import torch
 from torch import nn
 
 from . import kernels as K
-from .linear import _rows, linear
+from .linear import _rows, ffn_relu, linear
 from .msdeformattn_encoder import PositionEmbeddingSine
 
 
@@ -120,6 +122,15 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
         self.class_embed2 = nn.Linear(hidden_dim, num_classes + 1)
         self._stacks = {}
         self._pos_cache = {}
+        self._trainable = False
+
+    def set_trainable(self, flag=True):
+        """Opt in to (or out of) the differentiable path: with the switch on and grad mode enabled, forward() runs on autograd
+        nodes over the same kernels and every parameter the reference's autograd reaches (all but the unused fusion_layer), x[i]
+        and mask_features receive gradients. Off (the default) the module is forward-only apart from class_embed2, as before;
+        under torch.no_grad() the switch makes no difference."""
+        self._trainable = bool(flag)
+        return self
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         version = local_metadata.get("version", None)
@@ -225,6 +236,8 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
             raise ValueError(f"expected {self.num_feature_levels} feature levels, got {len(x)}")
         if not mask_features.is_cuda or not all(t.is_cuda for t in x):
             raise RuntimeError("MultiScaleMaskedTransformerDecoder_GMA (multishiftseg_amd) runs on an MI355X only; there is no CPU path")
+        if self._trainable and torch.is_grad_enabled():
+            return self._forward_train(x, mask_features, fuse_score, return_attn_bits)
         if mask_features.requires_grad or any(t.requires_grad for t in x):
             if torch.is_grad_enabled():
                 raise NotImplementedError("transformer_decoder (multishiftseg_amd): no backward to the inputs (forward only)")
@@ -301,6 +314,86 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
             masks.append(None if last and skip_last_nchw else K.nhwc_to_nchw(K.Act(logits, C=Q)))
         return norms, masks, logits, bits_used
 
+    def _forward_train(self, x, mask_features, fuse_score, return_attn_bits):
+        """The differentiable path (set_trainable): _forward_frozen's arithmetic on autograd nodes -- linear / ffn_relu /
+        add_layernorm, kernels.masked_attention, kernels.mask_logits; the stacked projections are torch.cat of the live parameters,
+        so autograd splits their gradients; the mask bits come from the detached logits. fuse_score stays inference-only here: the
+        anomaly score is computed from detached tensors and the last step's NCHW masks are still materialised."""
+        B = x[0].shape[0]
+        Q, L = self.num_queries, self.num_feature_levels
+        C = self.decoder_norm.normalized_shape[0]
+        ldq = (Q + 3) // 4 * 4
+        sizes, src, kin = [], [], []
+        for i in range(L):
+            h, w = x[i].shape[-2:]
+            sizes.append((h, w))
+            xa = K._NchwToRowsFn.apply(x[i])                                     # [B, h, w, Cp]
+            lvl = self.level_embed.weight[i]
+            proj = self.input_proj[i]
+            if isinstance(proj, nn.Conv2d):
+                wgt = proj.weight.view(proj.out_channels, -1)
+                if xa.shape[-1] != wgt.shape[1]:
+                    wgt = nn.functional.pad(wgt, (0, xa.shape[-1] - wgt.shape[1]))
+                s = linear(xa.view(B, h * w, -1), wgt, proj.bias + lvl)
+            else:
+                if xa.shape[-1] != C:
+                    raise ValueError(f"level {i}: {x[i].shape[1]} channels without an input projection, expected {C}")
+                s = xa.view(B, h * w, C) + lvl
+            src.append(s)
+            kin.append(s + self._position(x[i]))
+        if mask_features.shape[1] != self.mask_embed.layers[-1].out_features:
+            raise ValueError(f"mask_features has {mask_features.shape[1]} channels, mask_embed produces {self.mask_embed.layers[-1].out_features}")
+        feat = K.Act(K._NchwToRowsFn.apply(mask_features), C=mask_features.shape[1])
+        c1, c2 = self.class_embed, self.class_embed2
+        n = c1.out_features
+        pad_w = c1.weight.new_zeros((128 - 2 * n, c1.in_features))
+        cls_w, cls_b = torch.cat((c1.weight, c2.weight, pad_w), 0), torch.cat((c1.bias, c2.bias, pad_w[:, 0]), 0)
+        cls, cls_ood, masks, bits_used = [], [], [], []
+
+        def heads(tgt):
+            dn = K.add_layernorm(tgt, None, self.decoder_norm)
+            y = linear(dn, cls_w, cls_b)
+            cls.append(y[..., :n].contiguous())
+            cls_ood.append(y[..., n:2 * n].contiguous())
+            me = dn
+            for j, lin in enumerate(self.mask_embed.layers):
+                me = linear(me, lin.weight, lin.bias, relu=j < self.mask_embed.num_layers - 1)
+            logits = K.mask_logits(me, feat, ldq)
+            masks.append(K._RowsToNchwFn.apply(logits, Q))
+            return logits
+
+        qpos = self.query_embed.weight.float().unsqueeze(0)
+        tgt = self.query_feat.weight.float().unsqueeze(0).repeat(B, 1, 1)
+        logits = heads(tgt)
+        for i in range(self.num_layers):
+            lv = i % L
+            h, w = sizes[lv]
+            bits, allowed = K.m2f_attn_mask_bits(logits.detach(), Q, (h, w))
+            bits_used.append((bits, allowed))
+            ca = self.transformer_cross_attention_layers[i]
+            fg, bg = ca.multihead_attn_foreground, ca.multihead_attn_background
+
+            def part(j):
+                return (torch.cat((fg.in_proj_weight[j * C:(j + 1) * C], bg.in_proj_weight[j * C:(j + 1) * C]), 0),
+                        torch.cat((fg.in_proj_bias[j * C:(j + 1) * C], bg.in_proj_bias[j * C:(j + 1) * C]), 0))
+            qp = linear(tgt + qpos, *part(0))
+            kp = linear(kin[lv], *part(1))
+            vp = linear(src[lv], *part(2))
+            att = K.masked_attention(qp.view(B * Q, 2 * C), kp.view(B * h * w, 2 * C), vp.view(B * h * w, 2 * C), B, Q, h * w, A=2,
+                                     bits=bits, allowed=allowed)
+            o = linear(att.view(B, Q, 2 * C), torch.cat((fg.out_proj.weight, bg.out_proj.weight), 1), fg.out_proj.bias + bg.out_proj.bias)
+            tgt = K.add_layernorm(tgt, o, ca.norm)
+            sl = self.transformer_self_attention_layers[i]
+            sa = sl.self_attn
+            qk = linear(tgt + qpos, sa.in_proj_weight[:2 * C], sa.in_proj_bias[:2 * C]).view(B * Q, 2 * C)
+            sv = linear(tgt, sa.in_proj_weight[2 * C:], sa.in_proj_bias[2 * C:]).view(B * Q, C)
+            att = K.masked_attention(qk[:, :C], qk[:, C:], sv, B, Q, Q, A=1, chunks=1)
+            tgt = K.add_layernorm(tgt, linear(att.view(B, Q, C), sa.out_proj.weight, sa.out_proj.bias), sl.norm)
+            ffn = self.transformer_ffn_layers[i]
+            tgt = K.add_layernorm(tgt, ffn_relu(tgt, ffn.linear1, ffn.linear2), ffn.norm)
+            logits = heads(tgt)
+        return self._assemble(cls, cls_ood, masks, logits.detach(), bits_used, fuse_score, return_attn_bits)
+
     def _finish(self, state, fuse_score, return_attn_bits):
         norms, masks, last_logits, bits_used = state
         cls, cls_ood = [], []
@@ -308,6 +401,10 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
             c, co = self._class_logits(dn)
             cls.append(c)
             cls_ood.append(co)
+        return self._assemble(cls, cls_ood, masks, last_logits, bits_used, fuse_score, return_attn_bits)
+
+    @staticmethod
+    def _assemble(cls, cls_ood, masks, last_logits, bits_used, fuse_score, return_attn_bits):
         # the reference runs forward_ood_heads after every layer but not on the initial queries: its OOD lists are one short, and
         # _set_aux_loss zips them against the full lists (:502-521, 563-571) -- aux entry j pairs step j with the OOD heads of layer j
         ood_c, ood_m = cls_ood[1:], masks[1:]
