@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 16     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 17     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -41,7 +41,9 @@ extern "C" {
                                   14 (additive): the six mss_m2f_loss_* entry points (SetCriterion: class and sampled-mask losses);
                                   15 (additive): the five mss_m2f_mix_* entry points (SetCriterion.loss_ood: the class mix, forward and backward);
                                   16 (additive): mss_m2f_masked_attention_lse_f32, mss_m2f_attn_bwd_workspace_bytes, mss_m2f_masked_attention_bwd_f32
-                                  (the masked attention's training forward and backward) */
+                                  (the masked attention's training forward and backward);
+                                  17 (additive): mss_adamw_clip_step_f32 and its five host-only queries mss_adamw_chunk_elems, mss_adamw_tensors_per_launch,
+                                  mss_adamw_blocks_per_launch, mss_adamw_scratch_floats, mss_adamw_plan (multi-tensor AdamW with full-model gradient clipping) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -484,6 +486,35 @@ int mss_rcl_finalize_f32(const MssRclArgs* a, const double* counters, const uint
  * derived scalars are rounded to float (torch/optim/adam.py, single-tensor path); step counts from 1. */
 int mss_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr,
                       double beta1, double beta2, double eps, double weight_decay, int step, void* stream);
+
+/* ---- multi-tensor AdamW with full-model gradient clipping (csrc/m2f_optim.hip; Mask2Former stage 2, train_m2f.py:211-299) ----
+ * One call updates a LIST of `count` float32 tensors: clip_grad_norm_(all grads, max_norm) followed by torch.optim.AdamW's
+ * single-tensor arithmetic with per-tensor lr, weight_decay and step count (torch/nn/utils/clip_grad.py, torch/optim/adam.py).
+ * param / grad / exp_avg / exp_avg_sq / numel / lr / weight_decay / step are HOST arrays of `count` entries (device pointers,
+ * element counts, Python's doubles, step counts from 1); they are read during the call only. Pointers may be 4-byte aligned
+ * (a tensor whose four pointers are all 16-byte aligned takes 16-byte accesses). grad is never written: the clipped gradient
+ * exists in registers only (torch scales p.grad in place).
+ * clip != 0: per-chunk sums of squares go to scratch[slot] (scratch_floats >= mss_adamw_scratch_floats(count, numel); every slot
+ * is written before it is read, the buffer needs no initialisation), one workgroup folds them in a fixed order in double and
+ * leaves norm_out[0] = total_norm and norm_out[1] = min((1 / (total_norm + 1e-6)) * max_norm, 1) (torch's reverse division: reciprocal, then product; a NaN stays NaN) on the device;
+ * the host never reads them. clip == 0: no norm launches, coefficient 1, scratch and norm_out may be NULL.
+ * Launches: with L = the launches the list needs (mss_adamw_plan), L + 1 + L with clipping and L without; *launches (host, may
+ * be NULL) receives the number issued. Empty tensors (numel 0) are skipped; an empty list is MSS_OK and launches nothing. */
+int mss_adamw_clip_step_f32(int count, float* const* param, const float* const* grad, float* const* exp_avg,
+                            float* const* exp_avg_sq, const long long* numel, const double* lr, const double* weight_decay,
+                            const int* step, double beta1, double beta2, double eps, int clip, double max_norm, float* scratch,
+                            long long scratch_floats, float* norm_out, int* launches, void* stream);
+/* Host-only queries of the compile-time launch geometry: elements per workgroup (chunk), tensors and workgroups one launch's
+ * kernel-argument table holds, and the scratch floats (= chunks) of a list. */
+int mss_adamw_chunk_elems(void);
+int mss_adamw_tensors_per_launch(void);
+int mss_adamw_blocks_per_launch(void);
+long long mss_adamw_scratch_floats(int count, const long long* numel);
+/* The launch plan the step uses for a list, entry by entry in issue order: workgroup `block` of launch `launch` handles chunk
+ * `chunk` of list entry `tensor` and owns scratch slot `slot`. Returns the number of entries (-1: bad arguments, or more than
+ * 2^31 - 1 chunks); writes the first `capacity` of them when all five arrays are given (pass NULLs to size them). */
+long long mss_adamw_plan(int count, const long long* numel, long long capacity, int* launch, int* block, int* tensor,
+                         long long* chunk, int* slot);
 
 /* Mask2Former anomaly score fused with the mask upsample (csrc/m2f.hip): logit = pixel-major
  * low-resolution mask logits [B, hm, wm, ldq] (queries contiguous; produced by mss_conv2d_forward_f32 in batched 1x1

@@ -1,6 +1,8 @@
 """multishiftseg_amd: the MultiShiftSeg networks on hand-written HIP kernels for the MI355X. Sub-modules are imported on demand
 (`from multishiftseg_amd import kernels`); the names below are the package's module-level mirrors of reference classes."""
 
+_M2F_TRAINER = ("build_m2f_param_groups", "build_m2f_optimizer", "m2f_weight_dict", "weighted_losses", "M2FTrainStep")
+
 
 def __getattr__(name):
     if name == "MultiScaleMaskedTransformerDecoder_GMA":
@@ -18,7 +20,11 @@ def __getattr__(name):
     if name == "masked_attention":
         from .kernels import masked_attention
         return masked_attention
+    if name in _M2F_TRAINER:
+        from . import m2f_trainer
+        return getattr(m2f_trainer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention"]
+__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention",
+           *_M2F_TRAINER]

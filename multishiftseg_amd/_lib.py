@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 16         # include/mss_hip.h
+MSS_ABI_VERSION = 17         # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -143,6 +143,12 @@ SIGNATURES = {
     "mss_rcl_gather_f32": [P, P, U, P, P],
     "mss_rcl_scatter_add_f32": [P, P, U, P, P],
     "mss_adam_step_f32": [P, P, P, P, L, c_double, c_double, c_double, c_double, c_double, I, P],
+    "mss_adamw_clip_step_f32": [I, P, P, P, P, P, P, P, P, c_double, c_double, c_double, I, c_double, P, L, P, P, P],
+    "mss_adamw_chunk_elems": [],
+    "mss_adamw_tensors_per_launch": [],
+    "mss_adamw_blocks_per_launch": [],
+    "mss_adamw_scratch_floats": [I, P],
+    "mss_adamw_plan": [I, P, L, P, P, P, P, P],
     "mss_wino_num_tiles": [I, I, I, I, I],
     "mss_wino_pack_weights_f32": [P, P, I, I, I, I, I, P],
     "mss_wino_pack_split_bf16x3": [P, P, I, I, I, I, P],
@@ -210,11 +216,13 @@ _VALUE_RETURNING = {"mss_chan_compact_wanted", "mss_gemm_split_last_mfma", "mss_
                     "mss_oodm_sort_temp_bytes", "mss_oodm_compact_lanes_cap", "mss_oodm_rank_blocks", "mss_wino_output_stats_parts",
                     "mss_conv2d_wgrad_workspace_bytes", "mss_col_reduce_accum_doubles", "mss_colsum_workspace_floats",
                     "mss_add_layernorm_bwd_workspace_floats", "mss_groupnorm_workspace_floats",
-                    "mss_groupnorm_stat_offset", "mss_groupnorm_bwd_workspace_floats"}
+                    "mss_groupnorm_stat_offset", "mss_groupnorm_bwd_workspace_floats",
+                    "mss_adamw_chunk_elems", "mss_adamw_tensors_per_launch", "mss_adamw_blocks_per_launch", "mss_adamw_scratch_floats",
+                    "mss_adamw_plan"}
 _RETURNS_LONGLONG = {"mss_oodm_compact_lanes_cap", "mss_gemm_split_weights_bytes", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_attn_bwd_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_wino_num_tiles", "mss_oodm_sort_temp_bytes", "mss_conv2d_wgrad_workspace_bytes",
                      "mss_col_reduce_accum_doubles", "mss_colsum_workspace_floats",
                      "mss_add_layernorm_bwd_workspace_floats", "mss_groupnorm_workspace_floats",
-                     "mss_groupnorm_stat_offset", "mss_groupnorm_bwd_workspace_floats"}
+                     "mss_groupnorm_stat_offset", "mss_groupnorm_bwd_workspace_floats", "mss_adamw_scratch_floats", "mss_adamw_plan"}
 
 _lib = None
 
