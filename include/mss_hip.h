@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 17     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 18     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -43,7 +43,9 @@ extern "C" {
                                   16 (additive): mss_m2f_masked_attention_lse_f32, mss_m2f_attn_bwd_workspace_bytes, mss_m2f_masked_attention_bwd_f32
                                   (the masked attention's training forward and backward);
                                   17 (additive): mss_adamw_clip_step_f32 and its five host-only queries mss_adamw_chunk_elems, mss_adamw_tensors_per_launch,
-                                  mss_adamw_blocks_per_launch, mss_adamw_scratch_floats, mss_adamw_plan (multi-tensor AdamW with full-model gradient clipping) */
+                                  mss_adamw_blocks_per_launch, mss_adamw_scratch_floats, mss_adamw_plan (multi-tensor AdamW with full-model gradient clipping);
+                                  18: MssM2fMaps / MssM2fTargets / MssM2fSteps / MssM2fGrads replace the loose mask-map, target-pack and per-step pointer-table
+                                  arguments of mss_m2f_match_cost_f32 and the mss_m2f_loss_* entry points (signatures changed, none added or removed) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -668,26 +670,40 @@ int mss_upsample_bilinear_add_nhwc_f32(const float* top, int ldt, long long top_
  * the reference. */
 int mss_nhwc_to_nchw_f32(const float* x, int ldx, long long x_sample_stride, int N, int HW, int C, float* y, void* stream);
 
+/* ---- what the Mask2Former matcher and criterion share: the mask logits of S prediction steps and the target pack ----
+ * Plain HOST structs that hold DEVICE pointers (as MssOodmBatch). One tensor per prediction step (the last output and the
+ * aux_outputs are separate tensors), at most MSS_M2F_MAX_STEPS; entries >= S are ignored, an entry < S that is NULL is a bad argument. */
+#define MSS_M2F_MAX_STEPS 16
+typedef struct MssM2fSteps { const float* step[MSS_M2F_MAX_STEPS]; } MssM2fSteps;      /* tensors that are read, e.g. class logits [B,Q,C1] contiguous */
+typedef struct MssM2fGrads { float* step[MSS_M2F_MAX_STEPS]; } MssM2fGrads;            /* tensors that are written, in the layout of what they are the gradient of */
+/* Mask logits of B images, all steps of one shape and layout: element (b, q, y, x) of step s at step[s] + b*img_stride + q*query_stride
+ * + (y*w + x)*pixel_stride floats. NCHW [B,Q,h,w]: (Q*h*w, h*w, 1); pixel-major [B,h,w,ldq]: (h*w*ldq, 1, ldq). */
+typedef struct MssM2fMaps {
+  const float* step[MSS_M2F_MAX_STEPS];
+  long long img_stride, query_stride, pixel_stride;
+  int S, B, Q, h, w;
+} MssM2fMaps;
+/* tmask uint8 [total_t,H,W] (0/1), tstart int32 [B+1]: image b owns targets tstart[b] .. tstart[b+1]-1; labels int32 [total_t] (NULL
+ * where the call does not read them). Shared by all steps. tmask (and labels) may be NULL when total_t == 0. */
+typedef struct MssM2fTargets {
+  const uint8_t* tmask; const int* tstart; const int* labels;
+  int total_t, H, W;
+} MssM2fTargets;
+
 /* ---- Hungarian matching of Mask2Former (csrc/m2f_match.hip) ----
  * replaces HungarianMatcher.memory_efficient_forward, lib/network/mask2former/modeling/matcher.py:95-156 (batch_dice_loss :15-30,
  * batch_sigmoid_ce_loss :38-62), called from criterion.py:444,463 once per prediction step. A problem is one (step s, image b):
  * all S*B problems of a train step go through one call = two launches, no float atomics, no host synchronisation.
- *   masks_host / cls_host: HOST arrays of S device pointers (S <= 16), one per prediction step (the last output and the
- *     aux_outputs are separate tensors): mask logits of B images, element (b, q, y, x) at b*img_stride + q*query_stride +
- *     (y*w + x)*pixel_stride floats (NCHW [B,Q,h,w]: h*w*Q, h*w, 1; pixel-major [B,h,w,ldq]: h*w*ldq, 1, ldq); class logits
- *     [B,Q,C1] contiguous, C1 = classes + 1.
- *   tmask uint8 [total_t,H,W] (0/1), labels int32 [total_t], tstart int32 [B+1]: image b owns targets tstart[b] .. tstart[b+1]-1
- *     (T_b <= Q <= 128, T_b <= Tmax <= 128); shared by all steps. points [S,B,P,2] = (x, y) in [0,1), shared by the masks of a problem
+ *   maps: the mask logits (S, B, Q come from it); cls: class logits [B,Q,C1] per step, C1 = classes + 1.
+ *   targets: T_b <= Q <= 128, T_b <= Tmax <= 128; labels are read. points [S,B,P,2] = (x, y) in [0,1), shared by the masks of a problem
  *     (matcher.py:119-132); point_sample = F.grid_sample(2u-1, bilinear, align_corners=False, zeros): pixel coordinate u*n - 0.5.
  *   cost [S,B,Q,Tmax] fp32 = w_mask cost_mask + w_class cost_class + w_dice cost_dice (matcher.py:144-148), columns >= T_b
  *     written as 0. ws: mss_m2f_match_workspace_bytes bytes of float scratch = 4 * S*B * NC * (2*Q*TP + 2*Q + TP) with
  *     TP = Tmax rounded up to 16 and NC = min(16, ceil(P / 64)) point chunks, added in index order in float64 (bit-reproducible).
  *   match / status (both or neither; NULL = cost only): the assignment is solved in the same second launch. */
 long long mss_m2f_match_workspace_bytes(int S, int B, int Q, int Tmax, int P);
-int mss_m2f_match_cost_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
-                           int h, int w, const float* const* cls_host, const uint8_t* tmask, const int* tstart, const int* labels,
-                           int total_t, int H, int W, const float* points, int S, int B, int Q, int C1, int P, int Tmax,
-                           float w_class, float w_mask, float w_dice, float* ws, float* cost, int* match, int* status, void* stream);
+int mss_m2f_match_cost_f32(const MssM2fMaps* maps, const MssM2fSteps* cls, const MssM2fTargets* targets, const float* points, int C1, int P,
+                           int Tmax, float w_class, float w_mask, float w_dice, float* ws, float* cost, int* match, int* status, void* stream);
 /* linear_sum_assignment (matcher.py:151) of cost [S,B,Q,Tmax] fp32, tcount int32 [B] targets per image: one wave per problem,
  * shortest augmenting paths (Crouse 2016, scipy's algorithm) in float64, every loop bounded by T_b or Q. match [S,B,Tmax] int32 =
  * the query of target m (-1 in the padding); status [S,B] int32: 0 solved, 1 infeasible / NaN / -inf cost / bad count (scipy's
@@ -700,7 +716,7 @@ int mss_m2f_match_assign_f32(const float* cost, const int* tcount, int S, int B,
  * get_clean_point_coords_with_randomness (:371-407) and detectron2's get_uncertain_point_coords_with_randomness for all S
  * prediction steps of a train step (criterion.py:455-467) in a fixed number of launches: no float atomics, no host synchronisation.
  * A row is one matched (step s, target g): r = s*total_t + g, g = tstart[b] + m; its source map is the mask logits of query
- * match[s,b,m] of image b in step s (masks_host / strides / tmask / tstart / match [S,B,Tmax] as in mss_m2f_match_cost_f32), its
+ * match[s,b,m] of image b in step s (maps and targets as above; labels are read by finalize only; match [S,B,Tmax]), its
  * target map tmask[g]. A row whose table entry is outside [0, Q) has no map: its points are written as 0 and its sums as NaN.
  *
  * select (criterion.py:335-341, :371-407): rows with g >= sel_start sample their K candidates cand[s, g - sel_start, :, :]
@@ -720,28 +736,23 @@ int mss_m2f_match_assign_f32(const float* cost, const int* tcount, int S, int B,
  *   (1 - sigmoid(x)) d with a = gloss[s,1+2G] scale_G, d = gloss[s,2+2G] scale_G, N = 2 st + 1, D = sg + tt + 1, scattered through
  *   the four bilinear taps into an int64 fixed-point window in LDS (quantum 2^(e-60), 2^e >= P (|a|/P + 2|d|)), converted once:
  *   the map of a matched query is written whole by its row's workgroup, other maps are left as they are (the caller zeroes them).
- *   grads_host: S device pointers in the layout of masks_host. ws: mss_m2f_loss_workspace_bytes(S*total_t, 0, P) bytes.
+ *   grads: one tensor per step in the layout of maps. ws: mss_m2f_loss_workspace_bytes(S*total_t, 0, P) bytes.
  *   Rows of a bad step write nothing.
- * label_backward: grads_host[s] [B,Q,C1] = w[c]/wsum (softmax - onehot) gloss[s,0], written whole (0 for a bad step). */
+ * label_backward: grads->step[s] [B,Q,C1] = w[c]/wsum (softmax - onehot) gloss[s,0], written whole (0 for a bad step). */
 long long mss_m2f_loss_workspace_bytes(long long R, int K, int P);
-int mss_m2f_loss_select_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride, int h,
-                            int w, const uint8_t* tmask, const int* tstart, const int* match, int total_t, int H, int W,
-                            const float* cand, const float* rnd, int S, int B, int Q, int Tmax, int K, int k, int P, int Pr, int mode,
-                            int sel_start, float* ws, float* points, void* stream);
-int mss_m2f_loss_mask_forward_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
-                                  int h, int w, const uint8_t* tmask, const int* tstart, const int* match, int total_t, int H, int W,
-                                  const float* points, int S, int B, int Q, int Tmax, int P, double* rows, void* stream);
-int mss_m2f_loss_finalize_f32(const float* const* cls_host, const int* labels, const int* tstart, const int* match, const float* weight,
-                              const double* rows, int total_t, int S, int B, int Q, int C1, int Tmax, int P, int split, double scale0,
-                              double scale1, int ncols, int* tclass, int* bad, double* wsum, float* loss, void* stream);
-int mss_m2f_loss_mask_backward_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
-                                   int h, int w, const uint8_t* tmask, const int* tstart, const int* match, const int* bad, int total_t,
-                                   int H, int W, const float* points, const double* rows, const float* gloss, int S, int B, int Q, int Tmax,
-                                   int P, int split, double scale0, double scale1, int ncols, float* ws, float* const* grads_host,
-                                   void* stream);
-int mss_m2f_loss_label_backward_f32(const float* const* cls_host, const int* tclass, const int* bad, const float* weight,
-                                    const double* wsum, const float* gloss, int S, int B, int Q, int C1, int ncols, float* const* grads_host,
-                                    void* stream);
+int mss_m2f_loss_select_f32(const MssM2fMaps* maps, const MssM2fTargets* targets, const int* match, const float* cand, const float* rnd,
+                            int Tmax, int K, int k, int P, int Pr, int mode, int sel_start, float* ws, float* points, void* stream);
+int mss_m2f_loss_mask_forward_f32(const MssM2fMaps* maps, const MssM2fTargets* targets, const int* match, const float* points, int Tmax,
+                                  int P, double* rows, void* stream);
+/* finalize and label_backward read no mask logits: they take S, B and Q as they are; finalize reads tstart, labels and total_t of targets. */
+int mss_m2f_loss_finalize_f32(const MssM2fSteps* cls, const MssM2fTargets* targets, const int* match, const float* weight,
+                              const double* rows, int S, int B, int Q, int C1, int Tmax, int P, int split, double scale0, double scale1,
+                              int ncols, int* tclass, int* bad, double* wsum, float* loss, void* stream);
+int mss_m2f_loss_mask_backward_f32(const MssM2fMaps* maps, const MssM2fTargets* targets, const int* match, const int* bad,
+                                   const float* points, const double* rows, const float* gloss, int Tmax, int P, int split, double scale0,
+                                   double scale1, int ncols, float* ws, const MssM2fGrads* grads, void* stream);
+int mss_m2f_loss_label_backward_f32(const MssM2fSteps* cls, const int* tclass, const int* bad, const float* weight, const double* wsum,
+                                    const float* gloss, int S, int B, int Q, int C1, int ncols, const MssM2fGrads* grads, void* stream);
 
 /* ---- SetCriterion.loss_ood, RCL branch: the class mix, forward and backward (csrc/m2f_mix.hip) ----
  * replaces, per prediction step, lib/network/mask2former/modeling/criterion.py:133-138 and :170-175 (softmax without the last

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 17         # include/mss_hip.h
+MSS_ABI_VERSION = 18         # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -29,6 +29,26 @@ class MssOodmBatch(Structure):
     """include/mss_hip.h: up to 16 (score, label, keys, lane_counts, n) entries of mss_oodm_compact_lanes_batch_f32."""
     _fields_ = [("score", c_void_p * MSS_OODM_BATCH), ("label", c_void_p * MSS_OODM_BATCH), ("keys", c_void_p * MSS_OODM_BATCH),
                 ("lane_counts", c_void_p * MSS_OODM_BATCH), ("n", ctypes.c_longlong * MSS_OODM_BATCH)]
+
+
+MSS_M2F_MAX_STEPS = 16         # include/mss_hip.h: one device pointer per prediction step in the three tables below
+
+
+class MssM2fSteps(Structure):   # tensors that are read (class logits)
+    _fields_ = [("step", c_void_p * MSS_M2F_MAX_STEPS)]
+
+
+class MssM2fGrads(Structure):   # tensors that are written
+    _fields_ = [("step", c_void_p * MSS_M2F_MAX_STEPS)]
+
+
+class MssM2fMaps(Structure):    # the mask logits of S prediction steps, NCHW or pixel-major
+    _fields_ = [("step", c_void_p * MSS_M2F_MAX_STEPS), ("img_stride", c_longlong), ("query_stride", c_longlong), ("pixel_stride", c_longlong),
+                ("S", c_int), ("B", c_int), ("Q", c_int), ("h", c_int), ("w", c_int)]
+
+
+class MssM2fTargets(Structure):
+    _fields_ = [("tmask", c_void_p), ("tstart", c_void_p), ("labels", c_void_p), ("total_t", c_int), ("H", c_int), ("W", c_int)]
 
 
 class MssConvArgs(Structure):
@@ -162,28 +182,28 @@ SIGNATURES = {
     "mss_wino_grad_output_transform_f32": [P, I, I, I, I, I, I, I, P, P],
     "mss_wino_weight_grad_transform_f32": [P, P, I, I, I, I, I, P],
     "mss_m2f_fused_score_ws_f32": [P, P, I, I, I, I, I, I, I, I, I, I, P, P, P],
-    "mss_m2f_attn_mask_bits_f32": [P, I, I, I, I, I, I, I, P, P],
+    "mss_m2f_attn_mask_bits_f32": [P, I, I, I, I, I, I, I, P, P, P],
     "mss_m2f_attn_workspace_bytes": [I, I, I, I],
-    "mss_m2f_masked_attention_f32": [P, I, P, I, P, I, P, P, I, I, I, I, F, I, P, P, I],
-    "mss_m2f_masked_attention_lse_f32": [P, I, P, I, P, I, P, P, I, I, I, I, F, I, P, P, I, P],
+    "mss_m2f_masked_attention_f32": [P, I, P, I, P, I, P, P, I, I, I, I, F, I, P, P, I, P],
+    "mss_m2f_masked_attention_lse_f32": [P, I, P, I, P, I, P, P, I, I, I, I, F, I, P, P, I, P, P],
     "mss_m2f_attn_bwd_workspace_bytes": [I, I, I, I],
-    "mss_m2f_masked_attention_bwd_f32": [P, I, P, I, P, I, P, P, P, I, P, P, I, I, I, I, I, F, I, P, P, P, P],
+    "mss_m2f_masked_attention_bwd_f32": [P, I, P, I, P, I, P, P, P, I, P, P, I, I, I, I, I, F, I, P, P, P, P, P],
     "mss_m2f_match_workspace_bytes": [I, I, I, I, I],
-    "mss_m2f_match_cost_f32": [P, L, L, L, I, I, P, P, P, P, I, I, I, P, I, I, I, I, I, I, F, F, F, P, P, P, P, P],
+    "mss_m2f_match_cost_f32": [POINTER(MssM2fMaps), POINTER(MssM2fSteps), POINTER(MssM2fTargets), P, I, I, I, F, F, F, P, P, P, P, P],
     "mss_m2f_match_assign_f32": [P, P, I, I, I, I, P, P, P],
     "mss_m2f_loss_workspace_bytes": [L, I, I],
-    "mss_m2f_loss_select_f32": [P, L, L, L, I, I, P, P, P, I, I, I, P, P, I, I, I, I, I, I, I, I, I, I, P, P, P],
-    "mss_m2f_loss_mask_forward_f32": [P, L, L, L, I, I, P, P, P, I, I, I, P, I, I, I, I, I, P, P],
-    "mss_m2f_loss_finalize_f32": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, c_double, c_double, I, P, P, P, P, P],
-    "mss_m2f_loss_mask_backward_f32": [P, L, L, L, I, I, P, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, c_double, c_double, I, P, P, P],
-    "mss_m2f_loss_label_backward_f32": [P, P, P, P, P, P, I, I, I, I, I, P, P],
+    "mss_m2f_loss_select_f32": [POINTER(MssM2fMaps), POINTER(MssM2fTargets), P, P, P, I, I, I, I, I, I, I, P, P, P],
+    "mss_m2f_loss_mask_forward_f32": [POINTER(MssM2fMaps), POINTER(MssM2fTargets), P, P, I, I, P, P],
+    "mss_m2f_loss_finalize_f32": [POINTER(MssM2fSteps), POINTER(MssM2fTargets), P, P, P, I, I, I, I, I, I, I, c_double, c_double, I, P, P, P, P, P],
+    "mss_m2f_loss_mask_backward_f32": [POINTER(MssM2fMaps), POINTER(MssM2fTargets), P, P, P, P, P, I, I, I, c_double, c_double, I, P, POINTER(MssM2fGrads), P],
+    "mss_m2f_loss_label_backward_f32": [POINTER(MssM2fSteps), P, P, P, P, P, I, I, I, I, I, POINTER(MssM2fGrads), P],
     "mss_m2f_mix_backward_chunks": [L],
     "mss_m2f_mix_forward_f32": [P, P, L, L, L, I, I, I, I, I, P, P, P],
     "mss_m2f_mix_upsample_f32": [P, I, I, I, I, I, I, I, I, I, P, P],
     "mss_m2f_mix_upsample_backward_f32": [P, P, P, I, I, I, I, I, I, I, I, P, P],
     "mss_m2f_mix_backward_f32": [P, P, P, P, L, L, L, I, I, I, I, I, P, P, P, P],
     "mss_oodm_compact_lanes_f32": [P, P, L, L, L, P, P, P],
-    "mss_oodm_compact_lanes_batch_f32": [P, I, L, L, P],
+    "mss_oodm_compact_lanes_batch_f32": [POINTER(MssOodmBatch), I, L, L, P],
     "mss_oodm_gather_lanes_u32": [P, L, P, P, P, P],
     "mss_oodm_sort_temp_bytes": [L],
     "mss_oodm_compact_lanes_cap": [L],
@@ -211,18 +231,16 @@ SIGNATURES = {
     "mss_peak_stream_f32": [P, P, L, I, P],
     "mss_peak_scatter_f32": [P, P, L, I, I, L, P],
 }
-# entry points that return a plain value rather than a status code
-_VALUE_RETURNING = {"mss_chan_compact_wanted", "mss_gemm_split_last_mfma", "mss_conv2d_wgrad_route", "mss_gemm_split_weights_bytes", "mss_abi_version", "mss_env_reset", "mss_env_generation", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_attn_bwd_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_m2f_mix_backward_chunks", "mss_conv2d_kpad", "mss_conv2d_forward_route", "mss_rcl_num_compact_blocks", "mss_wino_num_tiles",
-                    "mss_oodm_sort_temp_bytes", "mss_oodm_compact_lanes_cap", "mss_oodm_rank_blocks", "mss_wino_output_stats_parts",
-                    "mss_conv2d_wgrad_workspace_bytes", "mss_col_reduce_accum_doubles", "mss_colsum_workspace_floats",
-                    "mss_add_layernorm_bwd_workspace_floats", "mss_groupnorm_workspace_floats",
-                    "mss_groupnorm_stat_offset", "mss_groupnorm_bwd_workspace_floats",
-                    "mss_adamw_chunk_elems", "mss_adamw_tensors_per_launch", "mss_adamw_blocks_per_launch", "mss_adamw_scratch_floats",
-                    "mss_adamw_plan"}
-_RETURNS_LONGLONG = {"mss_oodm_compact_lanes_cap", "mss_gemm_split_weights_bytes", "mss_rcl_workspace_bytes", "mss_msda_backward_workspace_bytes", "mss_m2f_attn_workspace_bytes", "mss_m2f_attn_bwd_workspace_bytes", "mss_m2f_match_workspace_bytes", "mss_m2f_loss_workspace_bytes", "mss_wino_num_tiles", "mss_oodm_sort_temp_bytes", "mss_conv2d_wgrad_workspace_bytes",
-                     "mss_col_reduce_accum_doubles", "mss_colsum_workspace_floats",
-                     "mss_add_layernorm_bwd_workspace_floats", "mss_groupnorm_workspace_floats",
-                     "mss_groupnorm_stat_offset", "mss_groupnorm_bwd_workspace_floats", "mss_adamw_scratch_floats", "mss_adamw_plan"}
+# the entry points that return a plain value, and its C type; every other one returns an int status code
+VALUE_RESTYPE = {
+    "mss_abi_version": c_int, "mss_env_reset": c_int, "mss_env_generation": c_int, "mss_msda_backward_workspace_bytes": c_longlong, "mss_chan_compact_wanted": c_int, "mss_conv2d_kpad": c_int,
+    "mss_conv2d_forward_route": c_int, "mss_gemm_split_last_mfma": c_int, "mss_gemm_split_weights_bytes": c_longlong, "mss_conv2d_wgrad_workspace_bytes": c_longlong, "mss_conv2d_wgrad_route": c_int,
+    "mss_col_reduce_accum_doubles": c_longlong, "mss_colsum_workspace_floats": c_longlong, "mss_rcl_num_compact_blocks": c_int, "mss_rcl_workspace_bytes": c_longlong, "mss_adamw_chunk_elems": c_int,
+    "mss_adamw_tensors_per_launch": c_int, "mss_adamw_blocks_per_launch": c_int, "mss_adamw_scratch_floats": c_longlong, "mss_adamw_plan": c_longlong, "mss_wino_num_tiles": c_longlong,
+    "mss_wino_output_stats_parts": c_int, "mss_m2f_attn_workspace_bytes": c_longlong, "mss_m2f_attn_bwd_workspace_bytes": c_longlong, "mss_m2f_match_workspace_bytes": c_longlong,
+    "mss_m2f_loss_workspace_bytes": c_longlong, "mss_m2f_mix_backward_chunks": c_int, "mss_oodm_sort_temp_bytes": c_longlong, "mss_oodm_compact_lanes_cap": c_longlong, "mss_oodm_rank_blocks": c_int,
+    "mss_add_layernorm_bwd_workspace_floats": c_longlong, "mss_groupnorm_workspace_floats": c_longlong, "mss_groupnorm_stat_offset": c_longlong, "mss_groupnorm_bwd_workspace_floats": c_longlong,
+}
 
 _lib = None
 
@@ -240,7 +258,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.argtypes = argtypes
-        fn.restype = c_longlong if name in _RETURNS_LONGLONG else c_int
+        fn.restype = VALUE_RESTYPE.get(name, c_int)
     got = lib.mss_abi_version()
     if got != MSS_ABI_VERSION:
         raise MssError(f"{LIB_PATH} has ABI version {got}, this package expects {MSS_ABI_VERSION}: rebuild it "
@@ -295,5 +313,5 @@ def status(name, *args):
 
 
 def value(name, *args):
-    assert name in _VALUE_RETURNING
+    assert name in VALUE_RESTYPE
     return getattr(load(), name)(*args)

@@ -16,16 +16,12 @@
 // DESIGN.md 3.13 holds the reasoning.
 #include "mss_common.h"
 #include "mss_point_sample.h"
-#include "../../include/mss_hip.h"
+#include "mss_m2f_maps.h"
 
 namespace {
 
-constexpr int ML_MAXS = 16;        // most prediction steps of a call (as the matcher)
 constexpr int ML_T = 256;          // threads of every workgroup here
 constexpr int ML_BAND = 7680;      // int64 cells of the backward's LDS window: 60 KiB
-
-struct LossPtrs { const float* p[ML_MAXS]; };
-struct LossGradPtrs { float* p[ML_MAXS]; };
 
 struct LossRow { int s, b, g, q; };      // q < 0: the row has no map (an unsolved problem)
 
@@ -60,18 +56,18 @@ __device__ __forceinline__ unsigned key_bits(float key) {
 __device__ __forceinline__ float bce_with_logits(float x, float t) { return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x))); }
 
 // grid R, 256 threads
-__global__ __launch_bounds__(ML_T) void loss_select_kernel(LossPtrs masks, long long bs, long long qs, long long ps, int h, int w,
-                                                            const uint8_t* __restrict__ tmask, const int* __restrict__ tstart,
-                                                            const int* __restrict__ match, int total_t, int H, int W,
-                                                            const float* __restrict__ cand, const float* __restrict__ rnd, int B, int Q,
-                                                            int Tmax, int K, int k, int P, int Pr, int mode, int sel_start,
-                                                            unsigned* __restrict__ ws, float* __restrict__ points) {
+__global__ __launch_bounds__(ML_T) void loss_select_kernel(MssM2fMaps maps, MssM2fTargets tg, const int* __restrict__ match,
+                                                            const float* __restrict__ cand, const float* __restrict__ rnd, int Tmax, int K, int k,
+                                                            int P, int Pr, int mode, int sel_start, unsigned* __restrict__ ws,
+                                                            float* __restrict__ points) {
+  const long long bs = maps.img_stride, qs = maps.query_stride, ps = maps.pixel_stride;
+  const int B = maps.B, Q = maps.Q, h = maps.h, w = maps.w, total_t = tg.total_t, H = tg.H, W = tg.W;
   __shared__ unsigned hist[256];
   __shared__ unsigned sh_prefix, sh_need;
   __shared__ unsigned wcnt[ML_T / 64][2];
   const int tid = threadIdx.x;
   const long long r = blockIdx.x;
-  const LossRow row = loss_row(r, total_t, tstart, match, B, Q, Tmax);
+  const LossRow row = loss_row(r, total_t, tg.tstart, match, B, Q, Tmax);
   float* out = points + r * P * 2;
   if (row.q < 0) {
     for (int i = tid; i < 2 * P; i += ML_T) out[i] = 0.f;
@@ -84,8 +80,8 @@ __global__ __launch_bounds__(ML_T) void loss_select_kernel(LossPtrs masks, long 
 
   const float* cp = cand + ((long long)row.s * (total_t - sel_start) + (row.g - sel_start)) * K * 2;
   unsigned* keys = ws + r * K;
-  const float* src = masks.p[row.s] + (long long)row.b * bs + (long long)row.q * qs;
-  const uint8_t* tgt = tmask + (long long)row.g * H * W;
+  const float* src = maps.step[row.s] + (long long)row.b * bs + (long long)row.q * qs;
+  const uint8_t* tgt = tg.tmask + (long long)row.g * H * W;
   for (int i = tid; i < K; i += ML_T) {
     const float u = cp[2 * i], v = cp[2 * i + 1];
     PointTap a;
@@ -204,21 +200,20 @@ __device__ __forceinline__ PointVal point_val(const float* src, long long ps, in
 }
 
 // grid R, 256 threads
-__global__ __launch_bounds__(ML_T) void loss_mask_forward_kernel(LossPtrs masks, long long bs, long long qs, long long ps, int h, int w,
-                                                                  const uint8_t* __restrict__ tmask, const int* __restrict__ tstart,
-                                                                  const int* __restrict__ match, int total_t, int H, int W,
-                                                                  const float* __restrict__ points, int B, int Q, int Tmax, int P,
-                                                                  double* __restrict__ rows) {
+__global__ __launch_bounds__(ML_T) void loss_mask_forward_kernel(MssM2fMaps maps, MssM2fTargets tg, const int* __restrict__ match,
+                                                                  const float* __restrict__ points, int Tmax, int P, double* __restrict__ rows) {
+  const long long bs = maps.img_stride, qs = maps.query_stride, ps = maps.pixel_stride;
+  const int B = maps.B, Q = maps.Q, h = maps.h, w = maps.w, total_t = tg.total_t, H = tg.H, W = tg.W;
   __shared__ double red[ML_T];
   const int tid = threadIdx.x;
   const long long r = blockIdx.x;
-  const LossRow row = loss_row(r, total_t, tstart, match, B, Q, Tmax);
+  const LossRow row = loss_row(r, total_t, tg.tstart, match, B, Q, Tmax);
   if (row.q < 0) {
     if (tid < 4) rows[r * 4 + tid] = __builtin_nan("");
     return;
   }
-  const float* src = masks.p[row.s] + (long long)row.b * bs + (long long)row.q * qs;
-  const uint8_t* tgt = tmask + (long long)row.g * H * W;
+  const float* src = maps.step[row.s] + (long long)row.b * bs + (long long)row.q * qs;
+  const uint8_t* tgt = tg.tmask + (long long)row.g * H * W;
   const float* pts = points + r * P * 2;
   double a_bce = 0., a_st = 0., a_sg = 0., a_t = 0.;
   for (int p = tid; p < P; p += ML_T) {
@@ -242,12 +237,12 @@ __global__ __launch_bounds__(ML_T) void loss_mask_forward_kernel(LossPtrs masks,
 }
 
 // grid S, 256 threads
-__global__ __launch_bounds__(ML_T) void loss_finalize_kernel(LossPtrs cls, const int* __restrict__ labels, const int* __restrict__ tstart,
-                                                              const int* __restrict__ match, const float* __restrict__ weight,
-                                                              const double* __restrict__ rows, int total_t, int B, int Q, int C1, int Tmax,
-                                                              int P, int split, double scale0, double scale1, int ncols,
+__global__ __launch_bounds__(ML_T) void loss_finalize_kernel(MssM2fSteps cls, MssM2fTargets tg, const int* __restrict__ match,
+                                                              const float* __restrict__ weight, const double* __restrict__ rows, int B, int Q,
+                                                              int C1, int Tmax, int P, int split, double scale0, double scale1, int ncols,
                                                               int* __restrict__ tclass, int* __restrict__ bad, double* __restrict__ wsum,
                                                               float* __restrict__ loss) {
+  const int total_t = tg.total_t;
   __shared__ double red[ML_T];
   __shared__ int sbad;
   const int tid = threadIdx.x, s = blockIdx.x;
@@ -256,13 +251,13 @@ __global__ __launch_bounds__(ML_T) void loss_finalize_kernel(LossPtrs cls, const
   for (int i = tid; i < B * Q; i += ML_T) tc[i] = C1 - 1;
   __syncthreads();
   for (int g = tid; g < total_t; g += ML_T) {
-    const LossRow row = loss_row((long long)s * total_t + g, total_t, tstart, match, B, Q, Tmax);
-    const int lab = labels[g];
+    const LossRow row = loss_row((long long)s * total_t + g, total_t, tg.tstart, match, B, Q, Tmax);
+    const int lab = tg.labels[g];
     if (row.q < 0 || lab < 0 || lab >= C1 - 1) atomicOr(&sbad, 1);
     else tc[row.b * Q + row.q] = lab;
   }
   __syncthreads();
-  const float* lg = cls.p[s];
+  const float* lg = cls.step[s];
   double num = 0., den = 0.;
   for (int i = tid; i < B * Q; i += ML_T) {
     const float* x = lg + (long long)i * C1;
@@ -298,22 +293,22 @@ __global__ __launch_bounds__(ML_T) void loss_finalize_kernel(LossPtrs cls, const
 }
 
 // grid R, 256 threads
-__global__ __launch_bounds__(ML_T) void loss_mask_backward_kernel(LossPtrs masks, long long bs, long long qs, long long ps, int h, int w,
-                                                                   const uint8_t* __restrict__ tmask, const int* __restrict__ tstart,
-                                                                   const int* __restrict__ match, const int* __restrict__ bad, int total_t,
-                                                                   int H, int W, const float* __restrict__ points,
-                                                                   const double* __restrict__ rows, const float* __restrict__ gloss, int B,
-                                                                   int Q, int Tmax, int P, int split, double scale0, double scale1, int ncols,
-                                                                   float* __restrict__ ws, LossGradPtrs grads) {
+__global__ __launch_bounds__(ML_T) void loss_mask_backward_kernel(MssM2fMaps maps, MssM2fTargets tg, const int* __restrict__ match,
+                                                                   const int* __restrict__ bad, const float* __restrict__ points,
+                                                                   const double* __restrict__ rows, const float* __restrict__ gloss, int Tmax,
+                                                                   int P, int split, double scale0, double scale1, int ncols,
+                                                                   float* __restrict__ ws, MssM2fGrads grads) {
+  const long long bs = maps.img_stride, qs = maps.query_stride, ps = maps.pixel_stride;
+  const int B = maps.B, Q = maps.Q, h = maps.h, w = maps.w, total_t = tg.total_t, H = tg.H, W = tg.W;
   __shared__ unsigned long long win[ML_BAND];
   const int tid = threadIdx.x;
   const long long r = blockIdx.x;
-  const LossRow row = loss_row(r, total_t, tstart, match, B, Q, Tmax);
+  const LossRow row = loss_row(r, total_t, tg.tstart, match, B, Q, Tmax);
   if (row.q < 0 || bad[row.s]) return;
   const long long map = (long long)row.b * bs + (long long)row.q * qs;
-  const float* src = masks.p[row.s] + map;
-  float* dst = grads.p[row.s] + map;
-  const uint8_t* tgt = tmask + (long long)row.g * H * W;
+  const float* src = maps.step[row.s] + map;
+  float* dst = grads.step[row.s] + map;
+  const uint8_t* tgt = tg.tmask + (long long)row.g * H * W;
   const float* pts = points + r * P * 2;
   float* gc = ws + r * P;
   const int G = row.g >= split ? 1 : 0;
@@ -365,15 +360,15 @@ __global__ __launch_bounds__(ML_T) void loss_mask_backward_kernel(LossPtrs masks
 }
 
 // grid (ceil(B Q / 256), S), 256 threads: one query per thread
-__global__ __launch_bounds__(ML_T) void loss_label_backward_kernel(LossPtrs cls, const int* __restrict__ tclass, const int* __restrict__ bad,
+__global__ __launch_bounds__(ML_T) void loss_label_backward_kernel(MssM2fSteps cls, const int* __restrict__ tclass, const int* __restrict__ bad,
                                                                     const float* __restrict__ weight, const double* __restrict__ wsum,
                                                                     const float* __restrict__ gloss, int B, int Q, int C1, int ncols,
-                                                                    LossGradPtrs grads) {
+                                                                    MssM2fGrads grads) {
   const int s = blockIdx.y;
   const long long i = (long long)blockIdx.x * ML_T + threadIdx.x;
   if (i >= (long long)B * Q) return;
-  const float* x = cls.p[s] + i * C1;
-  float* o = grads.p[s] + i * C1;
+  const float* x = cls.step[s] + i * C1;
+  float* o = grads.step[s] + i * C1;
   if (bad[s]) {
     for (int c = 0; c < C1; ++c) o[c] = 0.f;
     return;
@@ -388,16 +383,7 @@ __global__ __launch_bounds__(ML_T) void loss_label_backward_kernel(LossPtrs cls,
 }
 
 bool loss_shape_ok(int S, int B, int Q, int Tmax, int total_t) {
-  return S >= 1 && S <= ML_MAXS && B >= 1 && Q >= 1 && Tmax >= 1 && total_t >= 0 && (long long)S * total_t <= 0x7fffffffll;
-}
-
-bool fill_ptrs(LossPtrs& o, const float* const* host, int S) {
-  if (!host) return false;
-  for (int s = 0; s < S; ++s) {
-    if (!host[s]) return false;
-    o.p[s] = host[s];
-  }
-  return true;
+  return m2f_steps_ok(S) && B >= 1 && Q >= 1 && Tmax >= 1 && total_t >= 0 && (long long)S * total_t <= 0x7fffffffll;
 }
 
 }  // namespace
@@ -407,89 +393,84 @@ extern "C" long long mss_m2f_loss_workspace_bytes(long long R, int K, int P) {
   return 4ll * R * (K > P ? K : P);
 }
 
-extern "C" int mss_m2f_loss_select_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
-                                       int h, int w, const uint8_t* tmask, const int* tstart, const int* match, int total_t, int H, int W,
-                                       const float* cand, const float* rnd, int S, int B, int Q, int Tmax, int K, int k, int P, int Pr,
-                                       int mode, int sel_start, float* ws, float* points, void* stream) {
-  if (!tstart || !match || h < 1 || w < 1 || H < 1 || W < 1 || P < 1 || K < 0 || k < 0 || k > K || k > P || Pr < 0) return MSS_ERR_BAD_ARG;
-  if (!loss_shape_ok(S, B, Q, Tmax, total_t)) return MSS_ERR_UNSUPPORTED;
-  if (img_stride < 0 || query_stride < 0 || pixel_stride < 0 || sel_start < 0 || sel_start > total_t || (mode != 1 && mode != 2)) return MSS_ERR_BAD_ARG;
+extern "C" int mss_m2f_loss_select_f32(const MssM2fMaps* maps, const MssM2fTargets* targets, const int* match, const float* cand,
+                                       const float* rnd, int Tmax, int K, int k, int P, int Pr, int mode, int sel_start, float* ws, float* points,
+                                       void* stream) {
+  if (!maps || !targets) return MSS_ERR_BAD_ARG;
+  MssM2fMaps m = *maps;
+  const MssM2fTargets tg = *targets;
+  const int S = m.S, total_t = tg.total_t;
+  if (!tg.tstart || !match || m.h < 1 || m.w < 1 || tg.H < 1 || tg.W < 1 || P < 1 || K < 0 || k < 0 || k > K || k > P || Pr < 0) return MSS_ERR_BAD_ARG;
+  if (!loss_shape_ok(S, m.B, m.Q, Tmax, total_t)) return MSS_ERR_UNSUPPORTED;
+  if (m.img_stride < 0 || m.query_stride < 0 || m.pixel_stride < 0 || sel_start < 0 || sel_start > total_t || (mode != 1 && mode != 2)) return MSS_ERR_BAD_ARG;
   if (total_t == 0) return MSS_OK;
   const bool selects = k > 0 && sel_start < total_t;
-  if (!tmask || !points || (selects && (!cand || !ws))) return MSS_ERR_BAD_ARG;
+  if (!tg.tmask || !points || (selects && (!cand || !ws))) return MSS_ERR_BAD_ARG;
   const int most_random = (sel_start > 0 || k == 0) ? P : P - k;      // the most points a row takes from rnd
   if (Pr < most_random || (most_random > 0 && !rnd)) return MSS_ERR_BAD_ARG;
-  LossPtrs mp = {};
-  if (!fill_ptrs(mp, masks_host, S)) return MSS_ERR_BAD_ARG;
-  loss_select_kernel<<<S * total_t, ML_T, 0, (hipStream_t)stream>>>(mp, img_stride, query_stride, pixel_stride, h, w, tmask, tstart, match, total_t, H,
-                                                                    W, cand, rnd, B, Q, Tmax, K, k, P, Pr, mode, sel_start, (unsigned*)ws, points);
+  if (!m2f_fill(m.step, maps->step, S)) return MSS_ERR_BAD_ARG;
+  loss_select_kernel<<<S * total_t, ML_T, 0, (hipStream_t)stream>>>(m, tg, match, cand, rnd, Tmax, K, k, P, Pr, mode, sel_start, (unsigned*)ws, points);
   return mss_launch_status();
 }
 
-extern "C" int mss_m2f_loss_mask_forward_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
-                                             int h, int w, const uint8_t* tmask, const int* tstart, const int* match, int total_t, int H, int W,
-                                             const float* points, int S, int B, int Q, int Tmax, int P, double* rows, void* stream) {
-  if (!tstart || !match || h < 1 || w < 1 || H < 1 || W < 1 || P < 1) return MSS_ERR_BAD_ARG;
-  if (!loss_shape_ok(S, B, Q, Tmax, total_t)) return MSS_ERR_UNSUPPORTED;
-  if (img_stride < 0 || query_stride < 0 || pixel_stride < 0) return MSS_ERR_BAD_ARG;
+extern "C" int mss_m2f_loss_mask_forward_f32(const MssM2fMaps* maps, const MssM2fTargets* targets, const int* match, const float* points, int Tmax,
+                                             int P, double* rows, void* stream) {
+  if (!maps || !targets) return MSS_ERR_BAD_ARG;
+  MssM2fMaps m = *maps;
+  const MssM2fTargets tg = *targets;
+  const int S = m.S, total_t = tg.total_t;
+  if (!tg.tstart || !match || m.h < 1 || m.w < 1 || tg.H < 1 || tg.W < 1 || P < 1) return MSS_ERR_BAD_ARG;
+  if (!loss_shape_ok(S, m.B, m.Q, Tmax, total_t)) return MSS_ERR_UNSUPPORTED;
+  if (m.img_stride < 0 || m.query_stride < 0 || m.pixel_stride < 0) return MSS_ERR_BAD_ARG;
   if (total_t == 0) return MSS_OK;
-  if (!tmask || !points || !rows) return MSS_ERR_BAD_ARG;
-  LossPtrs mp = {};
-  if (!fill_ptrs(mp, masks_host, S)) return MSS_ERR_BAD_ARG;
-  loss_mask_forward_kernel<<<S * total_t, ML_T, 0, (hipStream_t)stream>>>(mp, img_stride, query_stride, pixel_stride, h, w, tmask, tstart, match,
-                                                                          total_t, H, W, points, B, Q, Tmax, P, rows);
+  if (!tg.tmask || !points || !rows) return MSS_ERR_BAD_ARG;
+  if (!m2f_fill(m.step, maps->step, S)) return MSS_ERR_BAD_ARG;
+  loss_mask_forward_kernel<<<S * total_t, ML_T, 0, (hipStream_t)stream>>>(m, tg, match, points, Tmax, P, rows);
   return mss_launch_status();
 }
 
-extern "C" int mss_m2f_loss_finalize_f32(const float* const* cls_host, const int* labels, const int* tstart, const int* match,
-                                         const float* weight, const double* rows, int total_t, int S, int B, int Q, int C1, int Tmax, int P,
-                                         int split, double scale0, double scale1, int ncols, int* tclass, int* bad, double* wsum, float* loss,
-                                         void* stream) {
-  if (!tstart || !match || !weight || !tclass || !bad || !wsum || !loss || C1 < 2 || P < 1 || (ncols != 3 && ncols != 5)) return MSS_ERR_BAD_ARG;
+extern "C" int mss_m2f_loss_finalize_f32(const MssM2fSteps* cls, const MssM2fTargets* targets, const int* match, const float* weight,
+                                         const double* rows, int S, int B, int Q, int C1, int Tmax, int P, int split, double scale0, double scale1,
+                                         int ncols, int* tclass, int* bad, double* wsum, float* loss, void* stream) {
+  if (!targets) return MSS_ERR_BAD_ARG;
+  const MssM2fTargets tg = *targets;
+  const int total_t = tg.total_t;
+  if (!tg.tstart || !match || !weight || !tclass || !bad || !wsum || !loss || C1 < 2 || P < 1 || (ncols != 3 && ncols != 5)) return MSS_ERR_BAD_ARG;
   if (!loss_shape_ok(S, B, Q, Tmax, total_t) || (long long)B * Q > 0x7fffffffll) return MSS_ERR_UNSUPPORTED;
-  if (split < 0 || split > total_t || (ncols == 3 && split != total_t) || (total_t > 0 && (!labels || !rows))) return MSS_ERR_BAD_ARG;
-  LossPtrs cp = {};
-  if (!fill_ptrs(cp, cls_host, S)) return MSS_ERR_BAD_ARG;
-  loss_finalize_kernel<<<S, ML_T, 0, (hipStream_t)stream>>>(cp, labels, tstart, match, weight, rows, total_t, B, Q, C1, Tmax, P, split, scale0, scale1,
-                                                            ncols, tclass, bad, wsum, loss);
+  if (split < 0 || split > total_t || (ncols == 3 && split != total_t) || (total_t > 0 && (!tg.labels || !rows))) return MSS_ERR_BAD_ARG;
+  MssM2fSteps cp;
+  if (!cls || !m2f_fill(cp.step, cls->step, S)) return MSS_ERR_BAD_ARG;
+  loss_finalize_kernel<<<S, ML_T, 0, (hipStream_t)stream>>>(cp, tg, match, weight, rows, B, Q, C1, Tmax, P, split, scale0, scale1, ncols, tclass, bad,
+                                                            wsum, loss);
   return mss_launch_status();
 }
 
-extern "C" int mss_m2f_loss_mask_backward_f32(const float* const* masks_host, long long img_stride, long long query_stride,
-                                              long long pixel_stride, int h, int w, const uint8_t* tmask, const int* tstart, const int* match,
-                                              const int* bad, int total_t, int H, int W, const float* points, const double* rows,
-                                              const float* gloss, int S, int B, int Q, int Tmax, int P, int split, double scale0, double scale1,
-                                              int ncols, float* ws, float* const* grads_host, void* stream) {
-  if (!tstart || !match || !bad || !gloss || h < 1 || w < 1 || H < 1 || W < 1 || P < 1 || (ncols != 3 && ncols != 5)) return MSS_ERR_BAD_ARG;
-  if (!loss_shape_ok(S, B, Q, Tmax, total_t) || w > ML_BAND) return MSS_ERR_UNSUPPORTED;
-  if (img_stride < 0 || query_stride < 0 || pixel_stride < 0 || split < 0 || split > total_t || (ncols == 3 && split != total_t)) return MSS_ERR_BAD_ARG;
+extern "C" int mss_m2f_loss_mask_backward_f32(const MssM2fMaps* maps, const MssM2fTargets* targets, const int* match, const int* bad,
+                                              const float* points, const double* rows, const float* gloss, int Tmax, int P, int split,
+                                              double scale0, double scale1, int ncols, float* ws, const MssM2fGrads* grads, void* stream) {
+  if (!maps || !targets) return MSS_ERR_BAD_ARG;
+  MssM2fMaps m = *maps;
+  const MssM2fTargets tg = *targets;
+  const int S = m.S, total_t = tg.total_t;
+  if (!tg.tstart || !match || !bad || !gloss || m.h < 1 || m.w < 1 || tg.H < 1 || tg.W < 1 || P < 1 || (ncols != 3 && ncols != 5)) return MSS_ERR_BAD_ARG;
+  if (!loss_shape_ok(S, m.B, m.Q, Tmax, total_t) || m.w > ML_BAND) return MSS_ERR_UNSUPPORTED;
+  if (m.img_stride < 0 || m.query_stride < 0 || m.pixel_stride < 0 || split < 0 || split > total_t || (ncols == 3 && split != total_t)) return MSS_ERR_BAD_ARG;
   if (total_t == 0) return MSS_OK;
-  if (!tmask || !points || !rows || !ws || !grads_host) return MSS_ERR_BAD_ARG;
-  LossPtrs mp = {};
-  LossGradPtrs gp = {};
-  if (!fill_ptrs(mp, masks_host, S)) return MSS_ERR_BAD_ARG;
-  for (int s = 0; s < S; ++s) {
-    if (!grads_host[s]) return MSS_ERR_BAD_ARG;
-    gp.p[s] = grads_host[s];
-  }
-  loss_mask_backward_kernel<<<S * total_t, ML_T, 0, (hipStream_t)stream>>>(mp, img_stride, query_stride, pixel_stride, h, w, tmask, tstart, match, bad,
-                                                                           total_t, H, W, points, rows, gloss, B, Q, Tmax, P, split, scale0, scale1,
-                                                                           ncols, ws, gp);
+  if (!tg.tmask || !points || !rows || !ws || !grads) return MSS_ERR_BAD_ARG;
+  MssM2fGrads gp;
+  if (!m2f_fill(m.step, maps->step, S) || !m2f_fill(gp.step, grads->step, S)) return MSS_ERR_BAD_ARG;
+  loss_mask_backward_kernel<<<S * total_t, ML_T, 0, (hipStream_t)stream>>>(m, tg, match, bad, points, rows, gloss, Tmax, P, split, scale0, scale1, ncols,
+                                                                           ws, gp);
   return mss_launch_status();
 }
 
-extern "C" int mss_m2f_loss_label_backward_f32(const float* const* cls_host, const int* tclass, const int* bad, const float* weight,
-                                               const double* wsum, const float* gloss, int S, int B, int Q, int C1, int ncols,
-                                               float* const* grads_host, void* stream) {
-  if (!tclass || !bad || !weight || !wsum || !gloss || !grads_host || C1 < 2 || (ncols != 3 && ncols != 5)) return MSS_ERR_BAD_ARG;
-  if (S < 1 || S > ML_MAXS || B < 1 || Q < 1 || (long long)B * Q > 0x7fffffffll) return MSS_ERR_UNSUPPORTED;
-  LossPtrs cp = {};
-  LossGradPtrs gp = {};
-  if (!fill_ptrs(cp, cls_host, S)) return MSS_ERR_BAD_ARG;
-  for (int s = 0; s < S; ++s) {
-    if (!grads_host[s]) return MSS_ERR_BAD_ARG;
-    gp.p[s] = grads_host[s];
-  }
+extern "C" int mss_m2f_loss_label_backward_f32(const MssM2fSteps* cls, const int* tclass, const int* bad, const float* weight, const double* wsum,
+                                               const float* gloss, int S, int B, int Q, int C1, int ncols, const MssM2fGrads* grads, void* stream) {
+  if (!tclass || !bad || !weight || !wsum || !gloss || !grads || C1 < 2 || (ncols != 3 && ncols != 5)) return MSS_ERR_BAD_ARG;
+  if (!m2f_steps_ok(S) || B < 1 || Q < 1 || (long long)B * Q > 0x7fffffffll) return MSS_ERR_UNSUPPORTED;
+  MssM2fSteps cp;
+  MssM2fGrads gp;
+  if (!cls || !m2f_fill(cp.step, cls->step, S) || !m2f_fill(gp.step, grads->step, S)) return MSS_ERR_BAD_ARG;
   loss_label_backward_kernel<<<dim3(mss_cdiv((long long)B * Q, ML_T), S), ML_T, 0, (hipStream_t)stream>>>(cp, tclass, bad, weight, wsum, gloss, B, Q, C1,
                                                                                                          ncols, gp);
   return mss_launch_status();

@@ -12,17 +12,14 @@
 // The contraction runs on the vector ALUs: DESIGN.md 3.12 holds the measurement behind that.
 #include "mss_common.h"
 #include "mss_point_sample.h"
-#include "../../include/mss_hip.h"
+#include "mss_m2f_maps.h"
 
 namespace {
 
 constexpr int MT_Q = 128;        // most queries (and targets) of a problem
 constexpr int MT_PT = 32;        // points staged in LDS at a time
 constexpr int MT_COLS = 16;      // target columns of a workgroup of launch 1: two halves of the workgroup x 8 accumulators
-constexpr int MT_MAXS = 16;      // most prediction steps of a call
 constexpr int MT_MAXCHUNKS = 16;
-
-struct MatchPtrs { const float* p[MT_MAXS]; };
 
 struct MatchPlan { int TP, NC, PC; long long stride; };
 
@@ -39,10 +36,10 @@ inline MatchPlan match_plan(int Q, int Tmax, int P) {
 
 // Launch 1. grid (NC, S*B, TP / 16), 256 threads. Thread (q = tid & 127, half = tid >> 7): samples x[q][p] for the points p of its
 // parity, then accumulates its 8 target columns over all 32 staged points.
-__global__ __launch_bounds__(256) void match_partial_kernel(MatchPtrs masks, long long bs, long long qs, long long ps, int h, int w,
-                                                             const uint8_t* __restrict__ tmask, const int* __restrict__ tstart, int total_t,
-                                                             int H, int W, const float* __restrict__ points, int B, int Q, int P, int Tmax,
+__global__ __launch_bounds__(256) void match_partial_kernel(MssM2fMaps maps, MssM2fTargets tg, const float* __restrict__ points, int P, int Tmax,
                                                              int TP, int NC, int PC, long long stride, float* __restrict__ ws) {
+  const long long bs = maps.img_stride, qs = maps.query_stride, ps = maps.pixel_stride;
+  const int B = maps.B, Q = maps.Q, h = maps.h, w = maps.w, total_t = tg.total_t, H = tg.H, W = tg.W;
   __shared__ float xs[MT_PT][MT_Q];
   __shared__ float sg[MT_PT][MT_Q];
   __shared__ __attribute__((aligned(16))) float ts[MT_PT][MT_COLS];
@@ -51,10 +48,10 @@ __global__ __launch_bounds__(256) void match_partial_kernel(MatchPtrs masks, lon
   __shared__ float red[2][256];
   const int tid = threadIdx.x, c = blockIdx.x, prob = blockIdx.y, m0 = blockIdx.z * MT_COLS;
   const int s = prob / B, b = prob - s * B;
-  const int t0 = tstart[b], t1 = tstart[b + 1], Tb = t1 - t0;
+  const int t0 = tg.tstart[b], t1 = tg.tstart[b + 1], Tb = t1 - t0;
   if (t0 < 0 || Tb < 0 || t1 > total_t || Tb > Tmax || m0 >= Tb) return;      // a bad range is reported by launch 2 (status 1)
   const int q = tid & (MT_Q - 1), half = tid >> 7;
-  const float* mq = masks.p[s] + (long long)b * bs + (long long)q * qs;
+  const float* mq = maps.step[s] + (long long)b * bs + (long long)q * qs;
   const int pbeg = c * PC < P ? c * PC : P, pend = pbeg + PC < P ? pbeg + PC : P;
   float ax[8], ag[8], neg_acc = 0.f, sig_acc = 0.f, t_acc = 0.f;
 #pragma unroll
@@ -92,7 +89,7 @@ __global__ __launch_bounds__(256) void match_partial_kernel(MatchPtrs masks, lon
     for (int i = tid; i < MT_PT * MT_COLS; i += 256) {
       const int m = i & (MT_COLS - 1), p = i >> 4;
       float t = 0.f;
-      if (m0 + m < Tb && valid[p]) t = bilinear_zero(tmask + (long long)(t0 + m0 + m) * H * W, 1, H, W, ttap[p]);
+      if (m0 + m < Tb && valid[p]) t = bilinear_zero(tg.tmask + (long long)(t0 + m0 + m) * H * W, 1, H, W, ttap[p]);
       ts[p][m] = t;
     }
     __syncthreads();
@@ -150,9 +147,8 @@ __device__ __forceinline__ int bcast_i(int a0, int a1, int idx) { return __shfl(
 // Then wave 0 solves T_b rows (targets) x Q columns (queries); lane l owns columns l, l + 64 and rows l, l + 64 in registers.
 // Every loop is bounded by T_b or Q; a cost that is NaN or -inf, or a row without a finite column, ends the problem with status 1.
 template <bool MERGE>
-__global__ __launch_bounds__(256) void match_solve_kernel(const float* __restrict__ ws, MatchPtrs cls, const int* __restrict__ labels,
-                                                           const int* __restrict__ tstart, const int* __restrict__ tcount, int total_t, int B,
-                                                           int Q, int C1, int P, int Tmax, int TP, int NC, long long stride, float w_class,
+__global__ __launch_bounds__(256) void match_solve_kernel(const float* __restrict__ ws, MssM2fSteps cls, MssM2fTargets tg, const int* __restrict__ tcount,
+                                                           int B, int Q, int C1, int P, int Tmax, int TP, int NC, long long stride, float w_class,
                                                            float w_mask, float w_dice, float* __restrict__ cost, int* __restrict__ match,
                                                            int* __restrict__ status) {
   __shared__ float cs[MT_Q * MT_Q];        // C transposed: [T_b][Q]
@@ -161,10 +157,10 @@ __global__ __launch_bounds__(256) void match_solve_kernel(const float* __restric
   int t0 = 0, Tb;
   bool bad;
   if (MERGE) {
-    t0 = tstart[b];
-    const int t1 = tstart[b + 1];
+    t0 = tg.tstart[b];
+    const int t1 = tg.tstart[b + 1];
     Tb = t1 - t0;
-    bad = t0 < 0 || Tb < 0 || t1 > total_t;
+    bad = t0 < 0 || Tb < 0 || t1 > tg.total_t;
   } else {
     Tb = tcount[b];
     bad = Tb < 0;
@@ -174,7 +170,7 @@ __global__ __launch_bounds__(256) void match_solve_kernel(const float* __restric
   float* cp = cost + (long long)prob * Q * Tmax;
   if (MERGE) {
     const float* wp = ws + (long long)prob * NC * stride;
-    const float* lg = cls.p[s] + (long long)b * Q * C1;
+    const float* lg = cls.step[s] + (long long)b * Q * C1;
     const long long QT = (long long)Q * TP;
     for (int idx = tid; idx < Q * Tmax; idx += 256) {
       const int q = idx / Tmax, m = idx - q * Tmax;
@@ -191,7 +187,7 @@ __global__ __launch_bounds__(256) void match_solve_kernel(const float* __restric
         }
         const double cmask = (ng - xt) / (double)P;
         const double cdice = 1. - (2. * st + 1.) / (sm + tm + 1.);
-        const int lab = labels[t0 + m];
+        const int lab = tg.labels[t0 + m];
         double cclass = __builtin_nan("");             // a label outside the class range ends the problem with status 1
         if (lab >= 0 && lab < C1) {
           float mx = lg[q * C1];
@@ -302,7 +298,7 @@ __global__ __launch_bounds__(256) void match_solve_kernel(const float* __restric
   if (lane == 0) status[prob] = fail;
 }
 
-bool match_shape_ok(int S, int B, int Q, int Tmax) { return S >= 1 && S <= MT_MAXS && B >= 1 && Q >= 1 && Q <= MT_Q && Tmax >= 1 && Tmax <= MT_Q; }
+bool match_shape_ok(int S, int B, int Q, int Tmax) { return m2f_steps_ok(S) && B >= 1 && Q >= 1 && Q <= MT_Q && Tmax >= 1 && Tmax <= MT_Q; }
 
 }  // namespace
 
@@ -312,28 +308,24 @@ extern "C" long long mss_m2f_match_workspace_bytes(int S, int B, int Q, int Tmax
   return 4ll * S * B * pl.NC * pl.stride;
 }
 
-extern "C" int mss_m2f_match_cost_f32(const float* const* masks_host, long long img_stride, long long query_stride, long long pixel_stride,
-                                      int h, int w, const float* const* cls_host, const uint8_t* tmask, const int* tstart,
-                                      const int* labels, int total_t, int H, int W, const float* points, int S, int B, int Q, int C1,
-                                      int P, int Tmax, float w_class, float w_mask, float w_dice, float* ws, float* cost, int* match,
-                                      int* status, void* stream) {
-  if (!masks_host || !cls_host || !tstart || !points || !ws || !cost || (match == nullptr) != (status == nullptr)) return MSS_ERR_BAD_ARG;
-  if (S < 1 || B < 1 || Q < 1 || Tmax < 1 || P < 1 || C1 < 1 || h < 1 || w < 1 || H < 1 || W < 1 || total_t < 0) return MSS_ERR_BAD_ARG;
-  if (img_stride < 0 || query_stride < 0 || pixel_stride < 0 || (total_t > 0 && (!tmask || !labels))) return MSS_ERR_BAD_ARG;
+extern "C" int mss_m2f_match_cost_f32(const MssM2fMaps* maps, const MssM2fSteps* cls, const MssM2fTargets* targets, const float* points, int C1,
+                                      int P, int Tmax, float w_class, float w_mask, float w_dice, float* ws, float* cost, int* match, int* status,
+                                      void* stream) {
+  if (!maps || !cls || !targets || !targets->tstart || !points || !ws || !cost || (match == nullptr) != (status == nullptr)) return MSS_ERR_BAD_ARG;
+  MssM2fMaps m = *maps;
+  const MssM2fTargets tg = *targets;
+  const int S = m.S, B = m.B, Q = m.Q;
+  if (S < 1 || B < 1 || Q < 1 || Tmax < 1 || P < 1 || C1 < 1 || m.h < 1 || m.w < 1 || tg.H < 1 || tg.W < 1 || tg.total_t < 0) return MSS_ERR_BAD_ARG;
+  if (m.img_stride < 0 || m.query_stride < 0 || m.pixel_stride < 0 || (tg.total_t > 0 && (!tg.tmask || !tg.labels))) return MSS_ERR_BAD_ARG;
   if (!match_shape_ok(S, B, Q, Tmax) || (long long)S * B > 65535) return MSS_ERR_UNSUPPORTED;
-  MatchPtrs mp = {}, cp = {};
-  for (int s = 0; s < S; ++s) {
-    if (!masks_host[s] || !cls_host[s]) return MSS_ERR_BAD_ARG;
-    mp.p[s] = masks_host[s];
-    cp.p[s] = cls_host[s];
-  }
+  MssM2fSteps cp;
+  if (!m2f_fill(m.step, maps->step, S) || !m2f_fill(cp.step, cls->step, S)) return MSS_ERR_BAD_ARG;
   const MatchPlan pl = match_plan(Q, Tmax, P);
   hipStream_t st = (hipStream_t)stream;
-  if (total_t > 0)
-    match_partial_kernel<<<dim3(pl.NC, S * B, pl.TP / MT_COLS), 256, 0, st>>>(mp, img_stride, query_stride, pixel_stride, h, w, tmask, tstart, total_t,
-                                                                                H, W, points, B, Q, P, Tmax, pl.TP, pl.NC, pl.PC, pl.stride, ws);
-  match_solve_kernel<true><<<S * B, 256, 0, st>>>(ws, cp, labels, tstart, nullptr, total_t, B, Q, C1, P, Tmax, pl.TP, pl.NC, pl.stride, w_class, w_mask,
-                                                   w_dice, cost, match, status);
+  if (tg.total_t > 0)
+    match_partial_kernel<<<dim3(pl.NC, S * B, pl.TP / MT_COLS), 256, 0, st>>>(m, tg, points, P, Tmax, pl.TP, pl.NC, pl.PC, pl.stride, ws);
+  match_solve_kernel<true><<<S * B, 256, 0, st>>>(ws, cp, tg, nullptr, B, Q, C1, P, Tmax, pl.TP, pl.NC, pl.stride, w_class, w_mask, w_dice, cost, match,
+                                                   status);
   return mss_launch_status();
 }
 
@@ -341,7 +333,7 @@ extern "C" int mss_m2f_match_assign_f32(const float* cost, const int* tcount, in
                                         void* stream) {
   if (!cost || !tcount || !match || !status || S < 1 || B < 1 || Q < 1 || Tmax < 1) return MSS_ERR_BAD_ARG;
   if (Q > MT_Q || Tmax > MT_Q) return MSS_ERR_UNSUPPORTED;
-  match_solve_kernel<false><<<S * B, 256, 0, (hipStream_t)stream>>>(nullptr, MatchPtrs{}, nullptr, nullptr, tcount, 0, B, Q, 1, 1, Tmax, 0, 0, 0, 0.f, 0.f,
-                                                                    0.f, const_cast<float*>(cost), match, status);
+  match_solve_kernel<false><<<S * B, 256, 0, (hipStream_t)stream>>>(nullptr, MssM2fSteps{}, MssM2fTargets{}, tcount, B, Q, 1, 1, Tmax, 0, 0, 0, 0.f, 0.f, 0.f,
+                                                                    const_cast<float*>(cost), match, status);
   return mss_launch_status();
 }

@@ -1153,8 +1153,7 @@ def m2f_attn_mask_bits(mask_logits_nhwc, Q, size):
     queries, and per query the "some key is allowed" bits (include/mss_hip.h). Both live in one float32-typed buffer."""
     B, hm, wm, ldq = mask_logits_nhwc.shape
     h, w = size
-    if not mask_logits_nhwc.is_cuda or mask_logits_nhwc.dtype != torch.float32:
-        raise RuntimeError("m2f_attn_mask_bits runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    _need_f32_cuda("m2f_attn_mask_bits", mask_logits_nhwc)
     lg = mask_logits_nhwc.contiguous()
     W = (Q + 31) // 32
     words = torch.empty(B * 2 * (h * w + 1) * W, device=lg.device, dtype=torch.float32).view(torch.int32)
@@ -1168,34 +1167,6 @@ def m2f_attn_chunks(B, A, NK):
     """Pieces the key range is cut into so that 8 heads x A attentions x B images x pieces is ~2048 workgroups (two waves each:
     ~4 waves per SIMD of the 256 CUs), never less than 64 keys a piece."""
     return max(1, min(-(-NK // 64), 2048 // (8 * A * B)))
-
-
-def m2f_masked_attention(q, k, v, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, out=None, scale=None, ws=None):
-    """softmax(scale q k^T + mask) v for 8 heads of 32 channels and A attentions side by side: q [B*Q, >= A*256], k / v
-    [B*NK, >= A*256] (row-major 2-d, attention a in columns a*256 ...), -> out [B*Q, A*256]. bits / allowed: from
-    m2f_attn_mask_bits (or [B, A, NK, W] / [B, A, W] int32 made by hand); None = no mask. chunks: pieces of the key range
-    (default m2f_attn_chunks); ws: the float32 chunk workspace (allocated here when None; its contents do not matter)."""
-    for t in (q, k, v):
-        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-            raise RuntimeError("m2f_masked_attention takes row-major 2-d float32 CUDA tensors (there is no CPU path)")
-    if q.shape[0] != B * Q or k.shape[0] != B * NK or v.shape[0] != B * NK:
-        raise ValueError(f"rows {q.shape[0]} / {k.shape[0]} / {v.shape[0]} do not match B {B}, Q {Q}, NK {NK}")
-    if (bits is None) != (allowed is None):
-        raise ValueError("bits and allowed come together")
-    if bits is not None:
-        W = (Q + 31) // 32
-        if tuple(bits.shape) != (B, A, NK, W) or tuple(allowed.shape) != (B, A, W) or not bits.is_contiguous() or not allowed.is_contiguous() \
-                or bits.dtype != torch.int32 or allowed.dtype != torch.int32:
-            raise ValueError(f"bits {tuple(bits.shape)} / allowed {tuple(allowed.shape)} must be contiguous int32 [{B}, {A}, {NK}, {W}] / [{B}, {A}, {W}]")
-    if chunks is None:
-        chunks = m2f_attn_chunks(B, A, NK)
-    if out is None:
-        out = torch.empty((B * Q, A * 256), device=q.device, dtype=torch.float32)
-    if ws is None and chunks > 1:
-        ws = torch.empty(_lib.value("mss_m2f_attn_workspace_bytes", B, Q, A, chunks) // 4, device=q.device, dtype=torch.float32)
-    call("mss_m2f_masked_attention_f32", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(bits), ptr(allowed),
-         B, Q, NK, A, float(scale if scale is not None else 32 ** -0.5), chunks, ptr(ws), ptr(out), out.stride(0))
-    return out
 
 
 def _attn_check(name, q, k, v, B, Q, NK, A, bits, allowed):
@@ -1213,21 +1184,38 @@ def _attn_check(name, q, k, v, B, Q, NK, A, bits, allowed):
             raise ValueError(f"bits {tuple(bits.shape)} / allowed {tuple(allowed.shape)} must be contiguous int32 [{B}, {A}, {NK}, {W}] / [{B}, {A}, {W}]")
 
 
-def m2f_masked_attention_lse(q, k, v, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, out=None, scale=None, ws=None):
-    """m2f_masked_attention for training: the same kernels (`out` has the same bits for the same arguments and chunk count) ->
-    (out [B*Q, A*256], lse [B, A, 8, Q]); lse is the log-sum-exp of the scaled, masked scores in the log2 domain
-    (include/mss_hip.h), which m2f_masked_attention_backward takes."""
-    _attn_check("m2f_masked_attention_lse", q, k, v, B, Q, NK, A, bits, allowed)
+def _attn_forward(name, want_lse, q, k, v, B, Q, NK, A, bits, allowed, chunks, out, scale, ws):
+    """The forward of m2f_masked_attention (want_lse False -> (out, None)) and m2f_masked_attention_lse (-> (out, lse))."""
+    _attn_check(name, q, k, v, B, Q, NK, A, bits, allowed)
     if chunks is None:
         chunks = m2f_attn_chunks(B, A, NK)
     if out is None:
         out = torch.empty((B * Q, A * 256), device=q.device, dtype=torch.float32)
-    lse = torch.empty((B, A, 8, Q), device=q.device, dtype=torch.float32)
+    lse = torch.empty((B, A, 8, Q), device=q.device, dtype=torch.float32) if want_lse else None
     if ws is None and chunks > 1:
         ws = torch.empty(_lib.value("mss_m2f_attn_workspace_bytes", B, Q, A, chunks) // 4, device=q.device, dtype=torch.float32)
-    call("mss_m2f_masked_attention_lse_f32", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(bits), ptr(allowed),
-         B, Q, NK, A, float(scale if scale is not None else 32 ** -0.5), chunks, ptr(ws), ptr(out), out.stride(0), ptr(lse))
+    args = (ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(bits), ptr(allowed), B, Q, NK, A,
+            float(scale if scale is not None else 32 ** -0.5), chunks, ptr(ws), ptr(out), out.stride(0))
+    if want_lse:
+        call("mss_m2f_masked_attention_lse_f32", *args, ptr(lse))
+    else:
+        call("mss_m2f_masked_attention_f32", *args)
     return out, lse
+
+
+def m2f_masked_attention(q, k, v, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, out=None, scale=None, ws=None):
+    """softmax(scale q k^T + mask) v for 8 heads of 32 channels and A attentions side by side: q [B*Q, >= A*256], k / v
+    [B*NK, >= A*256] (row-major 2-d, attention a in columns a*256 ...), -> out [B*Q, A*256]. bits / allowed: from
+    m2f_attn_mask_bits (or [B, A, NK, W] / [B, A, W] int32 made by hand); None = no mask. chunks: pieces of the key range
+    (default m2f_attn_chunks); ws: the float32 chunk workspace (allocated here when None; its contents do not matter)."""
+    return _attn_forward("m2f_masked_attention", False, q, k, v, B, Q, NK, A, bits, allowed, chunks, out, scale, ws)[0]
+
+
+def m2f_masked_attention_lse(q, k, v, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, out=None, scale=None, ws=None):
+    """m2f_masked_attention for training: the same kernels (`out` has the same bits for the same arguments and chunk count) ->
+    (out [B*Q, A*256], lse [B, A, 8, Q]); lse is the log-sum-exp of the scaled, masked scores in the log2 domain
+    (include/mss_hip.h), which m2f_masked_attention_backward takes."""
+    return _attn_forward("m2f_masked_attention_lse", True, q, k, v, B, Q, NK, A, bits, allowed, chunks, out, scale, ws)
 
 
 def m2f_masked_attention_backward(q, k, v, out, lse, dout, B, Q, NK, A=1, bits=None, allowed=None, chunks=None, scale=None, ws=None,
@@ -1378,6 +1366,75 @@ def m2f_score_fused(class_logits, mask_logits_nhwc, image_size, size=None):
     return out
 
 
+# ---- what the Mask2Former matcher, criterion and class mix share -----------------------------------------------------------------
+def _need_f32_cuda(name, *tensors):
+    for t in tensors:
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+
+
+def _steps(tensors):
+    """One tensor (= one prediction step) or a list of them -> list."""
+    return [tensors] if isinstance(tensors, torch.Tensor) else list(tensors)
+
+
+def _m2f_table(table, tensors):
+    """Fill a 16-slot per-step pointer table of include/mss_hip.h (MssM2fMaps / MssM2fSteps / MssM2fGrads) from contiguous tensors,
+    which the caller keeps alive. A longer list fills the 16 slots only: the entry point refuses its S (MSS_ERR_UNSUPPORTED)."""
+    for s, t in enumerate(tensors[:_lib.MSS_M2F_MAX_STEPS]):
+        table.step[s] = t.data_ptr()
+    return table
+
+
+def _m2f_layout(name, shape, pixel_major, Q):
+    """Shape of mask logits, NCHW [B,Q,h,w] or with pixel_major [B,h,w,ldq] (Q <= ldq, default ldq) -> ((image, query, pixel) strides
+    in floats, B, Q, h, w, ldq)."""
+    if pixel_major:
+        B, h, w, ldq = shape
+        strides = (h * w * ldq, 1, ldq)
+    else:
+        B, ldq, h, w = shape
+        strides = (h * w * ldq, h * w, 1)
+    Q = ldq if Q is None else int(Q)
+    if Q < 1 or Q > ldq or (not pixel_major and Q != ldq):
+        raise ValueError(f"{name}: Q {Q} does not fit mask logits {tuple(shape)}")
+    return strides, B, Q, h, w, ldq
+
+
+def _m2f_maps(name, mask_logits, pixel_major, Q):
+    """The mask logits of the S prediction steps of a call -> (a filled MssM2fMaps, the contiguous tensors its pointers belong to)."""
+    masks = _steps(mask_logits)
+    _need_f32_cuda(name, *masks)
+    masks = [m.contiguous() for m in masks]
+    if masks[0].dim() != 4 or any(m.shape != masks[0].shape for m in masks):
+        raise ValueError(f"{name}: the mask logits of all steps share one 4-d shape, got {[tuple(m.shape) for m in masks]}")
+    strides, B, Q, h, w, _ = _m2f_layout(name, masks[0].shape, pixel_major, Q)
+    mp = _lib.MssM2fMaps(img_stride=strides[0], query_stride=strides[1], pixel_stride=strides[2], S=len(masks), B=B, Q=Q, h=h, w=w)
+    return _m2f_table(mp, masks), masks
+
+
+def _m2f_targets(name, S, B, tstart, tmask=None, labels=None, match=None, more=()):
+    """The target pack of a call -- tmask uint8 [sum T,H,W] and / or labels int32 [sum T], tstart int32 [B+1] -- and, where the call
+    has one, the matcher's table match int32 [S,B,Tmax] -> (a filled MssM2fTargets, the contiguous tensors its pointers belong to,
+    match contiguous). `more`: further tensors of the call that only have to be on the device."""
+    ints = [t for t in (tstart, labels, match) if t is not None]
+    for t in ([] if tmask is None else [tmask]) + ints + list(more):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on an MI355X only (CUDA tensors); there is no CPU path")
+    if (tmask is not None and tmask.dtype != torch.uint8) or any(t.dtype != torch.int32 for t in ints):
+        raise RuntimeError(f"{name} takes uint8 target masks and int32 tstart / labels / match on the device")
+    total_t = labels.numel() if tmask is None else tmask.shape[0]
+    if (tmask is not None and tmask.dim() != 3) or tstart.numel() != B + 1 or (labels is not None and labels.numel() != total_t) \
+            or (match is not None and (match.dim() != 3 or tuple(match.shape[:2]) != (S, B) or match.shape[2] < 1)):
+        raise ValueError(f"{name}: tmask {None if tmask is None else tuple(tmask.shape)} / tstart {tuple(tstart.shape)} / labels "
+                         f"{None if labels is None else tuple(labels.shape)} / match {None if match is None else tuple(match.shape)} "
+                         f"do not match S {S}, B {B}")
+    H, W = (0, 0) if tmask is None else tmask.shape[1:]
+    keep = tuple(None if t is None else t.contiguous() for t in (tmask, tstart, labels))
+    tg = _lib.MssM2fTargets(ptr(keep[0]) if total_t else None, ptr(keep[1]), ptr(keep[2]) if total_t else None, total_t, H, W)
+    return tg, keep, None if match is None else match.contiguous()
+
+
 # ---- Hungarian matching of Mask2Former (csrc/m2f_match.hip) ---------------------------------------------------------------------
 def _match_ints(S, B, Tmax, device):
     """match [S,B,Tmax] and status [S,B] as views of ONE int32 buffer (one device-to-host copy brings both), pre-filled: integer
@@ -1394,33 +1451,20 @@ def m2f_match_cost(mask_logits, class_logits, tmask, tstart, labels, point_coord
     point_coords [S,B,P,2] (x, y) in [0,1); weights = (cost_class, cost_mask, cost_dice); Tmax >= max T_b (host int, default
     sum T). -> cost [S,B,Q,Tmax] fp32 (columns >= T_b are 0); with solve also (match [S,B,Tmax], status [S,B], their shared
     int32 buffer) from the same second launch."""
-    masks = [mask_logits] if isinstance(mask_logits, torch.Tensor) else list(mask_logits)
-    clss = [class_logits] if isinstance(class_logits, torch.Tensor) else list(class_logits)
-    for t in masks + clss + [point_coords]:
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError("m2f_match_cost runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
-    if not (tmask.is_cuda and tstart.is_cuda and labels.is_cuda) or tmask.dtype != torch.uint8 or tstart.dtype != torch.int32 \
-            or labels.dtype != torch.int32:
-        raise RuntimeError("m2f_match_cost takes uint8 target masks and int32 tstart / labels on the device")
-    S = len(masks)
+    name = "m2f_match_cost"
+    clss = _steps(class_logits)
+    _need_f32_cuda(name, *clss, point_coords)
     B, Q, C1 = clss[0].shape
-    masks = [m.contiguous() for m in masks]
+    mp, masks = _m2f_maps(name, mask_logits, pixel_major, Q)
+    tg, keep, _ = _m2f_targets(name, len(clss), B, tstart, tmask=tmask, labels=labels)
+    S = len(masks)
     clss = [c.contiguous() for c in clss]
-    if pixel_major:
-        _, h, w, ldq = masks[0].shape
-        strides = (h * w * ldq, 1, ldq)
-    else:
-        _, ldq, h, w = masks[0].shape
-        strides = (h * w * ldq, h * w, 1)
-    if len(clss) != S or ldq < Q or (not pixel_major and ldq != Q) or any(m.shape != masks[0].shape or m.shape[0] != B for m in masks) \
-            or any(c.shape != clss[0].shape for c in clss):
+    if len(clss) != S or masks[0].shape[0] != B or any(c.shape != clss[0].shape for c in clss):
         raise ValueError(f"{S} mask logits {tuple(masks[0].shape)} do not match {len(clss)} class logits {tuple(clss[0].shape)}")
-    total_t, H, W = tmask.shape
     P = point_coords.shape[2]
-    if tuple(point_coords.shape) != (S, B, P, 2) or tstart.numel() != B + 1 or labels.numel() != total_t:
-        raise ValueError(f"point_coords {tuple(point_coords.shape)} / tstart {tuple(tstart.shape)} / labels {tuple(labels.shape)} "
-                         f"do not match S {S}, B {B}, sum T {total_t}")
-    Tmax = max(1, total_t if Tmax is None else int(Tmax))
+    if tuple(point_coords.shape) != (S, B, P, 2):
+        raise ValueError(f"point_coords {tuple(point_coords.shape)} does not match S {S}, B {B}")
+    Tmax = max(1, tg.total_t if Tmax is None else int(Tmax))
     dev = clss[0].device
     nbytes = _lib.value("mss_m2f_match_workspace_bytes", S, B, Q, Tmax, P)
     if nbytes <= 0:
@@ -1430,12 +1474,9 @@ def m2f_match_cost(mask_logits, class_logits, tmask, tstart, labels, point_coord
     buf = match = status = None
     if solve:
         buf, match, status = _match_ints(S, B, Tmax, dev)
-    mp = (ctypes.c_void_p * S)(*[m.data_ptr() for m in masks])
-    cp = (ctypes.c_void_p * S)(*[c.data_ptr() for c in clss])
-    pts, tm, lb = point_coords.contiguous(), tmask.contiguous(), labels.contiguous()
-    call("mss_m2f_match_cost_f32", mp, strides[0], strides[1], strides[2], h, w, cp, ptr(tm) if total_t else None, ptr(tstart.contiguous()),
-         ptr(lb) if total_t else None, total_t, H, W, ptr(pts), S, B, Q, C1, P, Tmax, float(weights[0]), float(weights[1]), float(weights[2]),
-         ptr(ws), ptr(cost), ptr(match), ptr(status))
+    pts = point_coords.contiguous()
+    call("mss_m2f_match_cost_f32", ctypes.byref(mp), ctypes.byref(_m2f_table(_lib.MssM2fSteps(), clss)), ctypes.byref(tg), ptr(pts), C1, P, Tmax,
+         float(weights[0]), float(weights[1]), float(weights[2]), ptr(ws), ptr(cost), ptr(match), ptr(status))
     return (cost, match, status, buf) if solve else cost
 
 
@@ -1459,41 +1500,6 @@ def m2f_match_assign(cost, tcount):
 
 # ---- SetCriterion of Mask2Former: class and sampled-mask losses (csrc/m2f_loss.hip) -----------------------------------------------
 _LOSS_MODES = {"uncertain": 1, "clean": 2}
-
-
-def _loss_maps(name, mask_logits, pixel_major, Q):
-    """The S mask-logit tensors of a call -> (contiguous list, host pointer array, (image, query, pixel) strides, h, w, Q)."""
-    masks = [mask_logits] if isinstance(mask_logits, torch.Tensor) else list(mask_logits)
-    for t in masks:
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
-    masks = [m.contiguous() for m in masks]
-    if masks[0].dim() != 4 or any(m.shape != masks[0].shape for m in masks):
-        raise ValueError(f"{name}: the mask logits of all steps share one 4-d shape, got {[tuple(m.shape) for m in masks]}")
-    if pixel_major:
-        _, h, w, ldq = masks[0].shape
-        strides = (h * w * ldq, 1, ldq)
-        Q = ldq if Q is None else int(Q)
-    else:
-        _, ldq, h, w = masks[0].shape
-        strides = (h * w * ldq, h * w, 1)
-        Q = ldq if Q is None else int(Q)
-    if Q < 1 or Q > ldq or (not pixel_major and Q != ldq):
-        raise ValueError(f"{name}: Q {Q} does not fit mask logits {tuple(masks[0].shape)}")
-    return masks, (ctypes.c_void_p * len(masks))(*[m.data_ptr() for m in masks]), strides, h, w, Q
-
-
-def _loss_table(name, S, B, tmask, tstart, match, *more):
-    """Checks of the target pack and the [S,B,Tmax] match table shared by the wrappers below -> (total_t, H, W, Tmax)."""
-    for t in (tmask, tstart, match) + more:
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} runs on an MI355X only (CUDA tensors); there is no CPU path")
-    if tmask.dtype != torch.uint8 or tstart.dtype != torch.int32 or match.dtype != torch.int32:
-        raise RuntimeError(f"{name} takes uint8 target masks and an int32 tstart / match table on the device")
-    if tmask.dim() != 3 or match.dim() != 3 or tuple(match.shape[:2]) != (S, B) or tstart.numel() != B + 1 or match.shape[2] < 1:
-        raise ValueError(f"{name}: tmask {tuple(tmask.shape)} / tstart {tuple(tstart.shape)} / match {tuple(match.shape)} do not match S {S}, B {B}")
-    total_t, H, W = tmask.shape
-    return total_t, H, W, match.shape[2]
 
 
 def _loss_ws(R, K, P, device):
@@ -1522,13 +1528,10 @@ def m2f_point_select(mask_logits, tmask, tstart, match, candidates, random_point
     ranks last -- followed by the first num_points - k of random_points [S * sum T, Pr, 2]; a row before sel_start takes its
     first num_points random points. -> points [S * sum T, num_points, 2]; all 0 for a row whose table entry is -1."""
     name = "m2f_point_select"
-    masks, mp, strides, h, w, Q = _loss_maps(name, mask_logits, pixel_major, Q)
-    S, B = len(masks), masks[0].shape[0]
-    floats = [t for t in (candidates, random_points) if t is not None]
-    for t in floats:
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
-    total_t, H, W, Tmax = _loss_table(name, S, B, tmask, tstart, match)
+    mp, masks = _m2f_maps(name, mask_logits, pixel_major, Q)
+    _need_f32_cuda(name, *[t for t in (candidates, random_points) if t is not None])
+    tg, keep, mt = _m2f_targets(name, mp.S, mp.B, tstart, tmask=tmask, match=match)
+    S, total_t = mp.S, tg.total_t
     P, k, sel_start = int(num_points), int(k), int(sel_start)
     if mode not in _LOSS_MODES:
         raise ValueError(f"{name}: mode {mode!r} is not one of {sorted(_LOSS_MODES)}")
@@ -1551,9 +1554,8 @@ def m2f_point_select(mask_logits, tmask, tstart, match, candidates, random_point
     ws = _loss_ws(R, K, P, dev)
     cand = candidates.contiguous() if k > 0 else None
     rnd = random_points.contiguous() if random_points is not None else None
-    call("mss_m2f_loss_select_f32", mp, strides[0], strides[1], strides[2], h, w, ptr(tmask.contiguous()), ptr(tstart.contiguous()),
-         ptr(match.contiguous()), total_t, H, W, ptr(cand), ptr(rnd), S, B, Q, Tmax, K, k, P, Pr, _LOSS_MODES[mode], sel_start, ptr(ws),
-         ptr(points))
+    call("mss_m2f_loss_select_f32", ctypes.byref(mp), ctypes.byref(tg), ptr(mt), ptr(cand), ptr(rnd), mt.shape[2], K, k, P, Pr, _LOSS_MODES[mode],
+         sel_start, ptr(ws), ptr(points))
     return points
 
 
@@ -1562,15 +1564,14 @@ def m2f_mask_loss(mask_logits, tmask, tstart, match, points, pixel_major=False, 
     points [S * sum T, P, 2]: -> rows [S * sum T, 4] float64 = sum_p BCEWithLogits(x, t), sum_p sigmoid(x) t, sum_p sigmoid(x),
     sum_p t (NaN for a row whose table entry is -1), x / t = the source / target map sampled bilinearly. One launch, one order."""
     name = "m2f_mask_loss"
-    masks, mp, strides, h, w, Q = _loss_maps(name, mask_logits, pixel_major, Q)
-    S, B = len(masks), masks[0].shape[0]
-    total_t, H, W, Tmax = _loss_table(name, S, B, tmask, tstart, match, points)
-    R = S * total_t
+    mp, masks = _m2f_maps(name, mask_logits, pixel_major, Q)
+    tg, keep, mt = _m2f_targets(name, mp.S, mp.B, tstart, tmask=tmask, match=match, more=(points,))
+    R = mp.S * tg.total_t
     if points.dtype != torch.float32 or points.dim() != 3 or points.shape[0] != R or points.shape[2] != 2 or points.shape[1] < 1:
         raise ValueError(f"{name}: points {tuple(points.shape)} {points.dtype} for {R} rows")
     rows = torch.empty((R, 4), device=masks[0].device, dtype=torch.float64)
-    call("mss_m2f_loss_mask_forward_f32", mp, strides[0], strides[1], strides[2], h, w, ptr(tmask.contiguous()), ptr(tstart.contiguous()),
-         ptr(match.contiguous()), total_t, H, W, ptr(points.contiguous()), S, B, Q, Tmax, points.shape[1], ptr(rows))
+    call("mss_m2f_loss_mask_forward_f32", ctypes.byref(mp), ctypes.byref(tg), ptr(mt), ptr(points.contiguous()), mt.shape[2], points.shape[1],
+         ptr(rows))
     return rows
 
 
@@ -1583,22 +1584,17 @@ def m2f_label_loss(class_logits, labels, tstart, match, weight, rows, num_points
     int32 (target_classes), bad [S] int32 (1: a table entry of -1 or a label outside the classes; the step's losses are NaN) and
     wsum [S] float64 (sum of the class weights): what m2f_label_loss_backward / m2f_mask_loss_backward take."""
     name = "m2f_label_loss"
-    clss = [class_logits] if isinstance(class_logits, torch.Tensor) else list(class_logits)
-    for t in clss + [weight]:
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
-    for t in (labels, tstart, match):
-        if not t.is_cuda or t.dtype != torch.int32:
-            raise RuntimeError(f"{name} takes int32 labels / tstart / match on the device")
+    clss = _steps(class_logits)
+    _need_f32_cuda(name, *clss, weight)
     clss = [c.contiguous() for c in clss]
     S = len(clss)
     if clss[0].dim() != 3 or any(c.shape != clss[0].shape for c in clss):
         raise ValueError(f"{name}: the class logits of all steps share one [B,Q,C+1] shape, got {[tuple(c.shape) for c in clss]}")
     B, Q, C1 = clss[0].shape
-    total_t = labels.numel()
-    if match.dim() != 3 or tuple(match.shape[:2]) != (S, B) or tstart.numel() != B + 1 or weight.numel() != C1 or C1 < 2:
-        raise ValueError(f"{name}: match {tuple(match.shape)} / tstart {tuple(tstart.shape)} / weight {tuple(weight.shape)} do not match "
-                         f"S {S}, B {B}, C+1 {C1}")
+    tg, keep, mt = _m2f_targets(name, S, B, tstart, labels=labels, match=match)
+    total_t = tg.total_t
+    if weight.numel() != C1 or C1 < 2:
+        raise ValueError(f"{name}: weight {tuple(weight.shape)} does not match C+1 {C1}")
     split, scale0, scale1, ncols = _loss_groups(name, scales, split, total_t)
     dev = clss[0].device
     if rows is None:
@@ -1610,10 +1606,9 @@ def m2f_label_loss(class_logits, labels, tstart, match, weight, rows, num_points
     bad = torch.zeros((S,), device=dev, dtype=torch.int32)
     wsum = torch.empty((S,), device=dev, dtype=torch.float64)
     loss = torch.empty((S, ncols), device=dev, dtype=torch.float32)
-    cp = (ctypes.c_void_p * S)(*[c.data_ptr() for c in clss])
-    call("mss_m2f_loss_finalize_f32", cp, ptr(labels.contiguous()) if total_t else None, ptr(tstart.contiguous()), ptr(match.contiguous()),
-         ptr(weight.contiguous()), ptr(rows.contiguous()) if total_t else None, total_t, S, B, Q, C1, match.shape[2], int(num_points), split,
-         scale0, scale1, ncols, ptr(tclass), ptr(bad), ptr(wsum), ptr(loss))
+    call("mss_m2f_loss_finalize_f32", ctypes.byref(_m2f_table(_lib.MssM2fSteps(), clss)), ctypes.byref(tg), ptr(mt), ptr(weight.contiguous()),
+         ptr(rows.contiguous()) if total_t else None, S, B, Q, C1, mt.shape[2], int(num_points), split, scale0, scale1, ncols, ptr(tclass), ptr(bad),
+         ptr(wsum), ptr(loss))
     return loss, tclass, bad, wsum
 
 
@@ -1623,9 +1618,10 @@ def m2f_mask_loss_backward(mask_logits, tmask, tstart, match, bad, points, rows,
     is written whole by its row's workgroup from an int64 fixed-point window (no float atomics: bit-reproducible), every other
     element -- unmatched queries, the padding columns of a pixel-major layout, the steps marked bad -- is 0."""
     name = "m2f_mask_loss_backward"
-    masks, mp, strides, h, w, Q = _loss_maps(name, mask_logits, pixel_major, Q)
-    S, B = len(masks), masks[0].shape[0]
-    total_t, H, W, Tmax = _loss_table(name, S, B, tmask, tstart, match, bad, points, rows, gloss)
+    mp, masks = _m2f_maps(name, mask_logits, pixel_major, Q)
+    S = mp.S
+    tg, keep, mt = _m2f_targets(name, S, mp.B, tstart, tmask=tmask, match=match, more=(bad, points, rows, gloss))
+    total_t = tg.total_t
     R = S * total_t
     split, scale0, scale1, ncols = _loss_groups(name, scales, split, total_t)
     if points.dtype != torch.float32 or points.dim() != 3 or points.shape[0] != R or points.shape[2] != 2 or points.shape[1] < 1 \
@@ -1637,10 +1633,9 @@ def m2f_mask_loss_backward(mask_logits, tmask, tstart, match, bad, points, rows,
     dev = masks[0].device
     grads = torch.zeros((S,) + tuple(masks[0].shape), device=dev, dtype=torch.float32)
     ws = _loss_ws(R, 0, P, dev)
-    gp = (ctypes.c_void_p * S)(*[grads[s].data_ptr() for s in range(S)])
-    call("mss_m2f_loss_mask_backward_f32", mp, strides[0], strides[1], strides[2], h, w, ptr(tmask.contiguous()), ptr(tstart.contiguous()),
-         ptr(match.contiguous()), ptr(bad.contiguous()), total_t, H, W, ptr(points.contiguous()), ptr(rows.contiguous()), ptr(gloss.contiguous()),
-         S, B, Q, Tmax, P, split, scale0, scale1, ncols, ptr(ws), gp)
+    call("mss_m2f_loss_mask_backward_f32", ctypes.byref(mp), ctypes.byref(tg), ptr(mt), ptr(bad.contiguous()), ptr(points.contiguous()),
+         ptr(rows.contiguous()), ptr(gloss.contiguous()), mt.shape[2], P, split, scale0, scale1, ncols, ptr(ws),
+         ctypes.byref(_m2f_table(_lib.MssM2fGrads(), list(grads))))
     return grads
 
 
@@ -1648,10 +1643,8 @@ def m2f_label_loss_backward(class_logits, tclass, bad, weight, wsum, gloss):
     """d loss_ce / d class_logits: -> [S,B,Q,C+1] = weight[c] / wsum (softmax - onehot) gloss[s,0] (0 for a step marked bad);
     tclass / bad / wsum from m2f_label_loss, gloss [S,ncols] the upstream gradient of its loss table."""
     name = "m2f_label_loss_backward"
-    clss = [class_logits] if isinstance(class_logits, torch.Tensor) else list(class_logits)
-    for t in clss + [weight, gloss]:
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    clss = _steps(class_logits)
+    _need_f32_cuda(name, *clss, weight, gloss)
     if not (tclass.is_cuda and bad.is_cuda and wsum.is_cuda):
         raise RuntimeError(f"{name} runs on an MI355X only (CUDA tensors); there is no CPU path")
     clss = [c.contiguous() for c in clss]
@@ -1663,10 +1656,9 @@ def m2f_label_loss_backward(class_logits, tclass, bad, weight, wsum, gloss):
         raise ValueError(f"{name}: tclass {tuple(tclass.shape)} / bad {tuple(bad.shape)} / wsum {tuple(wsum.shape)} / gloss {tuple(gloss.shape)} "
                          f"do not match {S} class logits {tuple(clss[0].shape)}")
     grads = torch.empty((S, B, Q, C1), device=clss[0].device, dtype=torch.float32)
-    cp = (ctypes.c_void_p * S)(*[c.data_ptr() for c in clss])
-    gp = (ctypes.c_void_p * S)(*[grads[s].data_ptr() for s in range(S)])
-    call("mss_m2f_loss_label_backward_f32", cp, ptr(tclass.contiguous()), ptr(bad.contiguous()), ptr(weight.contiguous()), ptr(wsum.contiguous()),
-         ptr(gloss.contiguous()), S, B, Q, C1, gloss.shape[1], gp)
+    call("mss_m2f_loss_label_backward_f32", ctypes.byref(_m2f_table(_lib.MssM2fSteps(), clss)), ptr(tclass.contiguous()), ptr(bad.contiguous()),
+         ptr(weight.contiguous()), ptr(wsum.contiguous()), ptr(gloss.contiguous()), S, B, Q, C1, gloss.shape[1],
+         ctypes.byref(_m2f_table(_lib.MssM2fGrads(), list(grads))))
     return grads
 
 
@@ -1679,35 +1671,23 @@ MIX_MAX_QUERIES, MIX_MAX_CLASSES = 128, 32
 def _mix_inputs(name, class_logits, mask_logits, pixel_major, Q):
     """Class logits [B,Q,C+1] and mask logits (NCHW [B,Q,h,w], or pixel-major [B,h,w,ldq]) -> (both contiguous, the (image,
     query, pixel) strides, B, Q, C, h, w)."""
-    for t in (class_logits, mask_logits):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    _need_f32_cuda(name, class_logits, mask_logits)
     cls, x = class_logits.contiguous(), mask_logits.contiguous()
     if cls.dim() != 3 or x.dim() != 4 or x.shape[0] != cls.shape[0]:
         raise ValueError(f"{name}: class logits {tuple(cls.shape)} / mask logits {tuple(x.shape)}")
     B, Qc, C1 = cls.shape
-    if pixel_major:
-        _, h, w, ldq = x.shape
-        strides = (h * w * ldq, 1, ldq)
-        Q = Qc if Q is None else int(Q)
-        if ldq % 4:
-            raise ValueError(f"{name}: the pitch {ldq} of pixel-major mask logits is no multiple of 4")
-    else:
-        _, ldq, h, w = x.shape
-        strides = (h * w * ldq, h * w, 1)
-        Q = ldq if Q is None else int(Q)
-        if Q != ldq:
-            raise ValueError(f"{name}: Q {Q} does not fit NCHW mask logits {tuple(x.shape)}")
+    strides, B, Q, h, w, ldq = _m2f_layout(name, x.shape, pixel_major, Qc if Q is None and pixel_major else Q)
+    if pixel_major and ldq % 4:
+        raise ValueError(f"{name}: the pitch {ldq} of pixel-major mask logits is no multiple of 4")
     C = C1 - 1
-    if Q != Qc or Q > ldq or not 1 <= Q <= MIX_MAX_QUERIES or not 1 <= C <= MIX_MAX_CLASSES or h < 1 or w < 1:
+    if Q != Qc or not 1 <= Q <= MIX_MAX_QUERIES or not 1 <= C <= MIX_MAX_CLASSES or h < 1 or w < 1:
         raise ValueError(f"{name}: {Qc} queries x {C} classes of class logits, Q {Q} of mask logits {tuple(x.shape)} "
                          f"(Q <= {MIX_MAX_QUERIES}, 1 <= C <= {MIX_MAX_CLASSES})")
     return cls, x, strides, B, Q, C, h, w
 
 
 def _mix_sizes(name, mix, size, crop):
-    if not mix.is_cuda or mix.dtype != torch.float32:
-        raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    _need_f32_cuda(name, mix)
     if mix.dim() != 4:
         raise ValueError(f"{name}: mix {tuple(mix.shape)} is not [B,C,h,w]")
     (H, W), (Ht, Wt) = (int(v) for v in size), (int(v) for v in (size if crop is None else crop))
@@ -1758,8 +1738,7 @@ def m2f_mix_upsample_backward(mix, size, crop=None, dlogits=None, dscore=None):
     for t, shape in ((dlogits, (B, Cl, Ht, Wt)), (dscore, (B, Ht, Wt))):
         if t is None:
             continue
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+        _need_f32_cuda(name, t)
         if tuple(t.shape) != shape:
             raise ValueError(f"{name}: an upstream gradient {tuple(t.shape)} where {shape} belongs")
     if dlogits is None and dscore is None:
@@ -1777,9 +1756,7 @@ def m2f_class_mix_backward(dmix, prob, class_logits, mask_logits, pixel_major=Fa
     sums folded in index order, no float atomics -- two runs give the same bits, and so do the two layouts."""
     name = "m2f_class_mix_backward"
     cls, x, strides, B, Q, C, h, w = _mix_inputs(name, class_logits, mask_logits, pixel_major, Q)
-    for t in (dmix, prob):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{name} runs on an MI355X only (float32 CUDA tensors); there is no CPU path")
+    _need_f32_cuda(name, dmix, prob)
     if tuple(dmix.shape) != (B, C, h, w) or tuple(prob.shape) != (B, Q, C):
         raise ValueError(f"{name}: dmix {tuple(dmix.shape)} / prob {tuple(prob.shape)} for B {B}, Q {Q}, C {C}, {h} x {w}")
     chunks = _lib.value("mss_m2f_mix_backward_chunks", h * w)

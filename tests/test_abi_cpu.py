@@ -59,14 +59,119 @@ def test_msda_binned_workspace_query_is_host_only(lib):
     assert q([(0, 5)], 1, 8, 32, 10, 4) == 0                        # degenerate level
 
 
-def test_struct_layout_matches_header(lib, tmp_path):
-    """sizeof(MssConvArgs)/sizeof(MssRclArgs) as the C compiler sees them."""
+def header_declarations():
+    """(return type, name, [parameter declarations]) of every function include/mss_hip.h declares, comments stripped: a declaration
+    is whatever stands between two of `;`, `{`, `}` and has the form `<type words> mss_name(<no parentheses>)`."""
+    src = open(os.path.join(ROOT, "include", "mss_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    src = re.sub(r"^\s*#.*$", ";", src, flags=re.M)           # a preprocessor line ends whatever stood before it
+    return [(ret, name, [" ".join(p.split()) for p in params.split(",")])
+            for ret, name, params in re.findall(r"(?:^|[;{}])\s*((?:\w+\s+)+?)\s*(mss_\w+)\s*\(([^()]*)\)\s*(?=;)", src)]
+
+
+def test_ctypes_table_matches_header(lib):
+    """Every argtype and restype _lib.py binds is the one include/mss_hip.h declares: a slip between int and long long in a long
+    argument list would otherwise show only as a wrong number on the GPU."""
     import ctypes
-    code = '#include <stdio.h>\n#include "mss_hip.h"\nint main(){printf("%zu %zu\\n", sizeof(MssConvArgs), sizeof(MssRclArgs));return 0;}'
+    scalars = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
+               "uint32_t": ctypes.c_uint32, "unsigned long long": ctypes.c_ulonglong}
+
+    def ctype(param):
+        if "*" in param:
+            m = re.match(r"(?:const )?(Mss\w+) ?\*", param)
+            return ctypes.POINTER(getattr(lib, m.group(1))) if m else ctypes.c_void_p       # an Mss* struct _lib.py lacks: AttributeError
+        base = re.sub(r" ?\w+$", "", param).replace("const ", "").strip()                    # drop the parameter's name
+        assert base in scalars, f"a parameter type this test does not know: {param!r}"
+        return scalars[base]
+    decls = header_declarations()
+    assert len(decls) == len(lib.SIGNATURES) == 140 and {d[1] for d in decls} == set(lib.SIGNATURES)
+    wrong = []
+    for ret, name, params in decls:
+        ret = " ".join(ret.split())
+        assert ret in scalars, f"a return type this test does not know: {ret!r} {name}"
+        want = [] if params in (["void"], [""]) else [ctype(p) for p in params]
+        if want != list(lib.SIGNATURES[name]):
+            wrong.append((name, "argtypes"))
+        if name in lib.VALUE_RESTYPE and lib.VALUE_RESTYPE[name] is not scalars[ret]:
+            wrong.append((name, "restype"))
+        if name not in lib.VALUE_RESTYPE and (ret != "int" or params[-1] != "void* stream"):
+            wrong.append((name, "a status-returning entry point returns int and ends in the stream"))
+    assert not wrong, wrong
+    assert set(lib.VALUE_RESTYPE) <= set(lib.SIGNATURES)
+    handle = lib.load()
+    for name in lib.SIGNATURES:
+        assert getattr(handle, name).restype is lib.VALUE_RESTYPE.get(name, ctypes.c_int), name
+
+
+def test_struct_layout_matches_header(lib, tmp_path):
+    """sizeof of every struct of the header, and offsetof of its last field, as the C compiler sees them."""
+    import ctypes
+    last = {"MssConvArgs": "w_img_stride", "MssRclArgs": "selection_ratio", "MssOodmBatch": "n", "MssM2fSteps": "step", "MssM2fGrads": "step",
+            "MssM2fMaps": "w", "MssM2fTargets": "W"}
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mss_hip.h")).read(), flags=re.S)
+    assert set(re.findall(r"typedef struct (Mss\w+)", header)) == set(last)
+    for name, field in last.items():
+        assert getattr(lib, name)._fields_[-1][0] == field, name
+    code = '#include <stdio.h>\n#include <stddef.h>\n#include "mss_hip.h"\nint main(){' + "".join(
+        f'printf("%zu %zu\\n", sizeof({n}), offsetof({n}, {f}));' for n, f in last.items()) + "return 0;}"
     exe = str(tmp_path / "mss_sizeof")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=code.encode(), check=True)
-    a, b = (int(v) for v in subprocess.check_output([exe], text=True).split())
-    assert ctypes.sizeof(lib.MssConvArgs) == a and ctypes.sizeof(lib.MssRclArgs) == b
+    out = subprocess.check_output([exe], text=True).split()
+    assert len(out) == 2 * len(last)
+    out = [" ".join(out[i:i + 2]) for i in range(0, len(out), 2)]
+    for (name, field), line in zip(last.items(), out):
+        size, offset = (int(v) for v in line.split())
+        cls = getattr(lib, name)
+        assert (ctypes.sizeof(cls), getattr(cls, field).offset) == (size, offset), name
+
+
+def test_m2f_entry_points_validate_arguments_before_any_launch(lib):
+    """The argument checks of the matcher's and the criterion's entry points return before any HIP call, so they run without a
+    device: raw calls with a NULL stream. Every expected code was read off the library of ABI version 17 (loose argument lists)
+    called with the same values; the order of the checks decides which code a call with more than one fault gets.
+    Base case: S 2, B 2, Q 5, 7 x 9 NCHW maps, 3 targets of 28 x 36, Tmax 3, P 33, K 40, k 25, C1 20, ncols 5, split 1."""
+    import ctypes
+    OK, BAD, UNSUPPORTED = 0, lib.MSS_ERR_BAD_ARG, lib.MSS_ERR_UNSUPPORTED
+    handle = lib.load()
+    buf = (ctypes.c_char * 64)()
+    X = ctypes.addressof(buf)                   # a non-NULL pointer nothing dereferences: every case returns before its launch
+    cases = {"S=0": dict(S=0), "S=17": dict(S=17), "Q=129": dict(Q=129), "null step": dict(null_step=1), "null grad step": dict(null_grad=1),
+             "negative stride": dict(qs=-1), "total_t=0": dict(total_t=0, split=0, null_all=True), "ncols=4": dict(ncols=4),
+             "split>total_t": dict(split=4)}
+
+    def run(fn, S=2, Q=5, qs=63, total_t=3, ncols=5, split=1, null_step=None, null_grad=None, null_all=False):
+        B, h, w, H, W, Tmax, P, K, k, C1 = 2, 7, 9, 28, 36, 3, 33, 40, 25, 20
+        opt = None if null_all else X           # what may be NULL when there are no targets
+        maps = lib.MssM2fMaps(img_stride=Q * h * w, query_stride=qs, pixel_stride=1, S=S, B=B, Q=Q, h=h, w=w)
+        cls, grads = lib.MssM2fSteps(), lib.MssM2fGrads()
+        for s in range(min(S, lib.MSS_M2F_MAX_STEPS)):
+            maps.step[s] = cls.step[s] = None if null_all or s == null_step else X
+            grads.step[s] = None if null_all or s == null_grad else X
+        tg = lib.MssM2fTargets(opt, X, opt, total_t, H, W)
+        mp, cp, gp, tp = (ctypes.byref(v) for v in (maps, cls, grads, tg))
+        if fn == "match_cost":
+            return handle.mss_m2f_match_cost_f32(mp, cp, tp, X, C1, P, Tmax, 1., 1., 1., X, X, X, X, None)
+        if fn == "loss_select":
+            return handle.mss_m2f_loss_select_f32(mp, tp, X, opt, opt, Tmax, K, k, P, P, 1, 0, opt, opt, None)
+        if fn == "loss_mask_forward":
+            return handle.mss_m2f_loss_mask_forward_f32(mp, tp, X, opt, Tmax, P, opt, None)
+        if fn == "loss_finalize":
+            return handle.mss_m2f_loss_finalize_f32(cp, tp, X, X, opt, S, B, Q, C1, Tmax, P, split, 1., 1., ncols, X, X, X, X, None)
+        if fn == "loss_mask_backward":
+            return handle.mss_m2f_loss_mask_backward_f32(mp, tp, X, X, opt, opt, X, Tmax, P, split, 1., 1., ncols, opt, gp, None)
+        return handle.mss_m2f_loss_label_backward_f32(cp, X, X, X, X, X, S, B, Q, C1, ncols, gp, None)
+    expected = {
+        "match_cost": {"S=0": BAD, "S=17": UNSUPPORTED, "Q=129": UNSUPPORTED, "null step": BAD, "negative stride": BAD, "total_t=0": BAD},
+        "loss_select": {"S=0": UNSUPPORTED, "S=17": UNSUPPORTED, "null step": BAD, "negative stride": BAD, "total_t=0": OK},
+        "loss_mask_forward": {"S=0": UNSUPPORTED, "S=17": UNSUPPORTED, "null step": BAD, "negative stride": BAD, "total_t=0": OK},
+        "loss_finalize": {"S=0": UNSUPPORTED, "S=17": UNSUPPORTED, "null step": BAD, "total_t=0": BAD, "ncols=4": BAD, "split>total_t": BAD},
+        "loss_mask_backward": {"S=0": UNSUPPORTED, "S=17": UNSUPPORTED, "null step": BAD, "null grad step": BAD, "negative stride": BAD,
+                               "total_t=0": OK, "ncols=4": BAD, "split>total_t": BAD},
+        "loss_label_backward": {"S=0": UNSUPPORTED, "S=17": UNSUPPORTED, "null step": BAD, "null grad step": BAD, "ncols=4": BAD},
+    }
+    got = {fn: {case: run(fn, **cases[case]) for case in want} for fn, want in expected.items()}
+    assert got == expected
 
 
 def test_product_path_fails_loudly_without_gpu():
