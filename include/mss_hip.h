@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 18     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 19     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -45,13 +45,14 @@ extern "C" {
                                   17 (additive): mss_adamw_clip_step_f32 and its five host-only queries mss_adamw_chunk_elems, mss_adamw_tensors_per_launch,
                                   mss_adamw_blocks_per_launch, mss_adamw_scratch_floats, mss_adamw_plan (multi-tensor AdamW with full-model gradient clipping);
                                   18: MssM2fMaps / MssM2fTargets / MssM2fSteps / MssM2fGrads replace the loose mask-map, target-pack and per-step pointer-table
-                                  arguments of mss_m2f_match_cost_f32 and the mss_m2f_loss_* entry points (signatures changed, none added or removed) */
+                                  arguments of mss_m2f_match_cost_f32 and the mss_m2f_loss_* entry points (signatures changed, none added or removed);
+                                  19: mss_wino_input_transform_aspp3_src2_f32 added (the ASPP transform on the two un-multiplied factors of the trunk output);
+                                  mss_env_generation removed from the ABI (nothing outside the library called it; it is a hidden helper now) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
  * cached. A process that changes one after its first call into the library calls this to have them re-read. */
 int mss_env_reset(void);        /* returns the new generation */
-int mss_env_generation(void);
 
 /* ---------------------------------------------------------------------------------------------
  * B1 -- MultiScaleDeformableAttention extension
@@ -282,6 +283,17 @@ int mss_wino_input_transform_upcat_f32(const float* a, int lda, int c_split, con
  * tile edge is 2 (the caller then runs the three transforms separately). */
 int mss_wino_input_transform_aspp3_f32(const float* x, int ldx, int N, int H, int W, int C, int d, const int* tiles, float* xt0,
                                        float* xt1, float* xt2, void* stream);
+/* The same transform on a map that is never stored: w = [relu(x0 * scale0 + shift0) ; relu(x1 * scale1 + shift1)], C0 + C1 channels
+ * (the two prologue factors of the trunk's last block, whose 1x1 output convolutions are folded into the ASPP weights). ss0 / ss1:
+ * per-sample stride of that source's (scale, shift) vectors, 0 = shared by all samples. xt_m = exactly what
+ * mss_affine_relu_nhwc_f32 into one (C0 + C1)-channel buffer followed by mss_wino_input_transform_aspp3_f32 writes; padding stays zero.
+ * sums (optional, with gap): scratch [N][d*d][C0 + C1], the column sums of w over each base residue sub-grid, in a fixed order;
+ * gap [N][C0 + C1] = their sum / (H*W) (float64 accumulation, fixed order): AdaptiveAvgPool2d(1) of w. xt0 = xt1 = xt2 = NULL:
+ * sums only, the same code path and the same bits. MSS_ERR_UNSUPPORTED as for mss_wino_input_transform_aspp3_f32. */
+int mss_wino_input_transform_aspp3_src2_f32(const float* x0, int ldx0, int C0, const float* scale0, const float* shift0, int ss0,
+                                            const float* x1, int ldx1, int C1, const float* scale1, const float* shift1, int ss1,
+                                            int N, int H, int W, int d, const int* tiles, float* xt0, float* xt1, float* xt2,
+                                            float* sums, float* gap, void* stream);
 int mss_wino_output_transform_f32(const float* yt, int N, int H, int W, int K, int dil, int tile, const float* res,
                                   int ldres, float* y, int ldy, float* stats, void* stream);
 /* stats (optional): [mss_wino_output_stats_parts(...)][2][K] partial sums / sums of squares of y, as MssConvArgs.stats */

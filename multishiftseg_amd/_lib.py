@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 18         # include/mss_hip.h
+MSS_ABI_VERSION = 19         # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -92,7 +92,6 @@ U = c_uint32
 SIGNATURES = {
     "mss_abi_version": [],
     "mss_env_reset": [],
-    "mss_env_generation": [],
     "mss_msda_forward_f32": [P, P, P, P, P, I, I, I, I, I, I, I, P, P],
     "mss_msda_forward_f64": [P, P, P, P, P, I, I, I, I, I, I, I, P, P],
     "mss_msda_backward_f32": [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P],
@@ -176,6 +175,7 @@ SIGNATURES = {
     "mss_wino_input_transform_bnbwd_f32": [P, I, P, I, I, I, I, I, I, I, P, P, P, P, P, I, P, P],
     "mss_wino_input_transform_upcat_f32": [P, I, I, P, I, I, I, I, I, I, I, I, P, P],
     "mss_wino_input_transform_aspp3_f32": [P, I, I, I, I, I, I, P, P, P, P, P],
+    "mss_wino_input_transform_aspp3_src2_f32": [P, I, I, P, P, I, P, I, I, P, P, I, I, I, I, I, P, P, P, P, P, P, P],
     "mss_wino_output_transform_f32": [P, I, I, I, I, I, I, P, I, P, I, P, P],
     "mss_wino_output_stats_parts": [I, I, I, I, I, I],
     "mss_bn_stats_partials_f32": [P, L, I, P, P],
@@ -233,7 +233,7 @@ SIGNATURES = {
 }
 # the entry points that return a plain value, and its C type; every other one returns an int status code
 VALUE_RESTYPE = {
-    "mss_abi_version": c_int, "mss_env_reset": c_int, "mss_env_generation": c_int, "mss_msda_backward_workspace_bytes": c_longlong, "mss_chan_compact_wanted": c_int, "mss_conv2d_kpad": c_int,
+    "mss_abi_version": c_int, "mss_env_reset": c_int, "mss_msda_backward_workspace_bytes": c_longlong, "mss_chan_compact_wanted": c_int, "mss_conv2d_kpad": c_int,
     "mss_conv2d_forward_route": c_int, "mss_gemm_split_last_mfma": c_int, "mss_gemm_split_weights_bytes": c_longlong, "mss_conv2d_wgrad_workspace_bytes": c_longlong, "mss_conv2d_wgrad_route": c_int,
     "mss_col_reduce_accum_doubles": c_longlong, "mss_colsum_workspace_floats": c_longlong, "mss_rcl_num_compact_blocks": c_int, "mss_rcl_workspace_bytes": c_longlong, "mss_adamw_chunk_elems": c_int,
     "mss_adamw_tensors_per_launch": c_int, "mss_adamw_blocks_per_launch": c_int, "mss_adamw_scratch_floats": c_longlong, "mss_adamw_plan": c_longlong, "mss_wino_num_tiles": c_longlong,

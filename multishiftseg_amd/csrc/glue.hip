@@ -1454,7 +1454,7 @@ int mss_m2f_score_f32(const float* cls, const float* mask, int B, int Q, int C, 
 }
 
 static std::atomic<int> g_env_generation{0};
-int mss_env_generation(void) { return g_env_generation.load(std::memory_order_relaxed); }
+int mssi_env_generation(void) { return g_env_generation.load(std::memory_order_relaxed); }
 int mss_env_reset(void) { return g_env_generation.fetch_add(1, std::memory_order_relaxed) + 1; }
 
 int mss_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr,

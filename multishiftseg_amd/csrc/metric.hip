@@ -394,7 +394,7 @@ inline RsPlan rs_plan(long long n) {
 }
 inline bool rs_use_rocprim() {
   static std::atomic<long long> slot{-(1ll << 32)};        // cached like MSS_ENV_INT (mss_common.h); the value is a word here
-  const int gen = mss_env_generation();
+  const int gen = mssi_env_generation();
   const long long v = slot.load(std::memory_order_relaxed);
   if ((int)(v >> 32) == gen) return (v & 1) != 0;
   const char* e = getenv("MSS_OODM_SORT");

@@ -23,9 +23,10 @@ static inline int mss_launch_status() {
 // Tuning / test switches (MSS_* environment variables) read on launch paths: each call site caches its value and re-reads the
 // environment only after mss_env_reset() (include/mss_hip.h) has bumped the generation -- no getenv() per kernel launch.
 // A process that sets its switches before the first call needs nothing; tests that flip them call the reset hook.
-extern "C" int mss_env_generation(void);
+// (library-internal: hidden visibility, not part of the C ABI)
+extern "C" __attribute__((visibility("hidden"))) int mssi_env_generation(void);
 static inline int mss_env_lookup(const char* name, int dflt, std::atomic<long long>& slot) {
-  const int gen = mss_env_generation();
+  const int gen = mssi_env_generation();
   const long long v = slot.load(std::memory_order_relaxed);
   if ((int)(v >> 32) == gen) return (int)(unsigned)(v & 0xffffffffll);
   const char* e = getenv(name);

@@ -717,45 +717,116 @@ def conv3x3_pair(x, w1, w2, dil1, dil2, out1, out2, tile, want_stats=False, xt=N
     return out1, out2
 
 
-def aspp_input_transforms(x, rates, weights, pair_tile=0, max_bytes=None):
+class FactoredAct:
+    """The trunk's 4096-channel output x = Wproj . u + W3 . v that the composed ASPP route never forms (deepv3._aspp_composed): its
+    two factors u = relu(a0 * aff0) and v = relu(a1 * aff1) (aff1 per sample under Dropout2d), which stand for the map
+    w = [u ; v] of C = a0.C + a1.C channels. Has the shape attributes of an Act so that the Winograd wrappers, which only read x's
+    shape once they are handed X', take it in x's place."""
+    __slots__ = ("a0", "aff0", "a1", "aff1", "N", "H", "W", "C", "buf")
+
+    def __init__(self, a0, aff0, a1, aff1):
+        assert (a0.N, a0.H, a0.W) == (a1.N, a1.H, a1.W)
+        self.a0, self.aff0, self.a1, self.aff1 = a0, aff0, a1, aff1
+        self.N, self.H, self.W, self.C, self.buf = a0.N, a0.H, a0.W, a0.C + a1.C, a0.buf
+
+    def materialise(self):
+        """w as an Act (mss_affine_relu_nhwc_f32 per source; a per-sample affine image by image): the second formulation of the
+        two-source transform, and what a route that needs the map itself reads."""
+        w = Act.empty(self.N, self.H, self.W, self.C, self.buf.device)
+        c0 = 0
+        for a, (sc, sh) in ((self.a0, self.aff0), (self.a1, self.aff1)):
+            dst = w.slice(c0, a.C)
+            if sc.dim() == 1:
+                call("mss_affine_relu_nhwc_f32", a.ptr, a.ld, dst.ptr, dst.ld, a.M, a.C, ptr(sc), ptr(sh), 1)
+            else:
+                hw = a.H * a.W
+                for n in range(a.N):
+                    call("mss_affine_relu_nhwc_f32", ctypes.c_void_p(a.ptr.value + 4 * n * hw * a.ld), a.ld,
+                         ctypes.c_void_p(dst.ptr.value + 4 * n * hw * dst.ld), dst.ld, hw, a.C, ptr(sc[n]), ptr(sh[n]), 1)
+            c0 += a.C
+        return w
+
+
+def aspp_compose_wanted():
+    """The switch of the composed ASPP route (MSS_ASPP_COMPOSE, default 1): taken under the Winograd policy without a tile hook; the
+    shapes are the caller's to check (deepv3.DeepWV3Plus._aspp_compose_gate)."""
+    return os.environ.get("MSS_ASPP_COMPOSE", "1") != "0" and _tile_hook is None and os.environ.get("MSS_WINOGRAD", "1") != "0"
+
+
+def aspp_tiles(H, W, C, rates, weights):
+    """The tile edges of the three dilated ASPP branches where the single-read transforms apply -- rates (d, 2d, 3d), every tile 4
+    or 6 under the Winograd policy, no tile hook -- else None."""
+    d = rates[0]
+    if _tile_hook is not None or tuple(rates) != (d, 2 * d, 3 * d):
+        return None
+    tiles = [wino_tile(H, W, r) for r in rates]
+    for w, t in zip(weights, tiles):
+        if t not in (4, 6) or w.shape[1] != C or not use_winograd(w.shape[1], w.shape[0], 1, None, t):
+            return None
+    return tiles
+
+
+def aspp_input_transforms(x, rates, weights, pair_tile=0, max_bytes=None, want_gap=False):
     """X' of the ONE map `x` for the three dilated 3x3 branches of ASPP (deepv3.py:84-92; rates d, 2d, 3d) from a single read of x
     (mss_wino_input_transform_aspp3_f32): bit-identical to the three separate input transforms, 1 x instead of 3 x 1.07 GB read at
     2 x 128 x 256 x 4096. Returns [xt_d, xt_2d, xt_3d] -- with pair_tile (conv3x3_pair_tile) the first two are the halves of ONE
     [2P, T, C] buffer, returned as its first element with None second -- or None when the policy / shapes do not take the fused
-    kernel (a tile edge of 2, Winograd off, a tile hook, sub-grids too large for LDS; MSS_WINO_ASPP3=0 switches it off)."""
+    kernel (a tile edge of 2, Winograd off, a tile hook, sub-grids too large for LDS; MSS_WINO_ASPP3=0 switches it off).
+    x a FactoredAct: the two-source kernel (mss_wino_input_transform_aspp3_src2_f32) on the map that is never stored; with
+    want_gap the answer is (xts or None, gap [N, C] or None), the global average of that map from the same kernel -- from its
+    sums-only mode when X' is not taken here (MSS_WINO_ASPP3=0, over budget), None only where the kernel refuses the shape."""
+    factored = isinstance(x, FactoredAct)
+    assert factored or not want_gap
     d = rates[0]
-    if os.environ.get("MSS_WINO_ASPP3", "1") == "0" or _tile_hook is not None or tuple(rates) != (d, 2 * d, 3 * d):
-        return None
-    tiles = [wino_tile(x.H, x.W, r) for r in rates]
-    if pair_tile and (tiles[0] != pair_tile or tiles[1] != pair_tile):
-        return None
-    for w, t in zip(weights, tiles):
-        if t not in (4, 6) or w.shape[1] != x.C or not use_winograd(w.shape[1], w.shape[0], 1, None, t):
-            return None
     N, H, W, C = x.N, x.H, x.W, x.C
     dev = x.buf.device
-    Ts = [_lib.value("mss_wino_num_tiles", N, H, W, r, t) for r, t in zip(rates, tiles)]
-    Ps = [(t + 2) ** 2 for t in tiles]
-    # all three X' are live at once here (2.25-4x the map each: 10.6 GB at 2 x 1024 x 2048); a caller that does not keep them for the
-    # backward passes its budget, beyond which each branch transforms for itself again with one X' live at a time (ADVICE r04)
-    if max_bytes is not None and 4.0 * sum(p * t for p, t in zip(Ps, Ts)) * C > max_bytes:
-        return None
-    if pair_tile:
-        assert Ts[0] == Ts[1]
-        both = torch.empty((2 * Ps[0], Ts[0], C), device=dev, dtype=torch.float32)
-        xts = [both[:Ps[0]], both[Ps[0]:], torch.empty((Ps[2], Ts[2], C), device=dev, dtype=torch.float32)]
+    tiles = aspp_tiles(H, W, C, rates, weights)
+    want_xt = tiles is not None and os.environ.get("MSS_WINO_ASPP3", "1") != "0"
+    if want_xt and pair_tile and (tiles[0] != pair_tile or tiles[1] != pair_tile):
+        want_xt = False
+    Ts = Ps = None
+    if want_xt:
+        Ts = [_lib.value("mss_wino_num_tiles", N, H, W, r, t) for r, t in zip(rates, tiles)]
+        Ps = [(t + 2) ** 2 for t in tiles]
+        # all three X' are live at once here (2.25-4x the map each: 10.6 GB at 2 x 1024 x 2048); a caller that does not keep them for
+        # the backward passes its budget, beyond which each branch transforms for itself again with one X' live at a time (ADVICE r04)
+        if max_bytes is not None and 4.0 * sum(p * t for p, t in zip(Ps, Ts)) * C > max_bytes:
+            want_xt = False
+    if not want_xt and not (want_gap and tiles is not None):
+        return (None, None) if want_gap else None
+    both, xts = None, [None, None, None]
+    if want_xt:
+        if pair_tile:
+            assert Ts[0] == Ts[1]
+            both = torch.empty((2 * Ps[0], Ts[0], C), device=dev, dtype=torch.float32)
+            xts = [both[:Ps[0]], both[Ps[0]:], torch.empty((Ps[2], Ts[2], C), device=dev, dtype=torch.float32)]
+        else:
+            xts = [torch.empty((p, t, C), device=dev, dtype=torch.float32) for p, t in zip(Ps, Ts)]
+    nbytes = 4.0 * (N * H * W * C + (sum(p * t for p, t in zip(Ps, Ts)) * C if want_xt else 0))
+    ctiles = (ctypes.c_int * 3)(*tiles)
+    gap = None
+    if factored:
+        name = "mss_wino_input_transform_aspp3_src2_f32"
+        sums = None
+        if want_gap:
+            sums = torch.empty((N, d * d, C), device=dev, dtype=torch.float32)       # fully overwritten by the kernel
+            gap = torch.empty((N, C), device=dev, dtype=torch.float32)
+        (sc0, sh0), (sc1, sh1) = x.aff0, x.aff1
+        assert all(t.is_contiguous() and t.shape[-1] == a.C for a, ts in ((x.a0, x.aff0), (x.a1, x.aff1)) for t in ts)
+        with _Timed("wino_transform", nbytes, ("input_aspp3" if want_xt else "aspp_gap", N, H, W, C, d, tuple(tiles))):
+            rc = _lib.status(name, x.a0.ptr, x.a0.ld, x.a0.C, ptr(sc0), ptr(sh0), x.a0.C if sc0.dim() == 2 else 0,
+                             x.a1.ptr, x.a1.ld, x.a1.C, ptr(sc1), ptr(sh1), x.a1.C if sc1.dim() == 2 else 0,
+                             N, H, W, d, ctiles, ptr(xts[0]), ptr(xts[1]), ptr(xts[2]), ptr(sums), ptr(gap))
     else:
-        both = None
-        xts = [torch.empty((p, t, C), device=dev, dtype=torch.float32) for p, t in zip(Ps, Ts)]
-    nbytes = 4.0 * (N * H * W * C + sum(p * t for p, t in zip(Ps, Ts)) * C)
-    with _Timed("wino_transform", nbytes, ("input_aspp3", N, H, W, C, d, tuple(tiles))):
-        rc = _lib.status("mss_wino_input_transform_aspp3_f32", x.ptr, x.ld, N, H, W, C, d, (ctypes.c_int * 3)(*tiles), ptr(xts[0]),
-                         ptr(xts[1]), ptr(xts[2]))
+        name = "mss_wino_input_transform_aspp3_f32"
+        with _Timed("wino_transform", nbytes, ("input_aspp3", N, H, W, C, d, tuple(tiles))):
+            rc = _lib.status(name, x.ptr, x.ld, N, H, W, C, d, ctiles, ptr(xts[0]), ptr(xts[1]), ptr(xts[2]))
     if rc == _lib.MSS_ERR_UNSUPPORTED:
-        return None
+        return (None, None) if want_gap else None
     if rc != 0:
-        raise _lib.MssError(f"mss_wino_input_transform_aspp3_f32 failed with code {rc}")
-    return [both, None, xts[2]] if pair_tile else xts
+        raise _lib.MssError(f"{name} failed with code {rc}")
+    out = None if not want_xt else ([both, None, xts[2]] if pair_tile else xts)
+    return (out, gap) if want_gap else out
 
 
 def conv2d_wgrad_winograd(x, dy, K, C, dil=1, in_affine=None, in_relu=False, xt=None, tile=None):

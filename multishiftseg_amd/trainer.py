@@ -140,6 +140,9 @@ class GraphedEval:
             self.static_out = ood_scores(self.model, self.static_in, self.score_only)
         # own what the graph reads: the packed forms current right now (+ the fused heads weight of the model)
         self._keep = [dict(p.__dict__.get("_mss_packed", {})) for p in self.model.parameters()] + [self.model._heads_cache]
+        cc = getattr(self.model, "_compose_cache", None)
+        if cc is not None:          # the composed ASPP weights (made in the warm-up, never inside the capture) and their packed forms
+            self._keep += [dict(cc)] + [dict(t.__dict__.get("_mss_packed", {})) for t in cc.get("wc", ())]
         self._sig = self._signature()
         self.captures += 1
 
