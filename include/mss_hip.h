@@ -255,7 +255,15 @@ int mss_conv2d_wgrad_route(const MssConvArgs* args, int lddy);
  * (T = mss_wino_num_tiles, BatchNorm/ReLU prologue and zero padding fused); then ONE mss_conv2d_forward_f32
  * call in batched 1x1 mode (batch = P, x_bs = T*C, w_bs = Kpad*Cp, y_bs = T*K) gives Y' [P][T][K];
  * Y' -> NHWC y (+ residual). Dilation is exact (per-residue sub-grids). MFMA work is 9*m^2/P = 2.25x (m = 2)
- * or 4x (m = 4) below the direct form; fp32 rounding error ~1e-6 (m = 2) / ~1e-5 (m = 4) relative per layer. */
+ * or 4x (m = 4) below the direct form; fp32 rounding error ~1e-6 (m = 2) / ~1e-5 (m = 4) relative per layer.
+ * Tile geometry and layout (m = 2, 4 or 6; n = m + 2; d = dil), restated in float64 by tests/ref_winograd.py:
+ *   Hs = ceil(H / d), tH = ceil(Hs / m), the same for W; T = N * d * d * tH * tW.
+ *   Tile index t = (((img * d + a) * d + b) * tH + ty) * tW + tx for image img, residue sub-grid (a, b), tile (ty, tx) of it.
+ *   Element (i, j), 0 <= i, j < n, of the input tile is image pixel ((m * ty + i - 1) * d + a, (m * tx + j - 1) * d + b), zero
+ *   outside the image (after the prologue); element (u, v), 0 <= u, v < m, of the output tile is pixel ((m * ty + u) * d + a,
+ *   (m * tx + v) * d + b), not written (dY': read as zero) outside it.
+ *   X' is [n * n][T][C] and Y' / dY' are [n * n][T][K], Winograd position (xi, nu) = (row, column) of B^T d B at index xi * n + nu;
+ *   U / dU are [n * n][Kpad][Cp] with (G g G^T)[xi][nu] of filter (k, c) at [xi * n + nu][k][c], zero for k >= K or c >= C. */
 long long mss_wino_num_tiles(int N, int H, int W, int dil, int tile);
 int mss_wino_pack_weights_f32(const float* w, float* u, int K, int C, int Kpad, int Cp, int tile, void* stream);
 /* The same U straight into the split-bf16 planes MssConvArgs.w_split takes ((tile + 2)^2 batch entries of [Kpad][C]; bit-identical to
