@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 19     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 20     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -47,7 +47,11 @@ extern "C" {
                                   18: MssM2fMaps / MssM2fTargets / MssM2fSteps / MssM2fGrads replace the loose mask-map, target-pack and per-step pointer-table
                                   arguments of mss_m2f_match_cost_f32 and the mss_m2f_loss_* entry points (signatures changed, none added or removed);
                                   19: mss_wino_input_transform_aspp3_src2_f32 added (the ASPP transform on the two un-multiplied factors of the trunk output);
-                                  mss_env_generation removed from the ABI (nothing outside the library called it; it is a hidden helper now) */
+                                  mss_env_generation removed from the ABI (nothing outside the library called it; it is a hidden helper now);
+                                  20: mss_wino_input_transform_aspp3_dropped_f32 added and MssConvArgs.k_base / k_imgs inserted in front of k_steps (the
+                                  composed ASPP products without the Dropout2d-zeroed channels); mss_chan_compact_index also writes `col`,
+                                  mss_conv2d_pack_weights_f32 / mss_conv2d_unpack_wgrad_f32 take the per-image column gather (signatures changed);
+                                  mss_msda_prepare_backward_f32 removed: it was mss_msda_prepare_backward_ld_f32 with dense strides, which its callers now pass */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -109,10 +113,7 @@ int mss_msda_forward_fused_f32(const float* value, const int64_t* spatial_shapes
 int mss_msda_prepare_f32(const float* offsets, const float* logits, const float* reference_points,
                          const int64_t* spatial_shapes, int N, int Lq, int M, int L, int P, float* sampling_loc,
                          float* attn_weight, void* stream);
-int mss_msda_prepare_backward_f32(const float* attn_weight, const float* grad_attn, const float* grad_loc,
-                                  const int64_t* spatial_shapes, int N, int Lq, int M, int L, int P, float* grad_offsets,
-                                  float* grad_logits, void* stream);
-/* The same with row strides: grad_offsets row (n, q) at + (n*Lq + q) * ld_offsets (>= M*2*L*P floats), grad_logits likewise with
+/* Row strides: grad_offsets row (n, q) at + (n*Lq + q) * ld_offsets (>= M*2*L*P floats, equal: dense), grad_logits likewise with
  * ld_logits (>= M*L*P). Both gradients in ONE [N*Lq, M*3*L*P] buffer (offsets | logits) make the weight gradient and the data
  * gradient of `sampling_offsets` and `attention_weights` -- two Linears on the same query (ops/modules/ms_deform_attn.py:98-100)
  * -- one GEMM each. */
@@ -178,6 +179,11 @@ typedef struct MssConvArgs {
                            /*   >= 48 input channels); other shapes run the native fp32 kernels on `w` (which must always be set).   */
   int route;               /* 0: native fp32 MFMA. 1: mss_conv2d_wgrad_f32 evaluates the TN product the same split-bf16 way (both    */
                            /*   operands split in the loader) where K % 128 == 0 and C % 256 == 0; other shapes stay native.         */
+  int k_base, k_imgs;      /* with k_steps (below). k_imgs > 0 (batch > 1, batch % k_imgs == 0): batch entry b holds the rows of      */
+                           /*   image b % k_imgs alone (Winograd-domain entries ordered (position, image)) and runs k_base +           */
+                           /*   k_steps[b % k_imgs] K-steps over its own weights (w_bs; w_img_stride 0); rows per entry need not be a  */
+                           /*   multiple of 128. In mss_conv2d_wgrad_f32: entry b's dU' covers its first 16 * (k_base + k_steps)       */
+                           /*   columns; c tiles behind them are not written. k_imgs == 0: the one-batch form described below.         */
   const int* k_steps;      /* optional (DEVICE, [N]): per-image reduction length of a 1x1 product over channel-compacted operands   */
   long long w_img_stride;  /*   (mss_chan_compact_*): image n runs k_steps[n] 16-deep K-steps (>= 3, 16 * k_steps[n] <= C) over the  */
                            /*   weights at w + n * w_img_stride floats. No prologue, no batch, OH * OW % 128 == 0, > 64 output       */
@@ -199,12 +205,14 @@ int mss_conv2d_forward_f32(MssConvArgs* args, void* stream);
  *            shift[n][c]) with c = place[n][p], 0 where place[n][p] < 0, for p < 16 * k_steps[n]; later columns are not written.
  *            The arithmetic is the prologue's of the persistent GEMM kernel, so the operand values are the ones the dense product sees.
  *   weights: packed w [Kpad][C] -> out [N][Kpad][C]: out[n][k][p] = w[k][place[n][p]], same zero fill, later columns not written.
+ *            col [N][C] int32 (optional, NULL: not wanted), written whole: the inverse of place -- the column channel c of sample n
+ *            went to, -1 for a dropped channel.
  * idx entries from K_n on are never written or read. All float pointers 16-byte aligned. */
 /* 1 when a 1x1 product with these (dense) arguments -- per-sample prologue affine + ReLU as the Dropout2d fold builds it -- qualifies
  * for the compacted form and MSS_DROPOUT_COMPACT (default 1) is not 0: stride 1, no padding, OH * OW % 128 == 0, 64 < K, Kpad % 128
  * == 0, 48 <= C <= 2048, ldx == C, no batch, no epilogue affine, native route (w_split NULL), operands within 32-bit byte offsets. */
 int mss_chan_compact_wanted(const MssConvArgs* args);
-int mss_chan_compact_index(const float* mask, int N, int C, int* idx, int* place, int* count, int* k_steps, void* stream);
+int mss_chan_compact_index(const float* mask, int N, int C, int* idx, int* place, int* count, int* k_steps, int* col, void* stream);
 int mss_chan_compact_act_f32(const float* x, int ldx, float* out, int ldout, int N, int rows_per_image, int C, const int* place,
                              const int* k_steps, const float* scale, const float* shift, void* stream);
 int mss_chan_compact_weights_f32(const float* w, float* out, int N, int Kpad, int C, const int* place, const int* k_steps,
@@ -234,8 +242,11 @@ int mss_gemm_split_last_mfma(void);
 /* w [K][C][R][S] (nn.Conv2d.weight) -> packed [R*S][Kpad][Cp] (zero padded).
  * flip=1 packs the data-gradient filter instead (K<->C swapped, taps rotated 180 degrees);
  * then Kpad/Cp refer to the swapped roles. */
+/* col != NULL (flip 0): w is n_img tensors [n][K][C][R][S] whose channels from c0 on are per-image compacted COLUMNS (col [n_img][C - c0]
+ * from mss_chan_compact_index: the column of image n that holds channel c0 + j, -1 none); `packed` gets, in original channel order, the
+ * sum over the images in ascending n, exact zero for a channel no image holds (the weight gradients of the dropped-channel ASPP products). */
 int mss_conv2d_pack_weights_f32(const float* w, float* packed, int K, int C, int R, int S, int Kpad, int Cp,
-                                int flip, void* stream);
+                                int flip, const int* col, int n_img, int c0, void* stream);
 /* weight gradient: dwp[tap][k][c] = sum_m dy[m][k]*act(x[m@tap][c]); dwp [taps][Kpad][Cp] is fully overwritten.
  * Deterministic (no atomics; pixel-range partials are summed in a fixed order: the reference pins
  * cudnn.deterministic, lib/utils/utils.py:10-13). ws: scratch of mss_conv2d_wgrad_workspace_bytes(args, Cp) bytes
@@ -244,8 +255,11 @@ int mss_conv2d_pack_weights_f32(const float* w, float* packed, int K, int C, int
 long long mss_conv2d_wgrad_workspace_bytes(const MssConvArgs* args, int Cp);
 int mss_conv2d_wgrad_f32(MssConvArgs* args, const float* dy, int lddy, float* dwp, int Cp, float* ws,
                          long long ws_bytes, void* stream);
+/* place != NULL (accumulate 0): grad is n_img tensors [n][K][C][R][S]; image n's holds packed's channels [0, c0) as they are, channel
+ * c0 + place[n][p] in column c0 + p for p < 16 * k_steps[n] (place -1: zero) and zeros behind: weights in the per-image compacted column
+ * order of mss_chan_compact_index (place [n_img][C - c0]). */
 int mss_conv2d_unpack_wgrad_f32(const float* packed, float* grad, int K, int C, int R, int S, int Kpad,
-                                int Cp, int accumulate, void* stream);
+                                int Cp, int accumulate, const int* place, const int* k_steps, int n_img, int c0, void* stream);
 /* 1 when mss_conv2d_wgrad_f32 runs these arguments on the split-bf16 TN kernel (args->route == 1, K % 128 == 0, C % 256 == 0, enough
  * tiles to fill half the chip), else 0 (native fp32 MFMA kernels). Profiling label only. */
 int mss_conv2d_wgrad_route(const MssConvArgs* args, int lddy);
@@ -302,6 +316,16 @@ int mss_wino_input_transform_aspp3_src2_f32(const float* x0, int ldx0, int C0, c
                                             const float* x1, int ldx1, int C1, const float* scale1, const float* shift1, int ss1,
                                             int N, int H, int W, int d, const int* tiles, float* xt0, float* xt1, float* xt2,
                                             float* sums, float* gap, void* stream);
+/* The same without the second factor's Dropout2d-zeroed channels. x1c: v = relu(x1 * scale1 + shift1) channel-compacted per image by
+ * mss_chan_compact_act_f32 (pitch ldx1 >= C1; place [N][C1], k_steps [N] of mss_chan_compact_index). Of image n's rows of every X'
+ * (pitch C0 + C1) only the first C0 + 16 * k_steps[n] columns are written: u's C0 channels (C0 % 16 == 0), then v's kept channels in
+ * `place` order -- each column bit for bit the dense X' column of its channel, exact zeros where place is -1. sums [N][d*d][C0 + C1]
+ * and gap [N][C0 + C1] (both or neither) come out in ORIGINAL channel order with the dense call's bits. All three X' are required.
+ * The batched products then take batch entries (position, image): MssConvArgs.k_steps / k_base = C0 / 16 / k_imgs = N. */
+int mss_wino_input_transform_aspp3_dropped_f32(const float* x0, int ldx0, int C0, const float* scale0, const float* shift0, int ss0,
+                                               const float* x1c, int ldx1, int C1, const int* place, const int* k_steps,
+                                               int N, int H, int W, int d, const int* tiles, float* xt0, float* xt1, float* xt2,
+                                               float* sums, float* gap, void* stream);
 int mss_wino_output_transform_f32(const float* yt, int N, int H, int W, int K, int dil, int tile, const float* res,
                                   int ldres, float* y, int ldy, float* stats, void* stream);
 /* stats (optional): [mss_wino_output_stats_parts(...)][2][K] partial sums / sums of squares of y, as MssConvArgs.stats */

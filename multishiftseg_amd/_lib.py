@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 19         # include/mss_hip.h
+MSS_ABI_VERSION = 20         # include/mss_hip.h
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
 
@@ -68,7 +68,7 @@ class MssConvArgs(Structure):
         ("res_mask", c_int),
         ("w_split", c_void_p),
         ("route", c_int),
-        ("k_steps", c_void_p), ("w_img_stride", c_longlong),
+        ("k_base", c_int), ("k_imgs", c_int), ("k_steps", c_void_p), ("w_img_stride", c_longlong),
     ]
 
 
@@ -101,14 +101,13 @@ SIGNATURES = {
     "mss_msda_backward_binned_proj_f32": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, L, P, L, P, L, P],
     "mss_msda_forward_fused_f32": [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P],
     "mss_msda_prepare_f32": [P, P, P, P, I, I, I, I, I, P, P, P],
-    "mss_msda_prepare_backward_f32": [P, P, P, P, I, I, I, I, I, P, P, P],
     "mss_msda_prepare_backward_ld_f32": [P, P, P, P, I, I, I, I, I, P, L, P, L, P],
     "mss_msda_forward_fused_ld_f32": [P, P, P, P, L, P, L, P, I, I, I, I, I, I, I, P, P],
     "mss_msda_forward_fused_save_f32": [P, P, P, P, L, P, L, P, I, I, I, I, I, I, I, P, P, P, P],
     "mss_msda_prepare_ld_f32": [P, L, P, L, P, P, I, I, I, I, I, P, P, P],
     "mss_conv2d_forward_f32": [POINTER(MssConvArgs), P],
     "mss_chan_compact_wanted": [POINTER(MssConvArgs)],
-    "mss_chan_compact_index": [P, I, I, P, P, P, P, P],
+    "mss_chan_compact_index": [P, I, I, P, P, P, P, P, P],
     "mss_chan_compact_act_f32": [P, I, P, I, I, I, I, P, P, P, P, P],
     "mss_chan_compact_weights_f32": [P, P, I, I, I, P, P, P],
     "mss_conv2d_kpad": [I],
@@ -117,11 +116,11 @@ SIGNATURES = {
     "mss_gemm_split_weights_bytes": [I, I, I],
     "mss_gemm_split_weights_bf16x3": [P, P, I, I, I, L, P],
     "mss_conv_split_weights_bf16x3": [P, P, I, I, I, P],
-    "mss_conv2d_pack_weights_f32": [P, P, I, I, I, I, I, I, I, P],
+    "mss_conv2d_pack_weights_f32": [P, P, I, I, I, I, I, I, I, P, I, I, P],
     "mss_conv2d_wgrad_workspace_bytes": [POINTER(MssConvArgs), I],
     "mss_conv2d_wgrad_f32": [POINTER(MssConvArgs), P, I, P, I, P, L, P],
     "mss_conv2d_wgrad_route": [POINTER(MssConvArgs), I],
-    "mss_conv2d_unpack_wgrad_f32": [P, P, I, I, I, I, I, I, I, P],
+    "mss_conv2d_unpack_wgrad_f32": [P, P, I, I, I, I, I, I, I, P, P, I, I, P],
     "mss_nchw_to_nhwc_pad_f32": [P, P, I, I, I, I, I, P],
     "mss_im2col3x3_c3_f32": [P, P, I, I, I, P],
     "mss_stem_conv_pool_f32": [P, P, P, I, I, I, I, P],
@@ -176,6 +175,7 @@ SIGNATURES = {
     "mss_wino_input_transform_upcat_f32": [P, I, I, P, I, I, I, I, I, I, I, I, P, P],
     "mss_wino_input_transform_aspp3_f32": [P, I, I, I, I, I, I, P, P, P, P, P],
     "mss_wino_input_transform_aspp3_src2_f32": [P, I, I, P, P, I, P, I, I, P, P, I, I, I, I, I, P, P, P, P, P, P, P],
+    "mss_wino_input_transform_aspp3_dropped_f32": [P, I, I, P, P, I, P, I, I, P, P, I, I, I, I, P, P, P, P, P, P, P],
     "mss_wino_output_transform_f32": [P, I, I, I, I, I, I, P, I, P, I, P, P],
     "mss_wino_output_stats_parts": [I, I, I, I, I, I],
     "mss_bn_stats_partials_f32": [P, L, I, P, P],

@@ -2,7 +2,8 @@
 // the dropped channels of sample n are exact zeros after the prologue, so the product only has to run over the K_n kept ones.
 //
 //   chan_compact_index_kernel   mask [N][C] -> idx [N][K_n] (ascending kept channels), count [N] = K_n, k_steps [N] = max(3, ceil(K_n/16)),
-//                               place [N][C]: the channel that goes to column p of the compacted rows, or -1 (below)
+//                               place [N][C]: the channel that goes to column p of the compacted rows, or -1 (below);
+//                               col [N][C] (optional): its inverse, the column channel c went to, or -1 for a dropped channel
 //   chan_compact_rows_kernel    rows [img][r][0..C) -> rows [img][r][0..16 k_steps[img]): column p = act(row[place[img][p]]), 0 where place is -1;
 //                               AFFINE: act = relu(v * sc + sh) (the expression of gemm.hip's finish_store), the activation side;
 //                               !AFFINE: act = identity with ONE source image for all samples, the weight side (w [Kpad][C] -> [N][Kpad][C])
@@ -25,7 +26,7 @@ constexpr int CC_NT = 256;
 
 __global__ __launch_bounds__(CC_NT) void chan_compact_index_kernel(const float* __restrict__ mask, int C, int* __restrict__ idx,
                                                                    int* __restrict__ place, int* __restrict__ count,
-                                                                   int* __restrict__ k_steps) {
+                                                                   int* __restrict__ k_steps, int* __restrict__ col) {
   __shared__ int part[CC_NT];
   const int n = blockIdx.x, tid = threadIdx.x;
   const int per = (C + CC_NT - 1) / CC_NT;             // consecutive channels per thread: thread order == channel order
@@ -45,7 +46,10 @@ __global__ __launch_bounds__(CC_NT) void chan_compact_index_kernel(const float* 
   int pos = part[tid] - kept;
   int* out = idx + (size_t)n * C;
   int* pl = place + (size_t)n * C;
+  int* cl = col ? col + (size_t)n * C : nullptr;        // optional inverse of place: the column channel c went to, or -1
   for (int c = c0; c < c1; ++c) pl[c] = -1;
+  if (cl)
+    for (int c = c0; c < c1; ++c) cl[c] = -1;           // a thread writes col only at its own channels
   __syncthreads();                                      // ... before any thread places a channel into another thread's columns
   for (int c = c0; c < c1; ++c)
     if (m[c] != 0.f) {
@@ -58,7 +62,9 @@ __global__ __launch_bounds__(CC_NT) void chan_compact_index_kernel(const float* 
         if (k && cq < c) --r;
         if (k && 2 * (q & 3) + ((q >> 2) & 1) < key) ++r;
       }
-      pl[8 * (r >> 3) + ((r & 7) >> 1) + 4 * (r & 1)] = c;
+      const int slot = 8 * (r >> 3) + ((r & 7) >> 1) + 4 * (r & 1);
+      pl[slot] = c;
+      if (cl) cl[c] = slot;
       out[pos++] = c;
     }
   if (tid == CC_NT - 1) {
@@ -186,12 +192,12 @@ int mss_chan_compact_wanted(const MssConvArgs* a) {
   return 1;
 }
 
-int mss_chan_compact_index(const float* mask, int N, int C, int* idx, int* place, int* count, int* k_steps, void* stream) {
+int mss_chan_compact_index(const float* mask, int N, int C, int* idx, int* place, int* count, int* k_steps, int* col, void* stream) {
   if (!mask || !idx || !place || !count || !k_steps) return MSS_ERR_BAD_ARG;
   if (N <= 0) return MSS_OK;
   if (C % 16 || C < 48) return MSS_ERR_UNSUPPORTED;     // 16 * k_steps <= C must hold with k_steps >= 3
   hipLaunchKernelGGL(chan_compact_index_kernel, dim3(N), dim3(CC_NT), 0, static_cast<hipStream_t>(stream), mask, C, idx, place,
-                     count, k_steps);
+                     count, k_steps, col);
   return mss_launch_status();
 }
 

@@ -302,8 +302,11 @@ int launch_conv_t(MssConvArgs& p, hipStream_t stream) {
 
 // [K][C][R][S] (PyTorch) -> [R*S][Kpad][Cp], zero padded. flip=1 builds the dgrad weights:
 // a conv from K channels back to C channels with the taps rotated 180 degrees.
+// col != nullptr (flip == 0): src is n_img tensors [n][K][C][R][S] whose channels from c0 on are per-image COMPACTED columns
+// (col[n][c - c0] = the column of image n that holds channel c, -1: none); dst gets, in original channel order, the sum over the
+// images in ascending n -- exact zero for a channel no image holds. The weight gradients of the dropped-channel ASPP products.
 __global__ void pack_weights_kernel(const float* __restrict__ src, float* __restrict__ dst, int K, int C,
-                                    int R, int S, int Kpad, int Cp, int flip) {
+                                    int R, int S, int Kpad, int Cp, int flip, const int* __restrict__ col, int n_img, int c0) {
   const size_t total = (size_t)R * S * Kpad * Cp;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
@@ -312,7 +315,13 @@ __global__ void pack_weights_kernel(const float* __restrict__ src, float* __rest
     int t = i / ((size_t)Cp * Kpad);
     int r = t / S, s = t % S;
     float val = 0.f;
-    if (!flip) {
+    if (col) {
+      if (k < K && c < C)
+        for (int n = 0; n < n_img; ++n) {
+          const int cc = c < c0 ? c : col[(size_t)n * (C - c0) + c - c0];
+          if (cc >= 0) val += src[((((size_t)n * K + k) * C + (c < c0 ? c : c0 + cc)) * R + r) * S + s];
+        }
+    } else if (!flip) {
       if (k < K && c < C) val = src[(((size_t)k * C + c) * R + r) * S + s];
     } else {
       // output channel index k runs over the conv's *input* channels (C of src), input index c over src's K
@@ -323,8 +332,28 @@ __global__ void pack_weights_kernel(const float* __restrict__ src, float* __rest
 }
 
 // [R*S][Kpad][Cp] packed gradient -> accumulate/assign into [K][C][R][S]
+// place != nullptr: dst is n_img tensors [n][K][C][R][S]; image n's gets src's channels [0, c0) as they are, then channel
+// c0 + place[n][p] in column c0 + p for p < 16 * k_steps[n] (place -1: zero), zeros behind -- the composed ASPP weights in the
+// per-image compacted column order of the dropped-channel products.
 __global__ void unpack_wgrad_kernel(const float* __restrict__ src, float* __restrict__ dst, int K, int C,
-                                    int R, int S, int Kpad, int Cp, int accumulate) {
+                                    int R, int S, int Kpad, int Cp, int accumulate, const int* __restrict__ place,
+                                    const int* __restrict__ k_steps, int n_img, int c0) {
+  if (place) {
+    const size_t per = (size_t)K * C * R * S, all = per * n_img;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < all; i += (size_t)gridDim.x * blockDim.x) {
+      const size_t e = i % per;
+      const int n = (int)(i / per);
+      const int s = e % S, r = (e / S) % R;
+      const int cc = (e / ((size_t)S * R)) % C, k = e / ((size_t)S * R * C);
+      int c = cc;                                           // source channel, -1: a zero column
+      if (cc >= c0) {
+        const int pc = cc - c0 < 16 * k_steps[n] ? place[(size_t)n * (C - c0) + cc - c0] : -1;
+        c = pc >= 0 ? c0 + pc : -1;
+      }
+      dst[i] = c >= 0 ? src[((size_t)(r * S + s) * Kpad + k) * Cp + c] : 0.f;
+    }
+    return;
+  }
   const size_t total = (size_t)K * C * R * S;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
@@ -1049,18 +1078,29 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ const float tn_zero_row[4096] = {0.f};              // the A operand of rows past the end of a split
 // AFFINE: x enters as relu(x * scale[c] + shift[c]) (the forward's BatchNorm + ReLU prologue, one affine for all rows), applied to the
 // registers at consume time -- bot_aspp's 1280 -> 256 weight gradient (deepv3.py:235-240 reads the BN+ReLU of the five ASPP branches)
-template <bool AFFINE = false>
+// PERIMG (batched, no splits): position-batch entry pb holds the rows of image pb % k_imgs alone, of which only the first
+// cend = 16 * (k_base + k_steps[image]) columns exist (the dropped-channel X' of the composed ASPP route). A job whose c tile starts
+// at or behind cend returns at once and leaves its tile of `out` unwritten; lanes whose columns lie behind cend inside a tile take
+// their B operand from the row of zeros, so those columns of the tile are exact zeros and nothing behind cend is read.
+template <bool AFFINE = false, bool PERIMG = false>
 __global__ __launch_bounds__(256, 1) void gemm_tn_direct_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                                 float* __restrict__ out, int P, int M, int K, int C, long long a_bs,
                                                                 long long b_bs, int Kpad, int Cp, int ktiles, int ctiles, int splits,
                                                                 int tps, long long total, long long full, float* __restrict__ tail_ws,
                                                                 const float* __restrict__ scale = nullptr,
-                                                                const float* __restrict__ shift = nullptr, int relu = 0, int lda = 0) {
+                                                                const float* __restrict__ shift = nullptr, int relu = 0, int lda = 0,
+                                                                const int* __restrict__ k_steps = nullptr, int k_base = 0,
+                                                                int k_imgs = 1) {
   if (lda <= 0) lda = K;               // row stride of A (dy): larger when dy is a channel slice of a wider buffer
   constexpr int KB = 4;                                        // 32-column blocks of dy per wave
   constexpr int TND = 8;                                       // row pairs per register block (two blocks: one consumed, one in flight)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long job = (long long)blockIdx.x * 4 + wave;
+  // PERIMG: the jobs behind an image's extent are the LAST c tiles of every (entry, k tile) -- with workgroups dealt round-robin to
+  // the 8 XCDs and 8 workgroups per (entry, k tile) at C = 4096 they would all land on the same two XCDs. An XCD owns a contiguous
+  // run of workgroups instead, as in gemm_nt_kernel: every XCD gets its share of live jobs, and the c tiles that read the same dY'
+  // rows share an L2. (Measured 8.30 -> 8.16 ms for the step's three launches, on two different boxes: not a proven gain. What keeps
+  // this form from being faster than the dense one is the granularity of its one-wave jobs)
+  const long long job = (long long)(PERIMG ? mss_xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x) * 4 + wave;
   if (job >= total) return;                                   // no barrier anywhere in this kernel
   // Two job layouts. full < 0: every (position, tile) is cut into `splits` row ranges (slab per split in `out`, reduced afterwards).
   // full >= 0 (TAIL plan, r04: more tiles than wave slots and not a multiple of them -- 36 x 2 x 32 = 2304 tiles on 1024 SIMDs are
@@ -1089,6 +1129,12 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_direct_kernel(const float* __r
   const int r0 = nsp > 1 ? sp * tps : 0, r1 = nsp > 1 ? (r0 + tps < M ? r0 + tps : M) : M;
   const float* a = A + (size_t)pb * a_bs + (size_t)(kt * (32 * KB) + KB * j);
   const float* b = B + (size_t)pb * b_bs + (size_t)(ct * 128 + 4 * j);
+  size_t b_ld = (size_t)C;
+  if (PERIMG) {
+    const int cend = 16 * (k_base + k_steps[pb % k_imgs]);
+    if (ct * 128 >= cend) return;                              // wave-uniform
+    if (ct * 128 + 4 * j >= cend) { b = tn_zero_row + 4 * j; b_ld = 0; }
+  }
   f32x16 acc[KB][4];
 #pragma unroll
   for (int i = 0; i < KB; ++i)
@@ -1110,7 +1156,7 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_direct_kernel(const float* __r
     const bool ok = row <= last;
     const size_t rr = (size_t)(ok ? row : last);
     va = *reinterpret_cast<const f32x4*>(ok ? a + rr * lda : az);  // a row past the end contributes A = 0: the product is zero
-    vb = *reinterpret_cast<const f32x4*>(b + rr * C);
+    vb = *reinterpret_cast<const f32x4*>(b + rr * (PERIMG ? b_ld : (size_t)C));
   };
   f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
   if (AFFINE) {
@@ -1439,6 +1485,15 @@ inline TnPlan tn_plan_direct(const MssConvArgs& p) {
 }
 int launch_wgrad_tn(const MssConvArgs& p, const float* dy, float* dwp, int Cp, float* ws, long long ws_bytes,
                     hipStream_t stream, int lddy = 0) {
+  if (p.k_steps) {
+    // per-image entries over channel-compacted columns: one whole-tile job per (entry, k tile, c tile), sized for the worst case
+    // (every column kept); the jobs behind an image's extent return at once. No splits, no scratch.
+    const long long total = (long long)p.batch * (p.K / 128) * (p.C / 128);
+    hipLaunchKernelGGL((gemm_tn_direct_kernel<false, true>), dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, dy, p.x, dwp, p.batch,
+                       p.M, p.K, p.C, p.y_bs, p.x_bs, p.Kpad, Cp, p.K / 128, p.C / 128, 1, p.M, total, -1ll, (float*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr, 0, lddy, p.k_steps, p.k_base, p.k_imgs);
+    return mss_launch_status();
+  }
   if (tn_direct(p)) {
     const TnPlan pl = tn_plan_direct(p);
     const int P = tn_batch(p);
@@ -1563,22 +1618,24 @@ int mss_conv2d_forward_route(const MssConvArgs* args) {
 int mss_conv2d_kpad(int K) { return K <= 64 ? 64 : ((K + 127) / 128) * 128; }
 
 int mss_conv2d_pack_weights_f32(const float* w, float* packed, int K, int C, int R, int S, int Kpad, int Cp,
-                                int flip, void* stream) {
+                                int flip, const int* col, int n_img, int c0, void* stream) {
   if (!w || !packed) return MSS_ERR_BAD_ARG;
+  if (col && (flip || n_img < 1 || c0 < 0 || c0 >= C)) return MSS_ERR_BAD_ARG;
   const size_t total = (size_t)R * S * Kpad * Cp;
   int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), w,
-                     packed, K, C, R, S, Kpad, Cp, flip);
+                     packed, K, C, R, S, Kpad, Cp, flip, col, n_img, c0);
   return mss_launch_status();
 }
 
 int mss_conv2d_unpack_wgrad_f32(const float* packed, float* grad, int K, int C, int R, int S, int Kpad, int Cp,
-                                int accumulate, void* stream) {
+                                int accumulate, const int* place, const int* k_steps, int n_img, int c0, void* stream) {
   if (!grad || !packed) return MSS_ERR_BAD_ARG;
-  const size_t total = (size_t)K * C * R * S;
+  if (place && (accumulate || !k_steps || n_img < 1 || c0 < 0 || c0 >= C)) return MSS_ERR_BAD_ARG;
+  const size_t total = (size_t)K * C * R * S * (place ? n_img : 1);
   int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), packed,
-                     grad, K, C, R, S, Kpad, Cp, accumulate);
+                     grad, K, C, R, S, Kpad, Cp, accumulate, place, k_steps, n_img, c0);
   return mss_launch_status();
 }
 
@@ -1607,7 +1664,7 @@ int mss_conv2d_wgrad_route(const MssConvArgs* args, int lddy) {
 long long mss_conv2d_wgrad_workspace_bytes(const MssConvArgs* args, int Cp) {
   MssConvArgs p = *args;
   p.M = p.N * p.OH * p.OW;
-  if (p.M <= 0) return 0;
+  if (p.M <= 0 || p.k_steps) return 0;                     // (the per-image TN form: whole-tile jobs, no scratch)
   if (const int wide = wgrad_wide_part(p, Cp)) {           // both parts run one after the other on the same scratch
     MssConvArgs a = p, b = p;
     a.K = a.Kpad = wide;
@@ -1654,6 +1711,13 @@ int mss_conv2d_wgrad_f32(MssConvArgs* args, const float* dy, int lddy, float* dw
   if (p.M <= 0) return MSS_OK;
   if (p.batch > 1 && (p.R * p.S != 1 || p.batch > 65535)) return MSS_ERR_BAD_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (p.k_steps) {               // MssConvArgs.k_imgs: the LDS-free TN kernel is the only one that has the per-image form
+    if (p.k_imgs < 1 || p.batch < 2 || p.batch % p.k_imgs || p.k_base < 0 || p.k_base * 16 > p.C || p.R * p.S != 1 || p.N != 1 || p.H != 1 ||
+        p.K % 128 || p.C % 128 || p.K > 4096 || p.Kpad != p.K || Cp != p.C || p.ldx != p.C || lddy != p.K || p.x_bs % 4 || p.y_bs % 4 ||
+        p.in_scale || p.in_shift || p.in_relu || p.route)
+      return MSS_ERR_UNSUPPORTED;
+    return launch_wgrad_tn(p, dy, dwp, Cp, ws, ws_bytes, s, lddy);
+  }
   if (const int wide = wgrad_wide_part(p, Cp)) {
     MssConvArgs a = *args, b = *args;
     a.K = a.Kpad = wide;

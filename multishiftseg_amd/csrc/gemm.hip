@@ -46,7 +46,8 @@ static_assert(NKC == 2, "the step body below is written for two 8-k chunks");
 // K-steps over the weights at p.w + img * p.w_img_stride, img = (mt * BM) / p.H (p.H = rows per image; tiles never straddle images).
 // The product behind csrc/chan_compact.hip: Dropout2d-zeroed input channels are compacted away per sample, so image n multiplies
 // only its kept channels. Both numbers are uniform over a tile: k_steps[img] is read where the tile's offsets are formed (setup_off),
-// the K-step body gains one scalar select.
+// the K-step body gains one scalar select. With p.k_imgs > 0 the images are the batch entries' (entry b belongs to image b % k_imgs) and
+// every image runs p.k_base further K-steps in front.
 template <bool AFFINE, int VARIANT, int BN, bool PERIMG = false>
 __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvArgs p, long long first_tile, long long total_tiles,
                                                                         int tiles_per_batch, int group_m) {
@@ -91,8 +92,11 @@ __global__ __launch_bounds__(NT, BN == 256 ? 2 : 3) void gemm_nt_kernel(MssConvA
     for (int j = 0; j < B_LD; ++j)
       bo[j] = (unsigned)(((size_t)b * p.w_bs + (size_t)(nt * BN + row0 + j * RPP) * p.C + chunk * 4) * sizeof(float));
     if (PERIMG) {
-      const int img = (mt * BM) / p.H;
-      nit = p.k_steps[img];
+      // p.k_imgs > 0 (the Winograd-domain products of the composed ASPP route): batch entry b = (position, image) holds ONE image's
+      // rows, so a row tile never straddles images and the entry's weights are its own (w_bs; w_img_stride is 0); the first p.k_base
+      // K-steps are columns every image has (the factor without Dropout2d)
+      const int img = p.k_imgs > 0 ? b % p.k_imgs : (mt * BM) / p.H;
+      nit = p.k_steps[img] + p.k_base;
       const unsigned wo = (unsigned)((size_t)img * (size_t)p.w_img_stride * sizeof(float));
 #pragma unroll
       for (int j = 0; j < B_LD; ++j) bo[j] += wo;
@@ -385,9 +389,35 @@ int mss_gemm_nt_dispatch(MssConvArgs p, void* stream) {
     // the per-image product behind csrc/chan_compact.hip: image n = rows [n * OH * OW, (n + 1) * OH * OW) runs k_steps[n] K-steps
     // over its own weights w + n * w_img_stride. It exists on this kernel only (variant 3, no prologue: the compaction pass applied
     // it), so a shape that does not qualify is an error, never another route.
-    if (!mss_gemm_nt_eligible(p) || p.in_scale || p.w_split || p.batch > 1 || p.K <= 64 || (p.OH * p.OW) % BM || p.C / BK < 3 ||
-        p.w_img_stride % 4 || p.w_img_stride < 0)
+    if (!mss_gemm_nt_eligible(p) || p.in_scale || p.w_split || p.K <= 64 || p.C / BK < 3 || p.w_img_stride % 4 || p.w_img_stride < 0 ||
+        p.k_base < 0 || p.k_imgs < 0)
       return MSS_ERR_UNSUPPORTED;
+    hipStream_t ps = static_cast<hipStream_t>(stream);
+    if (p.k_imgs > 0) {
+      // batch entries of one image each (the dropped-channel Winograd-domain products): p.M rows per entry, the last row tile of an
+      // entry partial; k_base + k_steps[b % k_imgs] K-steps, >= 3 since k_steps is
+      if (p.batch < 2 || p.batch % p.k_imgs || p.w_img_stride || p.N != 1 || p.k_base * BK > p.C) return MSS_ERR_UNSUPPORTED;
+      p.H = p.M;
+      p.mtiles = mss_cdiv(p.M, BM);
+      p.ntiles = mss_cdiv(p.K, 128);
+      if (p.Kpad < p.ntiles * 128) return MSS_ERR_BAD_ARG;
+      if ((unsigned long long)((long long)(p.batch - 1) * p.x_bs + (long long)p.M * p.ldx) * 4ull >= 0xffffffffull ||
+          (unsigned long long)((long long)(p.batch - 1) * p.w_bs + (long long)p.Kpad * p.C) * 4ull >= 0xffffffffull)
+        return MSS_ERR_UNSUPPORTED;
+      // tile width: the dense products' rule (below), on this launch's tile counts
+      const long long t256 = (long long)p.mtiles * (p.K / 256) * p.batch;
+      bool wide = p.K % 256 == 0 && t256 >= 1024 && p.C >= 256;
+      if (wide) {
+        const double ew = (double)t256 / (double)(((t256 + 511) / 512) * 512), en = (double)(2 * t256) / (double)(((2 * t256 + 767) / 768) * 768);
+        if (ew < 0.8 && en > ew + 0.15) wide = false;
+      }
+      if (wide) {
+        p.ntiles = p.K / 256;
+        return launch_gemm<false, 3, 256, true>(p, ps);
+      }
+      return launch_gemm<false, 3, 128, true>(p, ps);
+    }
+    if (p.batch > 1 || (p.OH * p.OW) % BM) return MSS_ERR_UNSUPPORTED;
     p.H = p.OH * p.OW;                                    // rows per image
     p.mtiles = mss_cdiv(p.M, BM);
     p.ntiles = mss_cdiv(p.K, 128);
@@ -395,7 +425,6 @@ int mss_gemm_nt_dispatch(MssConvArgs p, void* stream) {
     if ((unsigned long long)p.M * p.ldx * 4ull >= 0xffffffffull ||
         (unsigned long long)((long long)(p.N - 1) * p.w_img_stride + (long long)p.Kpad * p.C) * 4ull >= 0xffffffffull)
       return MSS_ERR_UNSUPPORTED;
-    hipStream_t ps = static_cast<hipStream_t>(stream);
     // tile width: the dense rule below without its last-round refinements (the per-image step counts make rounds uneven anyway)
     if (p.K % 256 == 0 && (long long)p.mtiles * (p.K / 256) >= 1024 && p.C >= 256) {
       p.ntiles = p.K / 256;

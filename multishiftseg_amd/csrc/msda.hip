@@ -1237,13 +1237,6 @@ int mss_msda_prepare_backward_ld_f32(const float* attn_weight, const float* grad
   return mss_launch_status();
 }
 
-int mss_msda_prepare_backward_f32(const float* attn_weight, const float* grad_attn, const float* grad_loc,
-                                  const int64_t* spatial_shapes, int N, int Lq, int M, int L, int P, float* grad_offsets,
-                                  float* grad_logits, void* stream) {
-  return mss_msda_prepare_backward_ld_f32(attn_weight, grad_attn, grad_loc, spatial_shapes, N, Lq, M, L, P, grad_offsets,
-                                          (long long)M * 2 * L * P, grad_logits, (long long)M * L * P, stream);
-}
-
 int mss_msda_backward_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
                           const double* sampling_loc, const double* attn_weight, const double* grad_out, int N,
                           int S, int M, int D, int L, int Lq, int P, double* grad_value, double* grad_loc,

@@ -231,7 +231,7 @@ class DeepWV3Plus(nn.Module):
         st3 = K.bn_fold(c.bn3[0], o2, train)
         aff3, mask = self._dropout_affine(st3, blk, name, a.N, want_mask=True)
         if factors:
-            return K.FactoredAct(a, aff1, o2, aff3)
+            return K.FactoredAct(a, aff1, o2, aff3, mask)
         pw3 = K.packed(c.conv3.weight)
         if mask is not None and K.dropout_compact_wanted(o2, pw3, aff3, shortcut):
             # the dropped channels are exact zeros behind the prologue: each sample multiplies its kept channels only
@@ -283,24 +283,34 @@ class DeepWV3Plus(nn.Module):
             return False
         return K.aspp_tiles(a.H, a.W, c_out, _ASPP_RATES, [feats[i][0].weight for i in (1, 2, 3)]) is not None
 
-    def _aspp_rows(self, tensors, pw):
+    def _aspp_rows(self, tensors, pw, dropped=None, keep_rows=None):
         """The four ASPP-shaped tensors [K][C][R][S] packed tap-major ([R*S][Kpad][C] each, 7168 rows of C in all), one 1x1 product
-        of the rows with `pw`, and the result unpacked into four tensors of the same shapes."""
+        of the rows with `pw`, and the result unpacked into four tensors of the same shapes. A five-dimensional tensor is a weight
+        gradient of the dropped-channel products ([N][K][C][3][3] in per-image compacted columns, kernels.conv3x3_wgrad_dropped): its
+        pack gathers the columns back to their channels and adds the images (`dropped`: that step's kernels.AsppDropped).
+        keep_rows (a list): also receives (rows of the product, row pitch, Kpad) per tensor, views of the one result buffer."""
         dev = tensors[0].device
-        C = tensors[0].shape[1]
-        geo = [(t.shape[0], t.shape[2], t.shape[3], K._lib.value("mss_conv2d_kpad", t.shape[0])) for t in tensors]
+        C = tensors[0].shape[-3]
+        geo = [(t.shape[-4], t.shape[-2], t.shape[-1], K._lib.value("mss_conv2d_kpad", t.shape[-4])) for t in tensors]
         rows = [r * s_ * kp for _, r, s_, kp in geo]
         src = Act.empty(1, 1, sum(rows), C, dev)
         r0 = 0
         for t, (k, r, s_, kp), n in zip(tensors, geo, rows):
-            K.call("mss_conv2d_pack_weights_f32", K.ptr(t.detach().contiguous()), K.ptr(src.buf[0, 0, r0:r0 + n]), k, C, r, s_, kp, C, 0)
+            if t.dim() == 5:
+                K.call("mss_conv2d_pack_weights_f32", K.ptr(t.detach().contiguous()), K.ptr(src.buf[0, 0, r0:r0 + n]), k, C, r, s_, kp, C, 0,
+                       K.ptr(dropped.col), t.shape[0], dropped.C0)
+            else:
+                K.call("mss_conv2d_pack_weights_f32", K.ptr(t.detach().contiguous()), K.ptr(src.buf[0, 0, r0:r0 + n]), k, C, r, s_, kp, C, 0,
+                       None, 0, 0)
             r0 += n
         dst = K.conv2d(src, pw)
         out, r0 = [], 0
         for t, (k, r, s_, kp), n in zip(tensors, geo, rows):
             g = torch.empty((k, pw.K, r, s_), device=dev, dtype=torch.float32)
-            K.call("mss_conv2d_unpack_wgrad_f32", K.ptr(dst.buf[0, 0, r0:r0 + n]), K.ptr(g), k, pw.K, r, s_, kp, dst.ld, 0)
+            K.call("mss_conv2d_unpack_wgrad_f32", K.ptr(dst.buf[0, 0, r0:r0 + n]), K.ptr(g), k, pw.K, r, s_, kp, dst.ld, 0, None, None, 0, 0)
             out.append(g)
+            if keep_rows is not None:
+                keep_rows.append((dst.buf[0, 0, r0:r0 + n], dst.ld, kp))
             r0 += n
         return out
 
@@ -319,9 +329,10 @@ class DeepWV3Plus(nn.Module):
         wkey = tuple((t._version, t.data_ptr()) for t in ws)
         if cc["wkey"] != wkey:
             with K._Timed("aspp_compose", 2.0 * sum(t.numel() for t in ws) * cc["Mt"].K, ("compose", len(ws))):
-                wc = self._aspp_rows(ws, cc["Mt"])
+                rows = []
+                wc = self._aspp_rows(ws, cc["Mt"], keep_rows=rows)
             c0 = cc["c0"]
-            cc.update(wkey=wkey, wc=wc, half0=K.pack_weight(wc[0][:, :c0].contiguous()), half1=K.pack_weight(wc[0][:, c0:].contiguous()))
+            cc.update(wkey=wkey, wc=wc, rows=rows, half0=K.pack_weight(wc[0][:, :c0].contiguous()), half1=K.pack_weight(wc[0][:, c0:].contiguous()))
         return cc
 
     # ---- decoder + heads -------------------------------------------------------------------------
@@ -361,10 +372,26 @@ class DeepWV3Plus(nn.Module):
         # the three dilated branches read the same 1 GB map: ONE kernel makes all three Winograd-domain inputs from a single read
         # (kernels.aspp_input_transforms); None: shapes / policy outside it, each branch transforms for itself as before
         max_bytes = None if (keep and xt_bytes < (40 << 30)) else (40 << 30)
+        drop = None
         if comp is None:
             pre_xt = K.aspp_input_transforms(x, _ASPP_RATES, wts[1:], pair_tile, max_bytes=max_bytes)
             pooled = K.gap(x)
         else:
+            # train mode: the Dropout2d-zeroed channels of v are exact zeros in all three products -- each image multiplies its kept
+            # channels only (kernels.AsppDropped; MSS_ASPP_DROPOUT_COMPACT=0, the split route and shapes outside the gate: dense)
+            pre_xt = gap_w = None
+            if not pair_tile and K.aspp_dropped_wanted(fx, wts[1:]):
+                drop = K.AsppDropped(fx)
+                pre_xt, gap_w = K.aspp_input_transforms(fx, _ASPP_RATES, wts[1:], 0, max_bytes=max_bytes, want_gap=True, dropped=drop)
+                if pre_xt is None and os.environ.get("MSS_WINO_ASPP3", "1") == "0":
+                    # the switch's second formulation, as on the dense route: the compacted map materialised, three separate transforms
+                    pre_xt, gap_w = K.aspp_dropped_separate_transforms(fx, _ASPP_RATES, wts[1:], drop, max_bytes=max_bytes)
+                if pre_xt is None:
+                    drop = None
+        if comp is not None and drop is not None:
+            x = fx
+            pooled = K.conv2d(Act(gap_w.view(N, 1, 1, 4096)), comp["M"]).buf.view(N, 4096)
+        elif comp is not None:
             # the same kernel on the two factors, which also leaves GAP(w); GAP(x) = M . GAP(w). Where X' is not taken from it
             # (MSS_WINO_ASPP3=0, over budget) or is not all kept for the weight gradients, w is materialised and is the map the
             # branches transform for themselves
@@ -406,7 +433,13 @@ class DeepWV3Plus(nn.Module):
                 # keep the Winograd-domain input X' for this layer's weight gradient when the three of them fit
                 # comfortably (2.25-4x the 4096-channel map each: 10.6 GB in all at 2x1024x2048)
                 kx = {} if (keep and feat[0].weight.requires_grad and xt_bytes < (40 << 30)) else None
-                K.conv3x3(x, wts[i], dil=rate, out=sl, keep_xt=kx, want_stats=train, xt=pre_xt[i - 1] if pre_xt else None)
+                if drop is not None:
+                    rows, ld, kp = comp["rows"][i]
+                    ww = K.aspp_dropped_weights(rows, wts[i].shape[0], wts[i].shape[1], kp, ld, K.WINO_TILE_OF_P[pre_xt[i - 1].shape[0]], drop)
+                    K.conv3x3_dropped(x, ww, rate, sl, kx, train, pre_xt[i - 1], drop)
+                    del ww
+                else:
+                    K.conv3x3(x, wts[i], dil=rate, out=sl, keep_xt=kx, want_stats=train, xt=pre_xt[i - 1] if pre_xt else None)
                 if pre_xt:
                     pre_xt[i - 1] = None                  # the layer owns it now (kept for the weight gradient, or freed)
                 aspp_xt[i] = kx.get("xt") if kx else None
@@ -441,7 +474,7 @@ class DeepWV3Plus(nn.Module):
                                       want_logit=want_logit)
         saved = None
         if keep:
-            saved = dict(aspp_xt=aspp_xt, x=x, fx=fx, comp=comp, m2=m2, raw=raw, scale=scale, shift=shift, states=states, pooled_act=pooled_act,
+            saved = dict(aspp_xt=aspp_xt, x=x, fx=fx, comp=comp, drop=drop, m2=m2, raw=raw, scale=scale, shift=shift, states=states, pooled_act=pooled_act,
                          u0_rows=u0_rows, dec0=dec0, f0=f0, st_f0=st_f0, f1=f1, st_f1=st_f1, dec12=dec12, size=size, final_xt=final_xt)
         return score, logit, saved
 
@@ -528,7 +561,7 @@ class DeepWV3Plus(nn.Module):
             if any(need[n] for n in names if n.startswith("aspp")):
                 d_act = K.conv2d(d_up, K.packed(self.bot_aspp.weight, flip=True))
                 states = s["states"]
-                comp, fx = s["comp"], s["fx"]
+                comp, fx, drop = s["comp"], s["fx"], s["drop"]
                 held = {}          # composed route: this loop's gradients, handed on in its own order once the four are projected
                 out = grads if comp is None else held
                 # the three dilated branches first (37.7 MB of gradient each), the two 4 MB branches last: under data parallelism the
@@ -548,6 +581,8 @@ class DeepWV3Plus(nn.Module):
                                  K.conv2d_wgrad(fx.a1, draw, 256, fx.a1.C, 1, 1, in_affine=fx.aff1, in_relu=True)], dim=1)
                         elif i == 0:
                             out[p + ".0.weight"] = K.conv2d_wgrad(x, draw, 256, 4096, 1, 1)
+                        elif drop is not None and s["aspp_xt"].get(i) is not None:
+                            out[p + ".0.weight"] = K.conv3x3_wgrad_dropped(x, draw, 256, 4096, _ASPP_RATES[i - 1], s["aspp_xt"].pop(i), drop)
                         else:
                             out[p + ".0.weight"] = K.conv3x3_wgrad(x, draw, 256, 4096, dil=_ASPP_RATES[i - 1],
                                                                    xt=s["aspp_xt"].pop(i, None))
@@ -556,8 +591,9 @@ class DeepWV3Plus(nn.Module):
                     # (tap-major rows, spatial domain) in ONE product
                     keys = [f"aspp.features.{i}.0.weight" for i in range(4) if f"aspp.features.{i}.0.weight" in held]
                     if keys:
-                        with K._Timed("aspp_compose", 2.0 * sum(held[k].numel() for k in keys) * comp["M"].K, ("project", len(keys))):
-                            for k, g in zip(keys, self._aspp_rows([held[k] for k in keys], comp["M"])):
+                        flops = 2.0 * sum(held[k].numel() // (held[k].shape[0] if held[k].dim() == 5 else 1) for k in keys) * comp["M"].K
+                        with K._Timed("aspp_compose", flops, ("project", len(keys))):
+                            for k, g in zip(keys, self._aspp_rows([held[k] for k in keys], comp["M"], dropped=drop)):
                                 held[k] = g
                     for k, g in held.items():
                         grads[k] = g

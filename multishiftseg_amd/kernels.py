@@ -150,7 +150,7 @@ def pack_weight(w, flip=False, min_c=16):
     Kpad = _lib.value("mss_conv2d_kpad", k_out)
     Cp = _round_up(max(c_in, min_c), 16)
     t = torch.empty((R * S, Kpad, Cp), device=w.device, dtype=torch.float32)
-    call("mss_conv2d_pack_weights_f32", ptr(w), ptr(t), K, C, R, S, Kpad, Cp, 1 if flip else 0)
+    call("mss_conv2d_pack_weights_f32", ptr(w), ptr(t), K, C, R, S, Kpad, Cp, 1 if flip else 0, None, 0, 0)
     return PackedWeight(t, k_out, c_in, R, S, Kpad, Cp)
 
 
@@ -331,18 +331,20 @@ def dropout_compact_wanted(x, pw, in_affine, res=None):
     return bool(_lib.value("mss_chan_compact_wanted", ctypes.byref(a)))
 
 
-def chan_compact_index(mask):
+def chan_compact_index(mask, want_col=False):
     """mask [N][C] (device fp32, != 0: kept) -> (idx [N][C] int32: ascending kept channels in the first count[n] entries of row n,
     count [N], k_steps [N] = max(3, ceil(count / 16)), place [N][C]: the channel that goes to each column of the compacted rows
-    or -1, in the order that makes the compacted product add its terms as the dense one does). One launch, nothing read back."""
+    or -1, in the order that makes the compacted product add its terms as the dense one does). One launch, nothing read back.
+    want_col: a fifth answer, col [N][C] -- the inverse of place: the column each channel went to, -1 for a dropped one."""
     N, C = mask.shape
     assert mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous()
     # int32 contents in float allocations: of `idx` only the first count[n] entries of a row are ever written or read
     idx = torch.empty((N, C), device=mask.device, dtype=torch.float32).view(torch.int32)
     place = torch.empty((N, C), device=mask.device, dtype=torch.float32).view(torch.int32)
     meta = torch.empty((2, N), device=mask.device, dtype=torch.float32).view(torch.int32)
-    call("mss_chan_compact_index", ptr(mask), N, C, ptr(idx), ptr(place), ptr(meta[0]), ptr(meta[1]))
-    return idx, meta[0], meta[1], place
+    col = torch.empty((N, C), device=mask.device, dtype=torch.float32).view(torch.int32) if want_col else None
+    call("mss_chan_compact_index", ptr(mask), N, C, ptr(idx), ptr(place), ptr(meta[0]), ptr(meta[1]), ptr(col))
+    return (idx, meta[0], meta[1], place, col) if want_col else (idx, meta[0], meta[1], place)
 
 
 def conv2d_dropped(x, pw, mask, in_affine, res=None, want_stats=False, out_relu=False):
@@ -404,7 +406,7 @@ def conv2d_wgrad(x, dy, K, C, R, S, stride=1, dil=1, pad=0, in_affine=None, in_r
     with _Timed(_wgrad_kind(a, dy.ld), 2.0 * x.N * dy.H * dy.W * K * C * R * S, (x.N, x.H, x.W, C, K, R, stride, dil)):
         call("mss_conv2d_wgrad_f32", ctypes.byref(a), dy.ptr, dy.ld, ptr(dwp), Cp, ptr(ws), ws_bytes)
     grad = torch.empty((K, C, R, S), device=x.buf.device, dtype=torch.float32)
-    call("mss_conv2d_unpack_wgrad_f32", ptr(dwp), ptr(grad), K, C, R, S, Kpad, Cp, 0)
+    call("mss_conv2d_unpack_wgrad_f32", ptr(dwp), ptr(grad), K, C, R, S, Kpad, Cp, 0, None, None, 0, 0)
     return grad
 
 
@@ -585,9 +587,10 @@ def _set_wino_w(a, ww):
     a.w = ptr(ww.t)
 
 
-def _wino_gemm_and_output(xt, ww, N, H, W, dil, res, out, keep_xt, want_stats):
+def _wino_gemm_and_output(xt, ww, N, H, W, dil, res, out, keep_xt, want_stats, dropped=None):
     """Steps 2 and 3 of the Winograd convolution on a transformed input X' [P][T][C]: the batched MFMA products and the output
-    transform (+ residual, + BatchNorm partial sums)."""
+    transform (+ residual, + BatchNorm partial sums). dropped (an AsppDropped; ww then holds one U per image, [P][N][Kpad][C]): the
+    batch entries are (position, image) and image n multiplies its first C0 + 16 k_steps[n] columns only."""
     C, K, ts = ww.C, ww.K, ww.tile
     P, T = xt.shape[0], xt.shape[1]
     dev = xt.device
@@ -607,8 +610,19 @@ def _wino_gemm_and_output(xt, ww, N, H, W, dil, res, out, keep_xt, want_stats):
     split = K - rem if (K > 128 and 0 < rem <= 64) else 0     # e.g. 304 = 256 + 48: narrow tail on the 64-wide tile
     if split:
         a.K = split
+    executed = float(T) * C
+    if dropped is not None:
+        assert not split and T % N == 0 and dropped.N == N and ww.Kpad == K
+        Ti = T // N
+        a.W = a.OW = Ti
+        a.batch, a.x_bs, a.y_bs = P * N, Ti * C, Ti * K
+        a.w_split = None
+        a.k_steps, a.k_base, a.k_imgs = ptr(dropped.k_steps), dropped.C0 // 16, N
+        executed = float(Ti) * dropped.columns()
     _set_wino_w(a, ww)
-    with _Timed(_fwd_kind(a), 2.0 * P * T * C * K, (P, 1, T, C, K, 1, 1, 1)):   # the MFMA work actually executed
+    # (bench.py unpacks this tag as eight numbers; the dropped form reports the mean number of columns an image's rows hold)
+    tag = (P, 1, T, C if dropped is None else int(dropped.columns() / N), K, 1, 1, 1)
+    with _Timed(_fwd_kind(a), 2.0 * P * executed * K, tag):   # the MFMA work actually executed
         call("mss_conv2d_forward_f32", ctypes.byref(a))
         if split:
             a.K, a.Kpad = rem, ww.Kpad - split
@@ -722,11 +736,12 @@ class FactoredAct:
     two factors u = relu(a0 * aff0) and v = relu(a1 * aff1) (aff1 per sample under Dropout2d), which stand for the map
     w = [u ; v] of C = a0.C + a1.C channels. Has the shape attributes of an Act so that the Winograd wrappers, which only read x's
     shape once they are handed X', take it in x's place."""
-    __slots__ = ("a0", "aff0", "a1", "aff1", "N", "H", "W", "C", "buf")
+    __slots__ = ("a0", "aff0", "a1", "aff1", "mask", "N", "H", "W", "C", "buf")
 
-    def __init__(self, a0, aff0, a1, aff1):
+    def __init__(self, a0, aff0, a1, aff1, mask=None):
         assert (a0.N, a0.H, a0.W) == (a1.N, a1.H, a1.W)
         self.a0, self.aff0, self.a1, self.aff1 = a0, aff0, a1, aff1
+        self.mask = mask           # the Dropout2d mask [N, a1.C] folded into aff1 (train mode), or None: what aspp_dropped reads
         self.N, self.H, self.W, self.C, self.buf = a0.N, a0.H, a0.W, a0.C + a1.C, a0.buf
 
     def materialise(self):
@@ -766,7 +781,85 @@ def aspp_tiles(H, W, C, rates, weights):
     return tiles
 
 
-def aspp_input_transforms(x, rates, weights, pair_tile=0, max_bytes=None, want_gap=False):
+class AsppDropped:
+    """One step's channel compaction of a FactoredAct's second factor v (its Dropout2d mask): what the three dilated ASPP products,
+    their weight gradients and the transform between them share. place / col / k_steps as chan_compact_index gives them (all on the
+    device: nothing is read back); xc: v with its prologue applied, channel-compacted per image (mss_chan_compact_act_f32)."""
+    __slots__ = ("N", "C0", "C1", "place", "col", "count", "k_steps", "xc")
+
+    def __init__(self, fx):
+        a1 = fx.a1
+        sc, sh = fx.aff1
+        self.N, self.C0, self.C1 = fx.N, fx.a0.C, a1.C
+        _idx, self.count, self.k_steps, self.place, self.col = chan_compact_index(fx.mask, want_col=True)
+        self.xc = Act.empty(a1.N, a1.H, a1.W, a1.C, a1.buf.device)
+        hw = a1.H * a1.W
+        kept = float(self.count.sum().item()) if _profile is not None else 0.0
+        with _Timed("chan_compact", 4.0 * hw * (self.N * self.C1 + kept), ("act", self.N, a1.H, a1.W, self.C1)):
+            call("mss_chan_compact_act_f32", a1.ptr, a1.ld, self.xc.ptr, self.xc.ld, self.N, hw, self.C1, ptr(self.place), ptr(self.k_steps),
+                 ptr(sc), ptr(sh))
+
+    def columns(self):
+        """Sum over the images of the columns their rows hold (profiling pass only: reads the counts back; else the dense number)."""
+        if _profile is None:
+            return float(self.N * (self.C0 + self.C1))
+        return float(self.N * self.C0 + 16 * int(self.k_steps.sum().item()))
+
+
+def aspp_dropped_wanted(fx, weights):
+    """True where the composed ASPP route leaves the Dropout2d-zeroed channels of its second factor out of the three dilated branches
+    (MSS_ASPP_DROPOUT_COMPACT, default 1): native route, a train-mode mask with its per-sample affine, C0 % 16 == 0, 48 <= C1 <= 2048,
+    C1 % 16 == 0, (C0 + C1) % 128 == 0, every weight's K a multiple of 128 and at most 4096. Everything else keeps the dense products."""
+    if os.environ.get("MSS_ASPP_DROPOUT_COMPACT", "1") == "0" or gemm_route() == "bf16x3":
+        return False
+    if not isinstance(fx, FactoredAct) or fx.mask is None or fx.aff1[0].dim() != 2 or fx.aff0[0].dim() != 1:
+        return False
+    c0, c1 = fx.a0.C, fx.a1.C
+    if c0 % 16 or c1 % 16 or c1 < 48 or c1 > 2048 or (c0 + c1) % 128 or tuple(fx.mask.shape) != (fx.N, c1):
+        return False
+    return all(w.shape[0] % 128 == 0 and w.shape[0] <= 4096 and w.shape[1] == c0 + c1 for w in weights)
+
+
+def aspp_dropped_separate_transforms(fx, rates, weights, dropped, max_bytes=None):
+    """The second formulation of the dropped-channel transform (MSS_WINO_ASPP3=0, as for the dense route): the compacted map
+    [u ; compacted v] is materialised with its 4096-column pitch and each dilation runs the plain input transform on it; GAP(w) comes
+    from the two-source kernel's sums-only mode. The columns an image's rows hold get the bits of the single-read kernel; the columns
+    behind them are transformed too (zeros), which nothing reads. (xts, gap) or (None, None) outside the same bounds."""
+    N, H, W, C = fx.N, fx.H, fx.W, fx.C
+    tiles = aspp_tiles(H, W, C, rates, weights)
+    if tiles is None:
+        return None, None
+    Ts = [_lib.value("mss_wino_num_tiles", N, H, W, r, t) for r, t in zip(rates, tiles)]
+    Ps = [(t + 2) ** 2 for t in tiles]
+    if any(4 * p * t * C >= 0xffffffff or t % N or p * N > 65535 for p, t in zip(Ps, Ts)):
+        return None, None
+    if max_bytes is not None and 4.0 * sum(p * t for p, t in zip(Ps, Ts)) * C > max_bytes:
+        return None, None
+    _none, gap = aspp_input_transforms(fx, rates, weights, 0, max_bytes=0, want_gap=True)
+    if gap is None:
+        return None, None
+    dev = fx.buf.device
+    wm = Act.zeros(N, H, W, C, dev)
+    u = wm.slice(0, fx.a0.C)
+    call("mss_affine_relu_nhwc_f32", fx.a0.ptr, fx.a0.ld, u.ptr, u.ld, fx.a0.M, fx.a0.C, ptr(fx.aff0[0]), ptr(fx.aff0[1]), 1)
+    hw = H * W
+    ks = dropped.k_steps
+    # v's compacted columns: what the compaction pass wrote, image by image; 16 * k_steps[n] is a device value, so whole rows are
+    # copied from a zero-filled compaction buffer (torch glue on a test route)
+    xc0 = Act.zeros(N, H, W, fx.a1.C, dev)
+    call("mss_chan_compact_act_f32", fx.a1.ptr, fx.a1.ld, xc0.ptr, xc0.ld, N, hw, fx.a1.C, ptr(dropped.place), ptr(ks), ptr(fx.aff1[0]),
+         ptr(fx.aff1[1]))
+    wm.buf[..., fx.a0.C:] = xc0.buf
+    xts = []
+    for r, t, p, T in zip(rates, tiles, Ps, Ts):
+        xt = torch.empty((p, T, C), device=dev, dtype=torch.float32)
+        with _Timed("wino_transform", 4.0 * (N * hw * C + p * T * C), ("input", N, H, W, C, r, t)):
+            call("mss_wino_input_transform_f32", wm.ptr, wm.ld, N, H, W, C, r, t, None, None, 0, ptr(xt))
+        xts.append(xt)
+    return xts, gap
+
+
+def aspp_input_transforms(x, rates, weights, pair_tile=0, max_bytes=None, want_gap=False, dropped=None):
     """X' of the ONE map `x` for the three dilated 3x3 branches of ASPP (deepv3.py:84-92; rates d, 2d, 3d) from a single read of x
     (mss_wino_input_transform_aspp3_f32): bit-identical to the three separate input transforms, 1 x instead of 3 x 1.07 GB read at
     2 x 128 x 256 x 4096. Returns [xt_d, xt_2d, xt_3d] -- with pair_tile (conv3x3_pair_tile) the first two are the halves of ONE
@@ -792,6 +885,10 @@ def aspp_input_transforms(x, rates, weights, pair_tile=0, max_bytes=None, want_g
         # the backward passes its budget, beyond which each branch transforms for itself again with one X' live at a time
         if max_bytes is not None and 4.0 * sum(p * t for p, t in zip(Ps, Ts)) * C > max_bytes:
             want_xt = False
+    if dropped is not None:
+        # the 32-bit operand offsets of the per-image products and their 65535 batch entries: outside them the dense form runs
+        if not want_xt or pair_tile or not want_gap or any(4 * p * t * C >= 0xffffffff or t % N or p * N > 65535 for p, t in zip(Ps, Ts)):
+            return None, None
     if not want_xt and not (want_gap and tiles is not None):
         return (None, None) if want_gap else None
     both, xts = None, [None, None, None]
@@ -813,10 +910,17 @@ def aspp_input_transforms(x, rates, weights, pair_tile=0, max_bytes=None, want_g
             gap = torch.empty((N, C), device=dev, dtype=torch.float32)
         (sc0, sh0), (sc1, sh1) = x.aff0, x.aff1
         assert all(t.is_contiguous() and t.shape[-1] == a.C for a, ts in ((x.a0, x.aff0), (x.a1, x.aff1)) for t in ts)
-        with _Timed("wino_transform", nbytes, ("input_aspp3" if want_xt else "aspp_gap", N, H, W, C, d, tuple(tiles))):
-            rc = _lib.status(name, x.a0.ptr, x.a0.ld, x.a0.C, ptr(sc0), ptr(sh0), x.a0.C if sc0.dim() == 2 else 0,
-                             x.a1.ptr, x.a1.ld, x.a1.C, ptr(sc1), ptr(sh1), x.a1.C if sc1.dim() == 2 else 0,
-                             N, H, W, d, ctiles, ptr(xts[0]), ptr(xts[1]), ptr(xts[2]), ptr(sums), ptr(gap))
+        if dropped is not None:
+            name = "mss_wino_input_transform_aspp3_dropped_f32"
+            with _Timed("wino_transform", nbytes, ("input_aspp3", N, H, W, C, d, tuple(tiles), "dropped")):
+                rc = _lib.status(name, x.a0.ptr, x.a0.ld, x.a0.C, ptr(sc0), ptr(sh0), x.a0.C if sc0.dim() == 2 else 0,
+                                 dropped.xc.ptr, dropped.xc.ld, x.a1.C, ptr(dropped.place), ptr(dropped.k_steps),
+                                 N, H, W, d, ctiles, ptr(xts[0]), ptr(xts[1]), ptr(xts[2]), ptr(sums), ptr(gap))
+        else:
+            with _Timed("wino_transform", nbytes, ("input_aspp3" if want_xt else "aspp_gap", N, H, W, C, d, tuple(tiles))):
+                rc = _lib.status(name, x.a0.ptr, x.a0.ld, x.a0.C, ptr(sc0), ptr(sh0), x.a0.C if sc0.dim() == 2 else 0,
+                                 x.a1.ptr, x.a1.ld, x.a1.C, ptr(sc1), ptr(sh1), x.a1.C if sc1.dim() == 2 else 0,
+                                 N, H, W, d, ctiles, ptr(xts[0]), ptr(xts[1]), ptr(xts[2]), ptr(sums), ptr(gap))
     else:
         name = "mss_wino_input_transform_aspp3_f32"
         with _Timed("wino_transform", nbytes, ("input_aspp3", N, H, W, C, d, tuple(tiles))):
@@ -865,6 +969,58 @@ def conv2d_wgrad_winograd(x, dy, K, C, dil=1, in_affine=None, in_relu=False, xt=
             call("mss_conv2d_wgrad_f32", ctypes.byref(a), ptr(dyt), K, ptr(du), Cp, ptr(ws), ws_bytes)
         grad = torch.empty((K, C, 3, 3), device=dev, dtype=torch.float32)
         call("mss_wino_weight_grad_transform_f32", ptr(du), ptr(grad), K, C, Kpad, Cp, ts)
+    return grad
+
+
+def aspp_dropped_weights(rows, K, C, Kpad, ld, tile, dropped):
+    """The per-image Winograd-domain weights U'_n of one dilated branch of the dropped-channel ASPP products, [P][N][Kpad][C] as a
+    WinoWeight over N * K output channels: `rows` is the branch's composed weight as the compose GEMM left it (tap-major
+    [9][Kpad][ld]); its columns are gathered per image into the compacted order (mss_conv2d_unpack_wgrad_f32 with `place`) and the
+    N [K][C][3][3] tensors go through the dense filter transform as one. No dense U' is made."""
+    assert Kpad == K and K % 128 == 0
+    N = dropped.N
+    wg = torch.empty((N, K, C, 3, 3), device=rows.device, dtype=torch.float32)
+    call("mss_conv2d_unpack_wgrad_f32", ptr(rows), ptr(wg), K, C, 3, 3, Kpad, ld, 0, ptr(dropped.place), ptr(dropped.k_steps), N, dropped.C0)
+    P = (tile + 2) ** 2
+    u = torch.empty((P, N * K, C), device=rows.device, dtype=torch.float32)
+    call("mss_wino_pack_weights_f32", ptr(wg), ptr(u), N * K, C, N * K, C, tile)
+    return WinoWeight(u, K, C, Kpad, C, tile)
+
+
+def conv3x3_dropped(x, ww, dil, out, keep_xt, want_stats, xt, dropped):
+    """One dilated ASPP branch on the dropped-channel X' (aspp_input_transforms(..., dropped=)) with aspp_dropped_weights."""
+    N, H, W, C, K = x.N, x.H, x.W, ww.C, ww.K
+    with _Timed("conv_winograd", 2.0 * N * H * W * K * C * 9, (N, H, W, C, K, 3, 1, dil)):
+        return _wino_gemm_and_output(xt, ww, N, H, W, dil, None, out, keep_xt, want_stats, dropped=dropped)
+
+
+def conv3x3_wgrad_dropped(x, dy, K, C, dil, xt, dropped):
+    """Weight gradient of a dilated ASPP branch from the dropped-channel X': dU'_n = dY'_n^T X'_n per (position, image) over that
+    image's rows and columns only (gemm_tn_direct_kernel's per-image form), G^T dU' G of all of them in one launch. The answer is
+    [N][K][C][3][3] in each image's COMPACTED column order; deepv3's projection pack gathers the columns back to their channels and
+    adds the images in ascending order (mss_conv2d_pack_weights_f32 with `col`)."""
+    N, H, W = x.N, x.H, x.W
+    dev = xt.device
+    ts = WINO_TILE_OF_P[xt.shape[0]]
+    P, T = xt.shape[0], xt.shape[1]
+    Ti = T // N
+    assert T % N == 0 and dropped.N == N and K % 128 == 0 and C % 128 == 0 and tuple(xt.shape) == (P, T, C)
+    with _Timed("wgrad_winograd", 2.0 * N * H * W * K * C * 9, (N, H, W, C, K, 3, 1, dil)):
+        dyt = torch.empty((P, T, K), device=dev, dtype=torch.float32)
+        with _Timed("wino_transform", 4.0 * (N * H * W * K + P * T * K), ("grad_output", N, H, W, K, dil, ts)):
+            call("mss_wino_grad_output_transform_f32", dy.ptr, dy.ld, N, H, W, K, dil, ts, ptr(dyt))
+        du = torch.empty((P, N * K, C), device=dev, dtype=torch.float32)     # tiles behind an image's extent stay unwritten, and unread
+        a = MssConvArgs()
+        a.x = ptr(xt)
+        a.N, a.H, a.W, a.C, a.ldx = 1, 1, Ti, C, C
+        a.OH, a.OW, a.K, a.Kpad = 1, Ti, K, K
+        a.R, a.S, a.stride, a.dil, a.pad = 1, 1, 1, 1, 0
+        a.batch, a.x_bs, a.y_bs = P * N, Ti * C, Ti * K
+        a.k_steps, a.k_base, a.k_imgs = ptr(dropped.k_steps), dropped.C0 // 16, N
+        with _Timed("conv_wgrad", 2.0 * P * Ti * K * dropped.columns(), ("aspp_dropped", P, N, Ti, C, K)):
+            call("mss_conv2d_wgrad_f32", ctypes.byref(a), ptr(dyt), K, ptr(du), C, None, 0)
+        grad = torch.empty((N, K, C, 3, 3), device=dev, dtype=torch.float32)
+        call("mss_wino_weight_grad_transform_f32", ptr(du), ptr(grad), N * K, C, N * K, C, ts)
     return grad
 
 

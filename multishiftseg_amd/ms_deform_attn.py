@@ -61,8 +61,8 @@ class _PrepareFn(Function):
         N, Lq, M, L, P = attn.shape
         goff = torch.empty((N, Lq, M, L, P, 2), device=attn.device, dtype=torch.float32)
         glog = torch.empty((N, Lq, M, L * P), device=attn.device, dtype=torch.float32)
-        call("mss_msda_prepare_backward_f32", ptr(attn), ptr(gattn.contiguous()), ptr(gloc.contiguous()), ptr(spatial_shapes),
-             N, Lq, M, L, P, ptr(goff), ptr(glog))
+        call("mss_msda_prepare_backward_ld_f32", ptr(attn), ptr(gattn.contiguous()), ptr(gloc.contiguous()), ptr(spatial_shapes),
+             N, Lq, M, L, P, ptr(goff), M * 2 * L * P, ptr(glog), M * L * P)
         return goff, glog, None, None
 
 
@@ -95,8 +95,8 @@ class _FusedSampleFn(Function):
         gvalue, gloc, gattn = MSDA.ms_deform_attn_backward(value, shapes, starts, loc, attn, grad_output.contiguous(), 128)
         goff = torch.empty_like(offsets)
         glog = torch.empty((N, Lq, M, L * P), device=offsets.device, dtype=torch.float32)
-        call("mss_msda_prepare_backward_f32", ptr(attn), ptr(gattn.contiguous()), ptr(gloc.contiguous()), ptr(shapes),
-             N, Lq, M, L, P, ptr(goff), ptr(glog))
+        call("mss_msda_prepare_backward_ld_f32", ptr(attn), ptr(gattn.contiguous()), ptr(gloc.contiguous()), ptr(shapes),
+             N, Lq, M, L, P, ptr(goff), M * 2 * L * P, ptr(glog), M * L * P)
         return gvalue, None, None, goff, glog, None
 
 
