@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 20     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 21     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -51,7 +51,9 @@ extern "C" {
                                   20: mss_wino_input_transform_aspp3_dropped_f32 added and MssConvArgs.k_base / k_imgs inserted in front of k_steps (the
                                   composed ASPP products without the Dropout2d-zeroed channels); mss_chan_compact_index also writes `col`,
                                   mss_conv2d_pack_weights_f32 / mss_conv2d_unpack_wgrad_f32 take the per-image column gather (signatures changed);
-                                  mss_msda_prepare_backward_f32 removed: it was mss_msda_prepare_backward_ld_f32 with dense strides, which its callers now pass */
+                                  mss_msda_prepare_backward_f32 removed: it was mss_msda_prepare_backward_ld_f32 with dense strides, which its callers now pass;
+                                  21: no entry point or struct changes; mss_conv2d_wgrad_f32's per-image form (MssConvArgs.k_steps) takes an OPTIONAL scratch of
+                                  MSS_WGRAD_PERIMG_TAIL_BYTES (the packed job plan's row-split last round) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -251,7 +253,12 @@ int mss_conv2d_pack_weights_f32(const float* w, float* packed, int K, int C, int
  * Deterministic (no atomics; pixel-range partials are summed in a fixed order: the reference pins
  * cudnn.deterministic, lib/utils/utils.py:10-13). ws: scratch of mss_conv2d_wgrad_workspace_bytes(args, Cp) bytes
  * (NULL allowed when that is 0). Replaces the autograd wgrad of nn.Conv2d for aspp/bot_aspp/bot_fine/ood_head
- * (exps/DeepLab.yaml:10-11, train_deeplab.py:113-132) */
+ * (exps/DeepLab.yaml:10-11, train_deeplab.py:113-132).
+ * Per-image form (args->k_steps): mss_conv2d_wgrad_workspace_bytes is 0 and ws = NULL works -- the live tiles are packed densely and
+ * every job is a whole tile. With ws_bytes >= MSS_WGRAD_PERIMG_TAIL_BYTES the last, partial round of one-wave jobs is cut by rows
+ * as well: partial tiles go to ws and a second launch adds them in ascending order (still no atomics, one fixed order). Either
+ * way, tiles behind an image's extent stay unwritten and the columns behind it inside a tile are exact zeros. */
+#define MSS_WGRAD_PERIMG_TAIL_BYTES (1024ll * 128 * 128 * 4)     /* 1024 wave slots x one 128 x 128 fp32 tile: tail tiles x splits <= slots */
 long long mss_conv2d_wgrad_workspace_bytes(const MssConvArgs* args, int Cp);
 int mss_conv2d_wgrad_f32(MssConvArgs* args, const float* dy, int lddy, float* dwp, int Cp, float* ws,
                          long long ws_bytes, void* stream);

@@ -19,6 +19,8 @@
 // Taps that are dead for the whole 128-pixel tile (all rows fall in the zero padding, common
 // for dilation 12/24/36 on /8 maps) are skipped with a block-uniform decision.
 #include "mss_epilogue.h"
+#include "tn_perimg_plan.h"
+static_assert(MSS_WGRAD_PERIMG_TAIL_BYTES == (long long)TN_PERIMG_MAX_SLOTS * 128 * 128 * 4, "include/mss_hip.h and tn_perimg_plan.h disagree");
 #include <stdlib.h>
 
 int mss_gemm_nt_dispatch(MssConvArgs p, void* stream);   // gemm.hip: persistent GEMM for the 1x1 / stride-1 shapes
@@ -1090,41 +1092,57 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_direct_kernel(const float* __r
                                                                 const float* __restrict__ scale = nullptr,
                                                                 const float* __restrict__ shift = nullptr, int relu = 0, int lda = 0,
                                                                 const int* __restrict__ k_steps = nullptr, int k_base = 0,
-                                                                int k_imgs = 1) {
+                                                                int k_imgs = 1, int pi_slots = 0) {
   if (lda <= 0) lda = K;               // row stride of A (dy): larger when dy is a channel slice of a wider buffer
   constexpr int KB = 4;                                        // 32-column blocks of dy per wave
   constexpr int TND = 8;                                       // row pairs per register block (two blocks: one consumed, one in flight)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // PERIMG: the jobs behind an image's extent are the LAST c tiles of every (entry, k tile) -- with workgroups dealt round-robin to
-  // the 8 XCDs and 8 workgroups per (entry, k tile) at C = 4096 they would all land on the same two XCDs. An XCD owns a contiguous
-  // run of workgroups instead, as in gemm_nt_kernel: every XCD gets its share of live jobs, and the c tiles that read the same dY'
-  // rows share an L2. (Measured 8.30 -> 8.16 ms for the step's three launches, on two different boxes: not a proven gain. What keeps
-  // this form from being faster than the dense one is the granularity of its one-wave jobs)
-  const long long job = (long long)(PERIMG ? mss_xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x) * 4 + wave;
-  if (job >= total) return;                                   // no barrier anywhere in this kernel
-  // Two job layouts. full < 0: every (position, tile) is cut into `splits` row ranges (slab per split in `out`, reduced afterwards).
-  // full >= 0 (TAIL plan, r04: more tiles than wave slots and not a multiple of them -- 36 x 2 x 32 = 2304 tiles on 1024 SIMDs are
-  // 2.25 rounds): the first `full` jobs are whole tiles written straight to the result; the remaining tiles are cut into `splits`
-  // row ranges each, so that the last round is 1/splits as long; their partial tiles go to tail_ws [split][tail tile][128][128].
-  long long t = job;
+  // PERIMG, unpacked plan (MSS_WGRAD_PERIMG_PACK=0, more than TN_PERIMG_MAX_IMGS images): the jobs behind an image's extent are the
+  // LAST c tiles of every (entry, k tile) -- with workgroups dealt round-robin to the 8 XCDs and 8 workgroups per (entry, k tile) at
+  // C = 4096 they would all land on the same two XCDs. An XCD owns a contiguous run of workgroups instead, as in gemm_nt_kernel:
+  // every XCD gets its share of live jobs, and the c tiles that read the same dY' rows share an L2.
+  long long t;
   int sp = 0, nsp = 1;
-  long long tail_tile = -1;
-  if (full >= 0) {
-    if (job >= full) {
-      const long long ntail = (total - full) / splits;
-      sp = (int)((job - full) / ntail);
-      tail_tile = (job - full) - (long long)sp * ntail;
-      t = full + tail_tile;
+  long long tail_tile = -1, ntail = 0;
+  int ct, kt, pb;
+  if (PERIMG && pi_slots > 0) {
+    // PACKED per-image plan (tn_perimg_plan.h): live tiles numbered densely, the last partial round cut by rows when there is scratch
+    // for its partial tiles (tail_ws). The plan is wave-uniform: k_steps comes in by scalar loads. Whole-tile jobs keep the
+    // contiguous-run XCD ownership, over the LIVE workgroups only (the worst-case grid's surplus returns here); the tail round's
+    // workgroups stay round-robin so that every XCD gets its share of the short jobs (full / 4 is a multiple of 8: slots % 32 == 0).
+    const TnPerimgPlan pl = tn_perimg_plan(P / k_imgs, k_imgs, ktiles, ctiles, k_base, k_steps, pi_slots, M, tail_ws != nullptr);
+    const int nwg = (int)((pl.total + 3) / 4), nrun = pl.tail ? (int)(pl.full / 4) : nwg;
+    const int bid = (int)blockIdx.x;
+    if (bid >= nwg) return;
+    const long long job = (long long)(bid < nrun ? mss_xcd_remap(bid, nrun) : bid) * 4 + __builtin_amdgcn_readfirstlane(wave);
+    TnPerimgJob jb;
+    if (!tn_perimg_decode(pl, k_steps, job, jb)) return;
+    ct = jb.ct; kt = jb.kt; pb = jb.pos * k_imgs + jb.img;
+    if (jb.tail_tile >= 0) { sp = jb.sp; nsp = pl.splits; tail_tile = jb.tail_tile; ntail = pl.tail; tps = pl.tps; }
+  } else {
+    const long long job = (long long)(PERIMG ? mss_xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x) * 4 + wave;
+    if (job >= total) return;                                   // no barrier anywhere in this kernel
+    // Two job layouts. full < 0: every (position, tile) is cut into `splits` row ranges (slab per split in `out`, reduced afterwards).
+    // full >= 0 (TAIL plan, r04: more tiles than wave slots and not a multiple of them -- 36 x 2 x 32 = 2304 tiles on 1024 SIMDs are
+    // 2.25 rounds): the first `full` jobs are whole tiles written straight to the result; the remaining tiles are cut into `splits`
+    // row ranges each, so that the last round is 1/splits as long; their partial tiles go to tail_ws [split][tail tile][128][128].
+    t = job;
+    if (full >= 0) {
+      if (job >= full) {
+        ntail = (total - full) / splits;
+        sp = (int)((job - full) / ntail);
+        tail_tile = (job - full) - (long long)sp * ntail;
+        t = full + tail_tile;
+        nsp = splits;
+      }
+    } else {
       nsp = splits;
     }
-  } else {
-    nsp = splits;
+    ct = (int)(t % ctiles); t /= ctiles;
+    kt = (int)(t % ktiles); t /= ktiles;
+    if (full >= 0) pb = (int)t;
+    else { sp = (int)(t % splits); pb = (int)(t / splits); }
   }
-  const int ct = (int)(t % ctiles); t /= ctiles;
-  const int kt = (int)(t % ktiles); t /= ktiles;
-  int pb;
-  if (full >= 0) pb = (int)t;
-  else { sp = (int)(t % splits); pb = (int)(t / splits); }
   const int half = lane >> 5, j = lane & 31;
   const int r0 = nsp > 1 ? sp * tps : 0, r1 = nsp > 1 ? (r0 + tps < M ? r0 + tps : M) : M;
   const float* a = A + (size_t)pb * a_bs + (size_t)(kt * (32 * KB) + KB * j);
@@ -1198,7 +1216,6 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_direct_kernel(const float* __r
   float* o;
   size_t ostride;
   if (tail_tile >= 0) {          // partial tile of the tail plan: compact [128][128]
-    const long long ntail = (total - full) / splits;
     o = tail_ws + ((size_t)sp * ntail + tail_tile) * (128 * 128) + (size_t)(4 * j);
     ostride = 128;
   } else {
@@ -1230,6 +1247,26 @@ __global__ __launch_bounds__(256) void tn_tail_reduce_kernel(const float* __rest
   f32x4 a = *reinterpret_cast<const f32x4*>(src);
   for (int sp = 1; sp < splits; ++sp) a += *reinterpret_cast<const f32x4*>(src + (size_t)sp * ntail * (128 * 128));
   *reinterpret_cast<f32x4*>(dwp + (size_t)pb * Kpad * Cp + (size_t)(kt * 128 + row) * Cp + ct * 128 + col) = a;
+}
+
+// the same for the packed per-image plan: worst-case grid of (slots / 2) x 16 workgroups, the plan from tn_perimg_plan.h as in the
+// kernel above; a workgroup at or behind the plan's tail tiles returns
+__global__ __launch_bounds__(256) void tn_tail_reduce_perimg_kernel(const float* __restrict__ tail_ws, float* __restrict__ dwp, int P,
+                                                                    int k_imgs, int ktiles, int ctiles, int k_base,
+                                                                    const int* __restrict__ k_steps, int slots, int rows, int Kpad,
+                                                                    int Cp) {
+  const int ti = blockIdx.x / 16, part = blockIdx.x % 16;
+  const TnPerimgPlan pl = tn_perimg_plan(P, k_imgs, ktiles, ctiles, k_base, k_steps, slots, rows, 1);
+  if (ti >= pl.tail) return;
+  TnPerimgJob jb;
+  if (!tn_perimg_decode(pl, k_steps, pl.full + ti, jb)) return;
+  const int pb = jb.pos * k_imgs + jb.img;
+  const int e = part * 1024 + threadIdx.x * 4;
+  const int row = e >> 7, col = e & 127;
+  const float* src = tail_ws + (size_t)ti * (128 * 128) + e;
+  f32x4 a = *reinterpret_cast<const f32x4*>(src);
+  for (int sp = 1; sp < pl.splits; ++sp) a += *reinterpret_cast<const f32x4*>(src + (size_t)sp * pl.tail * (128 * 128));
+  *reinterpret_cast<f32x4*>(dwp + (size_t)pb * Kpad * Cp + (size_t)(jb.kt * 128 + row) * Cp + jb.ct * 128 + col) = a;
 }
 
 // ---- narrow weight gradients (K <= 64 output channels: the 19-channel heads, bot_fine's 48) without LDS (r04) -----------------------
@@ -1486,11 +1523,29 @@ inline TnPlan tn_plan_direct(const MssConvArgs& p) {
 int launch_wgrad_tn(const MssConvArgs& p, const float* dy, float* dwp, int Cp, float* ws, long long ws_bytes,
                     hipStream_t stream, int lddy = 0) {
   if (p.k_steps) {
-    // per-image entries over channel-compacted columns: one whole-tile job per (entry, k tile, c tile), sized for the worst case
-    // (every column kept); the jobs behind an image's extent return at once. No splits, no scratch.
-    const long long total = (long long)p.batch * (p.K / 128) * (p.C / 128);
-    hipLaunchKernelGGL((gemm_tn_direct_kernel<false, true>), dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, dy, p.x, dwp, p.batch,
-                       p.M, p.K, p.C, p.y_bs, p.x_bs, p.Kpad, Cp, p.K / 128, p.C / 128, 1, p.M, total, -1ll, (float*)nullptr,
+    // per-image entries over channel-compacted columns. Packed plan (tn_perimg_plan.h, default): the live tiles numbered densely
+    // on the device, the grid sized here for the worst case (every column kept; the host never reads k_steps). With scratch of
+    // slots x 64 KiB (MSS_WGRAD_PERIMG_TAIL_BYTES at the default 1024 slots) the last partial round is cut by rows and a reduce
+    // launch adds its partial tiles in ascending split order; without it every job is a whole tile.
+    const int ktiles = p.K / 128, ctiles = p.C / 128;
+    const long long worst = (long long)p.batch * ktiles * ctiles;
+    if (MSS_ENV_INT("MSS_WGRAD_PERIMG_PACK", 1) != 0 && p.k_imgs <= TN_PERIMG_MAX_IMGS) {
+      int slots = MSS_ENV_INT("MSS_WGRAD_TN_SLOTS", TN_PERIMG_MAX_SLOTS) / 32 * 32;      // per-image plan only (tests reach the tail plan)
+      slots = slots < 32 ? 32 : slots > TN_PERIMG_MAX_SLOTS ? TN_PERIMG_MAX_SLOTS : slots;
+      const int P = p.batch / p.k_imgs;
+      const bool tail = MSS_ENV_INT("MSS_WGRAD_TN_TAIL", 1) != 0 && ws && ws_bytes >= (long long)slots * (128 * 128 * 4) && worst > slots;
+      const long long jobs = tn_perimg_worst_jobs(P, p.k_imgs, ktiles, ctiles, slots, tail);
+      hipLaunchKernelGGL((gemm_tn_direct_kernel<false, true>), dim3((unsigned)((jobs + 3) / 4)), dim3(256), 0, stream, dy, p.x, dwp, p.batch,
+                         p.M, p.K, p.C, p.y_bs, p.x_bs, p.Kpad, Cp, ktiles, ctiles, 1, p.M, jobs, -1ll, tail ? ws : (float*)nullptr,
+                         (const float*)nullptr, (const float*)nullptr, 0, lddy, p.k_steps, p.k_base, p.k_imgs, slots);
+      if (tail)
+        hipLaunchKernelGGL(tn_tail_reduce_perimg_kernel, dim3((unsigned)(slots / 2 * 16)), dim3(256), 0, stream, ws, dwp, P, p.k_imgs, ktiles,
+                           ctiles, p.k_base, p.k_steps, slots, p.M, p.Kpad, Cp);
+      return mss_launch_status();
+    }
+    // unpacked: one whole-tile job per (entry, k tile, c tile); the jobs behind an image's extent return at once. No splits, no scratch.
+    hipLaunchKernelGGL((gemm_tn_direct_kernel<false, true>), dim3((unsigned)((worst + 3) / 4)), dim3(256), 0, stream, dy, p.x, dwp, p.batch,
+                       p.M, p.K, p.C, p.y_bs, p.x_bs, p.Kpad, Cp, ktiles, ctiles, 1, p.M, worst, -1ll, (float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, 0, lddy, p.k_steps, p.k_base, p.k_imgs);
     return mss_launch_status();
   }

@@ -1017,8 +1017,10 @@ def conv3x3_wgrad_dropped(x, dy, K, C, dil, xt, dropped):
         a.R, a.S, a.stride, a.dil, a.pad = 1, 1, 1, 1, 0
         a.batch, a.x_bs, a.y_bs = P * N, Ti * C, Ti * K
         a.k_steps, a.k_base, a.k_imgs = ptr(dropped.k_steps), dropped.C0 // 16, N
+        # optional scratch: with it the packed job plan cuts its last, partial round by rows
+        ws = torch.empty(_lib.MSS_WGRAD_PERIMG_TAIL_BYTES // 4, device=dev, dtype=torch.float32)
         with _Timed("conv_wgrad", 2.0 * P * Ti * K * dropped.columns(), ("aspp_dropped", P, N, Ti, C, K)):
-            call("mss_conv2d_wgrad_f32", ctypes.byref(a), ptr(dyt), K, ptr(du), C, None, 0)
+            call("mss_conv2d_wgrad_f32", ctypes.byref(a), ptr(dyt), K, ptr(du), C, ptr(ws), _lib.MSS_WGRAD_PERIMG_TAIL_BYTES)
         grad = torch.empty((N, K, C, 3, 3), device=dev, dtype=torch.float32)
         call("mss_wino_weight_grad_transform_f32", ptr(du), ptr(grad), N * K, C, N * K, C, ts)
     return grad
