@@ -21,6 +21,7 @@
 #include "mss_epilogue.h"
 #include "mss_gemm_tiles.h"
 #include "mss_bf16x3.h"
+#include "wgrad_route.h"
 #include <stdlib.h>
 #include <mutex>
 #include <unordered_map>
@@ -1121,7 +1122,7 @@ int mss_gemm_nt_bf16x3_launch(MssConvArgs p, void* stream) {
 
 
 // ---- host side of the TN weight-gradient route ------------------------------------------------------------------------------------
-void mss_wgrad_reduce_launch(const float* ws, float* dwp, long long slab4, int splits, hipStream_t stream);   // conv_igemm.hip
+void mss_wgrad_reduce_launch(const float* ws, float* dwp, long long slab4, int splits, hipStream_t stream);   // conv_wgrad.hip
 
 namespace {
 struct TnSplitPlan { int ktiles, ctiles, splits, tps; long long total; };
@@ -1136,14 +1137,7 @@ TnSplitPlan tn_split_plan(const MssConvArgs& p) {
   const int cap = p.batch > 1 ? 64 : 256;
   if (max_splits > cap) max_splits = cap;
   if (max_splits < 1) max_splits = 1;
-  int splits = 1;
-  double best = 0.0;
-  for (int sp = 1; sp <= max_splits; ++sp) {
-    const long long total = base * sp;
-    const double eff = (double)total / (double)(((total + slots - 1) / slots) * slots);
-    if (eff > best + 1e-9) { best = eff; splits = sp; }
-    if (eff >= 0.95 && total >= slots) break;
-  }
+  const int splits = split_search(base, slots, max_splits);      // wgrad_route.h
   pl.tps = mss_cdiv(mss_cdiv(p.M, splits), 16) * 16;
   if (pl.tps > p.M) pl.tps = (p.M / 16) * 16;
   pl.splits = mss_cdiv(p.M, pl.tps);

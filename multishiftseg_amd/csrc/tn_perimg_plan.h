@@ -4,7 +4,7 @@
 // L[n] = ceil(that / 128) live c tiles (clamped to ctiles). The live 128 x 128 tiles of all entries are numbered densely --
 // position, then image, then k tile, c tile fastest -- so that no wave slot is spent on a tile behind an extent, and when they do not
 // fill whole rounds of `slots` one-wave jobs the last, partial round (`tail` tiles) is cut into `splits` row ranges of `tps` rows each
-// by tn_plan_direct's rule: the round is then 1 / splits as long. Job numbers: [0, full) whole tiles, then split-major
+// by wg_plan_tn_direct's rule (wgrad_route.h): the round is then 1 / splits as long. Job numbers: [0, full) whole tiles, then split-major
 // full + sp * tail + tail tile. k_steps lives on the device: every wave evaluates the plan from scalar loads, the host only sizes
 // the grid for the worst case (tn_perimg_worst_jobs) and the waves at or behind `total` return.
 #pragma once

@@ -1177,6 +1177,31 @@ def test_linear_wgrad_many_rows_vs_float64(K, T, C, Ko, gemm_route):
     assert err <= 2e-6 * T ** 0.5 * 16, err
 
 
+@pytest.mark.parametrize("c0", [0, 64])
+@pytest.mark.parametrize("Ko", [160, 192])
+def test_linear_wgrad_two_part_route_on_a_channel_slice_of_dy(K, Ko, c0):
+    """Ko = 128 + r output channels (r = 32, 64) over 16 385 rows -- one over the narrow kernel's floor, and odd -- run as two
+    launches: the first 128 channels as one product and the last r on the narrow streaming kernel (csrc/wgrad_route.h: WG_TWO_PART),
+    here with dy the columns [c0, c0 + Ko) of a [T][256] buffer and scratch of exactly the queried size. Every row of dW against the
+    float64 product, twice with identical bits, and bit for bit the result of the same call on a contiguous copy of the slice:
+    neither part's plan depends on the row stride of dy (the 128-channel part runs conv_wgrad_kernel's 128-row tile in both
+    calls -- with a row stride other than its own 128 channels only gemm_tn_direct_kernel could take it, and 65 one-wave jobs are
+    too few for that --, the rest gemm_tn_narrow_kernel), as tests/wgrad_route_check.cpp prints for these shapes."""
+    T, C = 16385, 128
+    torch.manual_seed(T + Ko + c0)
+    x = torch.randn(T, C, device="cuda")
+    buf = torch.randn(T, 256, device="cuda")
+    dy = buf[:, c0:c0 + Ko]
+    sliced = K.Act(buf.view(1, 1, T, 256), Ko, c0)
+    outs = [K.conv2d_wgrad(K.Act(x.view(1, 1, T, C)), sliced, Ko, C, 1, 1).view(Ko, C) for _ in range(2)]
+    assert torch.equal(outs[0], outs[1])
+    want = dy.double().t() @ x.double()
+    err = (outs[0].double() - want).abs().max().item()
+    assert err <= 2e-6 * T ** 0.5 * 16, err
+    dense = K.conv2d_wgrad(K.Act(x.view(1, 1, T, C)), K.Act(dy.contiguous().view(1, 1, T, Ko)), Ko, C, 1, 1).view(Ko, C)
+    assert torch.equal(outs[0], dense)
+
+
 @pytest.mark.parametrize("P,T,C,Ko,affine", [(64, 1892, 512, 512, False), (34, 2112, 320, 1024, False), (1, 70000, 512, 256, True)])
 def test_gemm_hybrid_last_round_is_bitwise_the_wide_result(K, monkeypatch, P, T, C, Ko, affine):
     """Wide-tile GEMMs whose last round would be mostly idle finish on narrow tiles in a second launch (gemm.hip): every
