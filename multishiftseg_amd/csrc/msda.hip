@@ -127,9 +127,12 @@ __global__ __launch_bounds__(256) void msda_fwd_rec_kernel(
       o.z = (okh1 && okw0) ? o00 + W * rs4 : oob;
       o.w = (okh1 && okw1) ? o00 + W * rs4 + rs4 : oob;
       *reinterpret_cast<uint4*>(soff + g * pstride + 4 * i) = o;
-      const f32x4 w = {hh * hw, hh * lw, lh * hw, lh * lw};
-      *reinterpret_cast<f32x4*>(swgt + g * pstride + 4 * i) = w;
-      satt[g * LPpad + i] = aw;
+      // a sample that fails the inside test is SKIPPED (.cuh:293), it is not a sample of weight zero times whatever its
+      // corners hold: a NaN / infinite / overflowing coordinate gives NaN weights here, and 0 (the out-of-range corners) x NaN
+      // would poison the row. Zero record weights, once per sample and lane group; the gather loop stays as it is.
+      const f32x4 wz = {0.f, 0.f, 0.f, 0.f}, wb = {hh * hw, hh * lw, lh * hw, lh * lw};
+      *reinterpret_cast<f32x4*>(swgt + g * pstride + 4 * i) = inside ? wb : wz;
+      satt[g * LPpad + i] = inside ? aw : 0.f;
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -365,9 +368,10 @@ __global__ __launch_bounds__(256) void msda_bwd_gather_fast_kernel(
         v4 = (okh1 && okw1) ? v4 : z;
       }
       const float p1 = dot8(v1), p2 = dot8(v2), p3 = dot8(v3), p4 = dot8(v4);
-      const float s_attn = hh * hw * p1 + hh * lw * p2 + lh * hw * p3 + lh * lw * p4;
-      const float s_w = aw * (float)W * (-hh * p1 + hh * p2 - lh * p3 + lh * p4);
-      const float s_h = aw * (float)H * (-hw * p1 - lw * p2 + hw * p3 + lw * p4);
+      // !inside: the sample is skipped (zero gradients, as msda_bwd_kernel's `if`), whatever NaN its coordinate made of lh / lw
+      const float s_attn = inside ? hh * hw * p1 + hh * lw * p2 + lh * hw * p3 + lh * lw * p4 : 0.f;
+      const float s_w = inside ? aw * (float)W * (-hh * p1 + hh * p2 - lh * p3 + lh * p4) : 0.f;
+      const float s_h = inside ? aw * (float)H * (-hw * p1 - lw * p2 + hw * p3 + lw * p4) : 0.f;
       if (live && j == 0) {
         // PROJ: d(offset) = g_loc / (W_l, H_l) right here, where the level is known (the same division the prepare-backward kernel does)
         myloc[sidx * 2] = proj ? s_w / (float)W : s_w;

@@ -69,8 +69,10 @@ class _PrepareFn(Function):
 class _FusedSampleFn(Function):
     """the op fed with the raw offsets / logits of the two Linears; softmax + location arithmetic run inside
     the sampling kernel (mss_msda_forward_fused_f32), so sampling_locations / attention_weights never touch HBM in the
-    forward. The backward rebuilds them with the one-pass prepare kernel (bit-identical values), runs the op's
-    backward and maps the gradients back to offsets / logits."""
+    forward. The backward rebuilds them with the one-pass prepare kernel, runs the op's backward and maps the gradients back
+    to offsets / logits. The rebuilt LOCATIONS are bit-identical to the forward's (both kernels form ref + off / size), so the
+    backward lands in the forward's bilinear cell; the rebuilt attention weights are not: the two kernels add the L*P
+    exponentials of the softmax in different orders (agreement to a few ulp)."""
 
     @staticmethod
     def forward(ctx, value, spatial_shapes, level_start_index, offsets, logits, reference_points):
