@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 21     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 22     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -53,7 +53,9 @@ extern "C" {
                                   mss_conv2d_pack_weights_f32 / mss_conv2d_unpack_wgrad_f32 take the per-image column gather (signatures changed);
                                   mss_msda_prepare_backward_f32 removed: it was mss_msda_prepare_backward_ld_f32 with dense strides, which its callers now pass;
                                   21: no entry point or struct changes; mss_conv2d_wgrad_f32's per-image form (MssConvArgs.k_steps) takes an OPTIONAL scratch of
-                                  MSS_WGRAD_PERIMG_TAIL_BYTES (the packed job plan's row-split last round) */
+                                  MSS_WGRAD_PERIMG_TAIL_BYTES (the packed job plan's row-split last round);
+                                  22: mss_m2f_targets_from_labels added (the Mask2Former target pack built from the label maps on the device); mss_peak_clock
+                                  removed to make room (only a diagnostic tool called it) */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -836,6 +838,26 @@ int mss_m2f_mix_backward_f32(const float* dmix, const float* prob, const float* 
                              long long query_stride, long long pixel_stride, int B, int Q, int C, int h, int w, double* partial,
                              float* dmasks, float* dcls, void* stream);
 
+/* ---- Mask2Former targets from label maps (csrc/m2f_targets.hip) ----
+ * replaces train_m2f.py:342-385 (prepare_input: target[b].cpu().numpy(), np.unique, one `sem_seg == class_id` map per class, the OOD
+ * map) and lib/network/mask2former/maskformer_model.py:316-339 (prepare_targets: the zero padding to Hp x Wp) and leaves the pack
+ * MssM2fTargets describes. sem [B,H,W] contiguous, sem_bytes per element: 8 (int64), 4 (int32) or 1 (uint8). A value v is a class
+ * iff 0 <= v < label_threshold (1..128); a pixel is OOD iff v > label_threshold and v != ignore_label; v == label_threshold is
+ * neither, and (unlike the reference, which would hand its criterion a negative label) neither is a negative v.
+ *   phase 0 "count", two launches behind a memset of present: present uint64 [B][2] = the set of classes of image b (bit v of the
+ *     128-bit set; integer atomicOr, exact); tstart int32 [B+1]; labels int32, room for B * label_threshold, the first tstart[B]
+ *     valid: the classes of image b ascending (np.unique's order) from tstart[b]; rank int32 [B][label_threshold]: the row of
+ *     class v inside image b, or -1. tmask, ood and total_t are not used.
+ *   phase 1 "fill", one launch: EVERY byte of tmask uint8 [total_t,Hp,Wp] and of ood uint8 [B,Hp,Wp] is written: row
+ *     tstart[b] + rank[b][v] of tmask is 1 where sem[b] == v, ood[b] is 1 where the pixel is OOD, both 0 elsewhere and in the padding
+ *     (y >= H or x >= W). total_t = tstart[B] as the host read it; rows >= total_t are never written. total_t == 0 is valid: tmask
+ *     may then be NULL and ood is still written. present and labels are not used. The stores are as wide (16 bytes at most) as Wp
+ *     and the two base addresses are aligned to, single bytes where Wp is odd.
+ * Integer arithmetic only, no float atomics, no scratch: two runs give the same bytes. */
+int mss_m2f_targets_from_labels(const void* sem, int sem_bytes, int B, int H, int W, int Hp, int Wp, int label_threshold, int ignore_label,
+                                int phase, unsigned long long* present, int* tstart, int* labels, int* rank, long long total_t,
+                                unsigned char* tmask, unsigned char* ood, void* stream);
+
 /* ---- on-device data path of the DeepLab trainer (csrc/data.hip) ----
  * One kernel for what DiverseCityscapes.__getitem__ + its transforms + the trainer's batch concat do per step
  * (lib/dataset/cityscapes.py:153-171, lib/utils/img_utils.py:110-153,246-259,398-435, train_deeplab.py:190-195):
@@ -861,9 +883,6 @@ int mss_peak_mfma_f32(float* out, int blocks, int iters, void* stream);
 /* The same for the bf16 matrix cores under load (the split-bf16 GEMM route's ceiling): register-only loops on pseudo-random operands,
  * blocks x 4 waves x iters x 1 572 864 FLOP; shape 0 = 48 x v_mfma_f32_32x32x16_bf16 per iteration, 1 = 96 x v_mfma_f32_16x16x32_bf16. */
 int mss_peak_mfma_bf16(float* out, int blocks, int iters, int shape, void* stream);
-/* Clock calibration: one wave spins for `ticks` of s_memrealtime; out[0] = s_memrealtime ticks, out[1] = s_memtime ticks of the span
- * (out: 2 x uint64 on the device). Timed from the host it gives the frequency of both counters. */
-int mss_peak_clock(unsigned long long* out, unsigned long long ticks, void* stream);
 int mss_peak_stream_f32(const float* src, float* dst, long long n, int variant, void* stream);
 /* layout experiment behind the Winograd-domain layout: one coalesced float4 read, ns (16|36) float4 writes
  * into ns slabs that are n floats apart (blocked = 0) or adjacent per block of blk_floats floats (blocked = 1). */

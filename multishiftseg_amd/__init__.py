@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "masked_attention":
         from .kernels import masked_attention
         return masked_attention
+    if name in ("prepare_targets", "M2FTargets"):
+        from . import m2f_targets
+        return getattr(m2f_targets, name)
     if name in _M2F_TRAINER:
         from . import m2f_trainer
         return getattr(m2f_trainer, name)
@@ -27,4 +30,4 @@ def __getattr__(name):
 
 
 __all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention",
-           *_M2F_TRAINER]
+           "prepare_targets", "M2FTargets", *_M2F_TRAINER]

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 21         # include/mss_hip.h
+MSS_ABI_VERSION = 22         # include/mss_hip.h
 MSS_WGRAD_PERIMG_TAIL_BYTES = 1024 * 128 * 128 * 4     # include/mss_hip.h: optional scratch of the per-image weight gradient
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
@@ -203,6 +203,7 @@ SIGNATURES = {
     "mss_m2f_mix_upsample_f32": [P, I, I, I, I, I, I, I, I, I, P, P],
     "mss_m2f_mix_upsample_backward_f32": [P, P, P, I, I, I, I, I, I, I, I, P, P],
     "mss_m2f_mix_backward_f32": [P, P, P, P, L, L, L, I, I, I, I, I, P, P, P, P],
+    "mss_m2f_targets_from_labels": [P, I, I, I, I, I, I, I, I, I, P, P, P, P, L, P, P, P],
     "mss_oodm_compact_lanes_f32": [P, P, L, L, L, P, P, P],
     "mss_oodm_compact_lanes_batch_f32": [POINTER(MssOodmBatch), I, L, L, P],
     "mss_oodm_gather_lanes_u32": [P, L, P, P, P, P],
@@ -228,7 +229,6 @@ SIGNATURES = {
     "mss_data_pair_f32": [P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, I, I, P, P, P],
     "mss_peak_mfma_f32": [P, I, I, P],
     "mss_peak_mfma_bf16": [P, I, I, I, P],
-    "mss_peak_clock": [P, ctypes.c_ulonglong, P],
     "mss_peak_stream_f32": [P, P, L, I, P],
     "mss_peak_scatter_f32": [P, P, L, I, I, L, P],
 }

@@ -1727,6 +1727,74 @@ def m2f_match_assign(cost, tcount):
     return match, status
 
 
+# ---- Mask2Former targets from label maps (csrc/m2f_targets.hip) ----------------------------------------------------------------
+_SEM_DTYPES = {torch.int64: 8, torch.int32: 4, torch.uint8: 1}
+
+
+def _targets_sem(name, sem, label_threshold):
+    if not isinstance(sem, torch.Tensor) or not sem.is_cuda:
+        raise RuntimeError(f"{name} runs on an MI355X only (a CUDA label map); there is no CPU path")
+    if sem.dtype not in _SEM_DTYPES:
+        raise RuntimeError(f"{name} takes int64, int32 or uint8 label maps, got {sem.dtype}")
+    if sem.dim() != 3 or sem.numel() == 0:
+        raise ValueError(f"{name}: the label maps are [B,H,W] with no empty dimension, got {tuple(sem.shape)}")
+    if not 1 <= int(label_threshold) <= 128:
+        raise NotImplementedError(f"{name}: label_threshold {label_threshold} outside 1..128")
+    return sem.contiguous(), _SEM_DTYPES[sem.dtype]
+
+
+def m2f_targets_count(sem, label_threshold=100):
+    """Which classes each label map holds (train_m2f.py:355-357: np.unique, `classes < label_threshold`), two launches, nothing read
+    back. sem [B,H,W] int64 / int32 / uint8 on the device; a class is a value in [0, label_threshold), label_threshold <= 128.
+    -> (tstart int32 [B+1], labels_buf int32 [B * label_threshold]: image b's classes ascending from tstart[b], the entries past
+    tstart[B] are 0; rank int32 [B, label_threshold]: the row of class v inside image b or -1; present int64 [B,2]: the 128-bit
+    class set of image b)."""
+    name = "m2f_targets_count"
+    sem, nbytes = _targets_sem(name, sem, label_threshold)
+    B, H, W = sem.shape
+    thr = int(label_threshold)
+    dev = sem.device
+    # integer buffers are never handed out uninitialised (tests/poison.py)
+    tstart = torch.zeros(B + 1, device=dev, dtype=torch.int32)
+    labels = torch.zeros(B * thr, device=dev, dtype=torch.int32)
+    rank = torch.full((B, thr), -1, device=dev, dtype=torch.int32)
+    present = torch.zeros((B, 2), device=dev, dtype=torch.int64)
+    call("mss_m2f_targets_from_labels", ptr(sem), nbytes, B, H, W, H, W, thr, 255, 0, ptr(present), ptr(tstart), ptr(labels), ptr(rank), 0,
+         None, None)
+    return tstart, labels, rank, present
+
+
+def m2f_targets_fill(sem, tstart, rank, total_t, padded_size, label_threshold=100, ignore_label=255, tmask=None, ood=None):
+    """The target masks and the OOD map of train_m2f.py:360-361 (`sem_seg == class_id`, `(sem_seg > label_threshold) & (sem_seg !=
+    ignore_label)`), zero padded to padded_size = (Hp, Wp) (maskformer_model.py:316-339), in one launch that writes every byte of
+    both. tstart / rank: m2f_targets_count's; total_t: tstart[B] as a host int. tmask uint8 [total_t,Hp,Wp] / ood uint8 [B,Hp,Wp]:
+    buffers of the caller's to write into (default: new ones). -> (tmask, ood)."""
+    name = "m2f_targets_fill"
+    sem, nbytes = _targets_sem(name, sem, label_threshold)
+    B, H, W = sem.shape
+    thr, total_t = int(label_threshold), int(total_t)
+    Hp, Wp = (int(v) for v in padded_size)
+    dev = sem.device
+    for t in (tstart, rank) + tuple(o for o in (tmask, ood) if o is not None):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} runs on an MI355X only (CUDA tensors); there is no CPU path")
+    if tstart.dtype != torch.int32 or rank.dtype != torch.int32 or any(o is not None and o.dtype != torch.uint8 for o in (tmask, ood)):
+        raise RuntimeError(f"{name} takes int32 tstart / rank and uint8 tmask / ood on the device")
+    if tstart.numel() != B + 1 or tuple(rank.shape) != (B, thr):
+        raise ValueError(f"{name}: tstart {tuple(tstart.shape)} / rank {tuple(rank.shape)} do not match B {B}, label_threshold {thr}")
+    if Hp < H or Wp < W or not 0 <= total_t <= B * thr:
+        raise ValueError(f"{name}: padded size {(Hp, Wp)} / total_t {total_t} do not fit label maps {tuple(sem.shape)}")
+    if tmask is None:
+        tmask = torch.zeros((total_t, Hp, Wp), device=dev, dtype=torch.uint8)
+    if ood is None:
+        ood = torch.zeros((B, Hp, Wp), device=dev, dtype=torch.uint8)
+    if tuple(tmask.shape) != (total_t, Hp, Wp) or tuple(ood.shape) != (B, Hp, Wp) or not tmask.is_contiguous() or not ood.is_contiguous():
+        raise ValueError(f"{name}: tmask {tuple(tmask.shape)} / ood {tuple(ood.shape)} must be contiguous [{total_t},{Hp},{Wp}] / [{B},{Hp},{Wp}]")
+    call("mss_m2f_targets_from_labels", ptr(sem), nbytes, B, H, W, Hp, Wp, thr, int(ignore_label), 1, None, ptr(tstart.contiguous()), None,
+         ptr(rank.contiguous()), total_t, ptr(tmask) if total_t else None, ptr(ood))
+    return tmask, ood
+
+
 # ---- SetCriterion of Mask2Former: class and sampled-mask losses (csrc/m2f_loss.hip) -----------------------------------------------
 _LOSS_MODES = {"uncertain": 1, "clean": 2}
 

@@ -8,6 +8,7 @@ import torch
 from torch import nn
 
 from . import kernels as K
+from .m2f_targets import M2FTargets
 
 MAX_QUERIES = 128       # include/mss_hip.h: T_b <= Q <= 128
 MAX_STEPS = 16
@@ -50,7 +51,13 @@ class HungarianMatcher(nn.Module):
         self.last_status = None         # [S,B] int32 on the device after a call (0 = solved)
 
     def _pack_targets(self, targets, device):
-        """-> (tmask uint8 [sum T,H,W], tstart int32 [B+1], labels int32 [sum T], counts) on `device`."""
+        """-> (tmask uint8 [sum T,H,W], tstart int32 [B+1], labels int32 [sum T], counts) on `device`. An M2FTargets
+        (m2f_targets.prepare_targets) on that device already holds the pack: it is returned as it is, nothing is copied."""
+        packed = getattr(targets, "packed", None)
+        if isinstance(targets, M2FTargets) and packed is not None:
+            have, want = packed[0].device, torch.device(device)
+            if have.type == want.type and (want.index is None or want.index == have.index):
+                return packed
         counts = [int(t["labels"].shape[0]) for t in targets]
         sizes = {tuple(t["masks"].shape[-2:]) for t in targets}
         if len(sizes) != 1:
