@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 22     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 23     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -55,7 +55,8 @@ extern "C" {
                                   21: no entry point or struct changes; mss_conv2d_wgrad_f32's per-image form (MssConvArgs.k_steps) takes an OPTIONAL scratch of
                                   MSS_WGRAD_PERIMG_TAIL_BYTES (the packed job plan's row-split last round);
                                   22: mss_m2f_targets_from_labels added (the Mask2Former target pack built from the label maps on the device); mss_peak_clock
-                                  removed to make room (only a diagnostic tool called it) */
+                                  removed to make room (only a diagnostic tool called it);
+                                  23 (additive): mss_wino_aspp3_supported, the host query of what the three single-read ASPP transforms refuse */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -335,6 +336,11 @@ int mss_wino_input_transform_aspp3_dropped_f32(const float* x0, int ldx0, int C0
                                                const float* x1c, int ldx1, int C1, const int* place, const int* k_steps,
                                                int N, int H, int W, int d, const int* tiles, float* xt0, float* xt1, float* xt2,
                                                float* sums, float* gap, void* stream);
+/* Host query, no launch: 1 where the three single-read transforms above take the shape, 0 where they answer MSS_ERR_UNSUPPORTED -- a
+ * tile edge that is not 4 or 6, a base residue sub-grid over 80 KiB of LDS, 2^31 workgroups, and for the two-source forms (two_source
+ * != 0, C = C0 + C1) C or d * d beyond 2^24. tiles: a HOST pointer to 3 tile edges. A caller asks it before it allocates X', so that
+ * a refusal at the launch is an error and not a fallback (multishiftseg_amd/aspp_plan.py). */
+int mss_wino_aspp3_supported(int N, int H, int W, int C, int d, const int* tiles, int two_source);
 int mss_wino_output_transform_f32(const float* yt, int N, int H, int W, int K, int dil, int tile, const float* res,
                                   int ldres, float* y, int ldy, float* stats, void* stream);
 /* stats (optional): [mss_wino_output_stats_parts(...)][2][K] partial sums / sums of squares of y, as MssConvArgs.stats */

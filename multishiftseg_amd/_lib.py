@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 22         # include/mss_hip.h
+MSS_ABI_VERSION = 23         # include/mss_hip.h
 MSS_WGRAD_PERIMG_TAIL_BYTES = 1024 * 128 * 128 * 4     # include/mss_hip.h: optional scratch of the per-image weight gradient
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
@@ -177,6 +177,7 @@ SIGNATURES = {
     "mss_wino_input_transform_aspp3_f32": [P, I, I, I, I, I, I, P, P, P, P, P],
     "mss_wino_input_transform_aspp3_src2_f32": [P, I, I, P, P, I, P, I, I, P, P, I, I, I, I, I, P, P, P, P, P, P, P],
     "mss_wino_input_transform_aspp3_dropped_f32": [P, I, I, P, P, I, P, I, I, P, P, I, I, I, I, P, P, P, P, P, P, P],
+    "mss_wino_aspp3_supported": [I, I, I, I, I, P, I],
     "mss_wino_output_transform_f32": [P, I, I, I, I, I, I, P, I, P, I, P, P],
     "mss_wino_output_stats_parts": [I, I, I, I, I, I],
     "mss_bn_stats_partials_f32": [P, L, I, P, P],
@@ -238,7 +239,7 @@ VALUE_RESTYPE = {
     "mss_conv2d_forward_route": c_int, "mss_gemm_split_last_mfma": c_int, "mss_gemm_split_weights_bytes": c_longlong, "mss_conv2d_wgrad_workspace_bytes": c_longlong, "mss_conv2d_wgrad_route": c_int,
     "mss_col_reduce_accum_doubles": c_longlong, "mss_colsum_workspace_floats": c_longlong, "mss_rcl_num_compact_blocks": c_int, "mss_rcl_workspace_bytes": c_longlong, "mss_adamw_chunk_elems": c_int,
     "mss_adamw_tensors_per_launch": c_int, "mss_adamw_blocks_per_launch": c_int, "mss_adamw_scratch_floats": c_longlong, "mss_adamw_plan": c_longlong, "mss_wino_num_tiles": c_longlong,
-    "mss_wino_output_stats_parts": c_int, "mss_m2f_attn_workspace_bytes": c_longlong, "mss_m2f_attn_bwd_workspace_bytes": c_longlong, "mss_m2f_match_workspace_bytes": c_longlong,
+    "mss_wino_output_stats_parts": c_int, "mss_wino_aspp3_supported": c_int, "mss_m2f_attn_workspace_bytes": c_longlong, "mss_m2f_attn_bwd_workspace_bytes": c_longlong, "mss_m2f_match_workspace_bytes": c_longlong,
     "mss_m2f_loss_workspace_bytes": c_longlong, "mss_m2f_mix_backward_chunks": c_int, "mss_oodm_sort_temp_bytes": c_longlong, "mss_oodm_compact_lanes_cap": c_longlong, "mss_oodm_rank_blocks": c_int,
     "mss_add_layernorm_bwd_workspace_floats": c_longlong, "mss_groupnorm_workspace_floats": c_longlong, "mss_groupnorm_stat_offset": c_longlong, "mss_groupnorm_bwd_workspace_floats": c_longlong,
 }

@@ -20,7 +20,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from . import kernels as K
+from . import aspp_plan, kernels as K
 from .kernels import Act
 
 _STRUCTURE = [3, 3, 6, 3, 1, 1]
@@ -271,7 +271,7 @@ class DeepWV3Plus(nn.Module):
     # one compose GEMM (7168 tap-major weight rows x 4096 x 4096) whenever an ASPP weight has changed, one projection of the four
     # weight gradients through M in the backward (DESIGN: "ASPP composed with mod7's output convolutions").
     def _aspp_compose_gate(self, blk, a):
-        """True where the trunk's last block hands ASPP its factors: MSS_ASPP_COMPOSE (default 1), a stride-1 bottleneck with
+        """True where the trunk's last block hands ASPP its factors: aspp_plan.compose_wanted, a stride-1 bottleneck with
         proj_conv, and the shapes / policy kernels.aspp_tiles takes (Winograd tiles 4 or 6 on all three rates, no tile hook).
         Everything else -- the direct and F(2x2) routes, small sub-grids -- keeps the present path."""
         if not (K.aspp_compose_wanted() and blk.bottleneck and hasattr(blk, "proj_conv") and blk.stride == 1):
@@ -365,39 +365,23 @@ class DeepWV3Plus(nn.Module):
         comp = self._aspp_composed(self.mod7[-1]) if isinstance(x, K.FactoredAct) else None
         fx = x if comp is not None else None
         wts = comp["wc"] if comp is not None else [f[0].weight for f in asp.features]
-        xt_bytes = sum(K.wino_xt_bytes(N, h8, w8, 4096, r) for r in _ASPP_RATES)
-        # two dilated branches whose Winograd-domain products have the same shape share ONE GEMM launch when that fills the chip
-        # better (the one-image eval forward: dilations 12 and 24, kernels.conv3x3_pair_tile); never when X' is kept for a backward
-        pair_tile = 0 if keep else K.conv3x3_pair_tile(x, wts[1], wts[2], *_ASPP_RATES[:2])
-        # the three dilated branches read the same 1 GB map: ONE kernel makes all three Winograd-domain inputs from a single read
-        # (kernels.aspp_input_transforms); None: shapes / policy outside it, each branch transforms for itself as before
-        max_bytes = None if (keep and xt_bytes < (40 << 30)) else (40 << 30)
-        drop = None
+        # every route decision of the block, taken once (aspp_plan.AsppPlan); what follows executes it
+        plan = K.aspp_plan_for(x, _ASPP_RATES, wts[1:], keep, [f[0].weight.requires_grad for f in asp.features[1:]])
+        # train mode: the Dropout2d-zeroed channels of v are exact zeros in all three products -- each image multiplies its kept
+        # channels only
+        drop = K.AsppDropped(fx) if plan.dropped else None
+        # the three dilated branches read the same 1 GB map: ONE kernel makes all three Winograd-domain inputs from a single read,
+        # on the composed route from the two factors, which also leaves GAP(w); GAP(x) = M . GAP(w)
+        pre = gap_w = None
+        if plan.dropped_separate:
+            pre, gap_w = K.aspp_dropped_separate_transforms(fx, _ASPP_RATES, plan, drop)
+        elif plan.single_read or plan.gap_from_kernel:
+            pre, gap_w = K.aspp_transforms(x, _ASPP_RATES, plan, drop)
+        if plan.materialise:
+            x = fx.materialise()
         if comp is None:
-            pre_xt = K.aspp_input_transforms(x, _ASPP_RATES, wts[1:], pair_tile, max_bytes=max_bytes)
             pooled = K.gap(x)
         else:
-            # train mode: the Dropout2d-zeroed channels of v are exact zeros in all three products -- each image multiplies its kept
-            # channels only (kernels.AsppDropped; MSS_ASPP_DROPOUT_COMPACT=0, the split route and shapes outside the gate: dense)
-            pre_xt = gap_w = None
-            if not pair_tile and K.aspp_dropped_wanted(fx, wts[1:]):
-                drop = K.AsppDropped(fx)
-                pre_xt, gap_w = K.aspp_input_transforms(fx, _ASPP_RATES, wts[1:], 0, max_bytes=max_bytes, want_gap=True, dropped=drop)
-                if pre_xt is None and os.environ.get("MSS_WINO_ASPP3", "1") == "0":
-                    # the switch's second formulation, as on the dense route: the compacted map materialised, three separate transforms
-                    pre_xt, gap_w = K.aspp_dropped_separate_transforms(fx, _ASPP_RATES, wts[1:], drop, max_bytes=max_bytes)
-                if pre_xt is None:
-                    drop = None
-        if comp is not None and drop is not None:
-            x = fx
-            pooled = K.conv2d(Act(gap_w.view(N, 1, 1, 4096)), comp["M"]).buf.view(N, 4096)
-        elif comp is not None:
-            # the same kernel on the two factors, which also leaves GAP(w); GAP(x) = M . GAP(w). Where X' is not taken from it
-            # (MSS_WINO_ASPP3=0, over budget) or is not all kept for the weight gradients, w is materialised and is the map the
-            # branches transform for themselves
-            pre_xt, gap_w = K.aspp_input_transforms(fx, _ASPP_RATES, wts[1:], pair_tile, max_bytes=max_bytes, want_gap=True)
-            wgrad_x = keep and any(f[0].weight.requires_grad for f in asp.features[1:]) and not xt_bytes < (40 << 30)
-            x = fx.materialise() if (pre_xt is None or wgrad_x) else fx
             if gap_w is None:
                 gap_w = K.gap(x)
             pooled = K.conv2d(Act(gap_w.view(N, 1, 1, 4096)), comp["M"]).buf.view(N, 4096)
@@ -419,30 +403,28 @@ class DeepWV3Plus(nn.Module):
                 del half
             elif i == 0:
                 K.conv2d(x, K.packed(feat[0].weight), out=sl, want_stats=train)
-            elif pair_tile and i in (1, 2):
+            elif plan.pair_tile and i in (1, 2):
                 if i == 1:
                     sl2 = raw.slice(256 * 3, 256)          # ONE object: conv3x3_pair leaves the batch statistics on it
                     K.conv3x3_pair(x, wts[1], wts[2], _ASPP_RATES[0], _ASPP_RATES[1], sl,
-                                   sl2, pair_tile, want_stats=train, xt=pre_xt[0] if pre_xt else None)
-                    if pre_xt:
-                        pre_xt[0] = None
+                                   sl2, plan.pair_tile, want_stats=train, xt=pre.take_pair() if pre else None)
                     pair_slices = {1: sl, 2: sl2}
                 sl = pair_slices[i]              # carries the statistics the producing transform left (train-mode BatchNorm)
-                aspp_xt[i] = None
             else:
                 # keep the Winograd-domain input X' for this layer's weight gradient when the three of them fit
                 # comfortably (2.25-4x the 4096-channel map each: 10.6 GB in all at 2x1024x2048)
-                kx = {} if (keep and feat[0].weight.requires_grad and xt_bytes < (40 << 30)) else None
-                if drop is not None:
+                kx = {} if plan.keep_xt[i - 1] else None
+                xt = pre.take(i - 1) if pre else None       # the layer owns it now (kept for the weight gradient, or freed)
+                if plan.dropped:
                     rows, ld, kp = comp["rows"][i]
-                    ww = K.aspp_dropped_weights(rows, wts[i].shape[0], wts[i].shape[1], kp, ld, K.WINO_TILE_OF_P[pre_xt[i - 1].shape[0]], drop)
-                    K.conv3x3_dropped(x, ww, rate, sl, kx, train, pre_xt[i - 1], drop)
+                    ww = K.aspp_dropped_weights(rows, wts[i].shape[0], wts[i].shape[1], kp, ld, plan.tiles[i - 1], drop)
+                    K.conv3x3_dropped(x, ww, rate, sl, kx, train, xt, drop)
                     del ww
                 else:
-                    K.conv3x3(x, wts[i], dil=rate, out=sl, keep_xt=kx, want_stats=train, xt=pre_xt[i - 1] if pre_xt else None)
-                if pre_xt:
-                    pre_xt[i - 1] = None                  # the layer owns it now (kept for the weight gradient, or freed)
-                aspp_xt[i] = kx.get("xt") if kx else None
+                    K.conv3x3(x, wts[i], dil=rate, out=sl, keep_xt=kx, want_stats=train, xt=xt)
+                del xt
+                if kx:
+                    aspp_xt[i] = kx["xt"]
             states.append(K.bn_fold(feat[1], sl, train, out=(scale[256 * (i + 1):256 * (i + 2)], shift[256 * (i + 1):256 * (i + 2)])))
         up_small = K.conv2d(raw, K.packed(self.bot_aspp.weight), in_affine=(scale, shift), in_relu=True)
         # dec0 = concat [bot_fine(m2), up(bot_aspp)]: when nothing needs it as a tensor (final.0 is not trained in either stage of
@@ -459,7 +441,7 @@ class DeepWV3Plus(nn.Module):
         # the two decoder convolutions keep their Winograd-domain inputs for the weight gradient too (2.3 + 1.9 GB at
         # 2x1024x2048; re-transforming costs 0.73 ms each), under the same budget as the ASPP layers
         dec_xt_bytes = K.wino_xt_bytes(N, h2, w2, 304, 1) + K.wino_xt_bytes(N, h2, w2, 256, 1)
-        keep_dec = keep and xt_bytes + dec_xt_bytes < (40 << 30) and os.environ.get("MSS_KEEP_DEC_XT", "1") != "0"
+        keep_dec = keep and plan.xt_bytes + dec_xt_bytes < aspp_plan.XT_BUDGET_BYTES and os.environ.get("MSS_KEEP_DEC_XT", "1") != "0"
         kx0 = {} if (keep_dec and self.final[0].weight.requires_grad) else None
         kx3 = {} if (keep_dec and self.final[3].weight.requires_grad) else None
         if f0 is None:
@@ -474,7 +456,7 @@ class DeepWV3Plus(nn.Module):
                                       want_logit=want_logit)
         saved = None
         if keep:
-            saved = dict(aspp_xt=aspp_xt, x=x, fx=fx, comp=comp, drop=drop, m2=m2, raw=raw, scale=scale, shift=shift, states=states, pooled_act=pooled_act,
+            saved = dict(plan=plan, aspp_xt=aspp_xt, x=x, fx=fx, comp=comp, drop=drop, m2=m2, raw=raw, scale=scale, shift=shift, states=states, pooled_act=pooled_act,
                          u0_rows=u0_rows, dec0=dec0, f0=f0, st_f0=st_f0, f1=f1, st_f1=st_f1, dec12=dec12, size=size, final_xt=final_xt)
         return score, logit, saved
 
@@ -561,7 +543,7 @@ class DeepWV3Plus(nn.Module):
             if any(need[n] for n in names if n.startswith("aspp")):
                 d_act = K.conv2d(d_up, K.packed(self.bot_aspp.weight, flip=True))
                 states = s["states"]
-                comp, fx, drop = s["comp"], s["fx"], s["drop"]
+                plan, comp, fx, drop = s["plan"], s["comp"], s["fx"], s["drop"]
                 held = {}          # composed route: this loop's gradients, handed on in its own order once the four are projected
                 out = grads if comp is None else held
                 # the three dilated branches first (37.7 MB of gradient each), the two 4 MB branches last: under data parallelism the
@@ -581,7 +563,8 @@ class DeepWV3Plus(nn.Module):
                                  K.conv2d_wgrad(fx.a1, draw, 256, fx.a1.C, 1, 1, in_affine=fx.aff1, in_relu=True)], dim=1)
                         elif i == 0:
                             out[p + ".0.weight"] = K.conv2d_wgrad(x, draw, 256, 4096, 1, 1)
-                        elif drop is not None and s["aspp_xt"].get(i) is not None:
+                        elif plan.dropped:
+                            # (its X' is always kept: a step over the X' budget does not take the dropped route)
                             out[p + ".0.weight"] = K.conv3x3_wgrad_dropped(x, draw, 256, 4096, _ASPP_RATES[i - 1], s["aspp_xt"].pop(i), drop)
                         else:
                             out[p + ".0.weight"] = K.conv3x3_wgrad(x, draw, 256, 4096, dil=_ASPP_RATES[i - 1],

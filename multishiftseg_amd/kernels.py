@@ -9,8 +9,9 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, aspp_plan
 from ._lib import MssConvArgs, call, ptr
+from .aspp_plan import WINOGRAD_MIN_CHANNELS, use_winograd, wino_tile     # noqa: F401  (the Winograd tile policy, host-only)
 
 
 class Act:
@@ -474,41 +475,7 @@ def packed_wino(param, flip=False, tile=2):
     return _cached_pack(param, ("wino", flip, tile), lambda: pack_weight_wino(param, flip, tile))
 
 
-# measured on MI355X (tools/bench_wino.py): F(2x2) 0.87x at 128 channels, 1.24-1.28x at 256, 1.7-2.1x at >= 512;
-# F(4x4) 1.29x at 128 channels, 2.0x at 256, 2.4-3.4x at >= 512; F(6x6): 64 -> 128 at 512x1024 1.50 -> 0.8 ms
-WINOGRAD_MIN_CHANNELS = {2: 256, 4: 128, 6: 64}
 WINO_TILE_OF_P = {16: 2, 36: 4, 64: 6}
-
-
-def use_winograd(c_in, k_out, stride, in_affine=None, tile=2):
-    """Policy: 3x3 stride-1 layers whose channel counts make the two HBM-bound transforms cheaper than the
-    MFMA work they remove. MSS_WINOGRAD=0 forces the direct implicit GEMM everywhere."""
-    if os.environ.get("MSS_WINOGRAD", "1") == "0" or stride != 1:
-        return False
-    if in_affine is not None and in_affine[0].dim() != 1:
-        return False
-    lo = WINOGRAD_MIN_CHANNELS[tile]
-    return c_in >= lo and k_out >= lo and c_in % 16 == 0 and k_out % 4 == 0
-
-
-def wino_tile(H, W, dil, max_tile=6):
-    """Output-tile edge m of F(m x m, 3x3) for a layer: the one with fewer Winograd-domain elements
-    (tiles x (m+2)^2), which decides both the MFMA work and the transform traffic: 1.78 per output pixel for m = 6,
-    2.25 for m = 4, 4 for m = 2, unless the dilation sub-grid is so small that the larger tiles are mostly padding
-    (e.g. a 12x16 map at dilation 12; the 4x8 sub-grids of dilation 36 at 128x256 stay on 4x4 tiles, the 6x11 ones of
-    dilation 24 go from six 4x4 tiles to two 6x6 tiles). m = 6 carries 3x the fp32 rounding error of m = 4 (5.8e-6 vs
-    1.9e-6 of the output per layer, tools/wino_matrices.py), so it must save at least 5 % to be chosen, and the caller
-    caps it (`max_tile`) on the layers whose error the rest of the network amplifies most (deepv3.wino_cap).
-    MSS_WINO_TILE=2|4|6 forces one, MSS_WINO_MAX_TILE=4 keeps the policy off 6x6 tiles everywhere."""
-    forced = os.environ.get("MSS_WINO_TILE")
-    if forced:
-        return int(forced)
-    hs, ws = -(-H // dil), -(-W // dil)
-    cost = {m: (-(-hs // m)) * (-(-ws // m)) * (m + 2) ** 2 for m in (2, 4, 6)}
-    best = 4 if cost[4] < cost[2] else 2
-    if min(max_tile, int(os.environ.get("MSS_WINO_MAX_TILE", "6"))) >= 6 and cost[6] <= 0.95 * cost[best]:
-        best = 6
-    return best
 
 
 def wino_xt_bytes(N, H, W, C, dil):
@@ -533,7 +500,7 @@ def conv3x3(x, weight, dil=1, stride=1, in_affine=None, in_relu=False, res=None,
     """3x3 convolution with padding = dilation on nn.Conv2d-layout `weight` (flip=True: its data gradient),
     through Winograd when the policy says so, else through the direct implicit GEMM. max_tile: accuracy cap on the
     Winograd tile edge for this layer (0: no Winograd at all). xt: the layer's Winograd-domain input X' when the caller has
-    it already (aspp_input_transforms); its tile edge decides the route."""
+    it already (aspp_transforms); its tile edge decides the route."""
     k_out, c_in = (weight.shape[1], weight.shape[0]) if flip else (weight.shape[0], weight.shape[1])
     if xt is not None:
         assert in_affine is None and not in_relu and not flip and stride == 1
@@ -587,42 +554,44 @@ def _set_wino_w(a, ww):
     a.w = ptr(ww.t)
 
 
-def _wino_gemm_and_output(xt, ww, N, H, W, dil, res, out, keep_xt, want_stats, dropped=None):
-    """Steps 2 and 3 of the Winograd convolution on a transformed input X' [P][T][C]: the batched MFMA products and the output
-    transform (+ residual, + BatchNorm partial sums). dropped (an AsppDropped; ww then holds one U per image, [P][N][Kpad][C]): the
-    batch entries are (position, image) and image n multiplies its first C0 + 16 k_steps[n] columns only."""
-    C, K, ts = ww.C, ww.K, ww.tile
-    P, T = xt.shape[0], xt.shape[1]
-    dev = xt.device
-    if out is None:
-        # pixel rows on 128-byte lines: a 304-channel map (the decoder's first data gradient) with ld = 304 shares every other
-        # cache line between two pixels that different waves write (0.99 -> 0.94 ms at 2 x 512 x 1024, tools/bench_wino_r04.py)
-        out = Act.empty(N, H, W, K, dev, ld=_round_up(K, 32) if K % 32 else None)
-    yt = torch.empty((P, T, K), device=dev, dtype=torch.float32)
+def _wino_args(xt, T, C, K, Kpad, batch, dropped=None):
+    """What the MssConvArgs of every Winograd-domain batched product share, forward and weight gradient: `batch` 1x1 products over T
+    rows of X' [batch][T][C]. dropped (an AsppDropped): the batch entries are (position, image), T one image's rows, and image n
+    multiplies its first C0 + 16 k_steps[n] columns only."""
     a = MssConvArgs()
-    a.x, a.y = ptr(xt), ptr(yt)
-    a.w_split = w_split_of(ww)
+    a.x = ptr(xt)
     a.N, a.H, a.W, a.C, a.ldx = 1, 1, T, C, C
-    a.OH, a.OW, a.K, a.Kpad, a.ldy = 1, T, K, ww.Kpad, K
+    a.OH, a.OW, a.K, a.Kpad = 1, T, K, Kpad
     a.R, a.S, a.stride, a.dil, a.pad = 1, 1, 1, 1, 0
-    a.batch, a.x_bs, a.w_bs, a.y_bs = P, T * C, ww.Kpad * ww.Cp, T * K
+    a.batch, a.x_bs, a.y_bs = batch, T * C, T * K
+    if dropped is not None:
+        a.k_steps, a.k_base, a.k_imgs = ptr(dropped.k_steps), dropped.C0 // 16, dropped.N
+    return a
+
+
+def _wino_product(xt, ww, dropped=None):
+    """Step 2 of the Winograd convolution on a transformed input X' [P][T][C] (2P positions for a packed_wino_pair): the batched MFMA
+    products, Y' [P][T][K]. dropped (an AsppDropped; ww then holds one U per image, [P][N][Kpad][C]): _wino_args' per-image form."""
+    C, K = ww.C, ww.K
+    P, T = xt.shape[0], xt.shape[1]
+    yt = torch.empty((P, T, K), device=xt.device, dtype=torch.float32)
     rem = K % 128
     split = K - rem if (K > 128 and 0 < rem <= 64) else 0     # e.g. 304 = 256 + 48: narrow tail on the 64-wide tile
+    if dropped is None:
+        a = _wino_args(xt, T, C, K, ww.Kpad, P)
+        a.w_split = w_split_of(ww)
+        executed, cols = float(T) * C, C
+    else:
+        N = dropped.N
+        assert not split and T % N == 0 and ww.Kpad == K
+        a = _wino_args(xt, T // N, C, K, ww.Kpad, P * N, dropped)
+        executed, cols = float(T // N) * dropped.columns(), int(dropped.columns() / N)
+    a.y, a.ldy, a.w_bs = ptr(yt), K, ww.Kpad * ww.Cp
     if split:
         a.K = split
-    executed = float(T) * C
-    if dropped is not None:
-        assert not split and T % N == 0 and dropped.N == N and ww.Kpad == K
-        Ti = T // N
-        a.W = a.OW = Ti
-        a.batch, a.x_bs, a.y_bs = P * N, Ti * C, Ti * K
-        a.w_split = None
-        a.k_steps, a.k_base, a.k_imgs = ptr(dropped.k_steps), dropped.C0 // 16, N
-        executed = float(Ti) * dropped.columns()
     _set_wino_w(a, ww)
     # (bench.py unpacks this tag as eight numbers; the dropped form reports the mean number of columns an image's rows hold)
-    tag = (P, 1, T, C if dropped is None else int(dropped.columns() / N), K, 1, 1, 1)
-    with _Timed(_fwd_kind(a), 2.0 * P * executed * K, tag):   # the MFMA work actually executed
+    with _Timed(_fwd_kind(a), 2.0 * P * executed * K, (P, 1, T, cols, K, 1, 1, 1)):   # the MFMA work actually executed
         call("mss_conv2d_forward_f32", ctypes.byref(a))
         if split:
             a.K, a.Kpad = rem, ww.Kpad - split
@@ -630,17 +599,32 @@ def _wino_gemm_and_output(xt, ww, N, H, W, dil, res, out, keep_xt, want_stats, d
             a.w = ctypes.c_void_p(ww.t.data_ptr() + 4 * split * ww.Cp)
             a.y = ctypes.c_void_p(yt.data_ptr() + 4 * split)
             call("mss_conv2d_forward_f32", ctypes.byref(a))
-    if keep_xt is not None:
-        keep_xt["xt"] = xt
-    del xt
+    return yt
+
+
+def _wino_output(yt, N, H, W, K, dil, ts, res, out, want_stats):
+    """Step 3: the output transform of Y' [P][T][K] into `out` (+ residual, + BatchNorm partial sums left on out.stats)."""
     out.stats = None
     if want_stats and out.C == K:
-        out.stats = torch.empty((_lib.value("mss_wino_output_stats_parts", N, H, W, K, dil, ts), 2, K), device=dev,
+        out.stats = torch.empty((_lib.value("mss_wino_output_stats_parts", N, H, W, K, dil, ts), 2, K), device=yt.device,
                                 dtype=torch.float32)
-    with _Timed("wino_transform", 4.0 * (P * T * K + N * H * W * K * (2 if res is not None else 1)), ("output", N, H, W, K, dil, ts)):
+    with _Timed("wino_transform", 4.0 * (yt.numel() + N * H * W * K * (2 if res is not None else 1)), ("output", N, H, W, K, dil, ts)):
         call("mss_wino_output_transform_f32", ptr(yt), N, H, W, K, dil, ts, res.ptr if res is not None else None,
              res.ld if res is not None else 0, out.ptr, out.ld, ptr(out.stats))
     return out
+
+
+def _wino_gemm_and_output(xt, ww, N, H, W, dil, res, out, keep_xt, want_stats, dropped=None):
+    """Steps 2 and 3 of the Winograd convolution on a transformed input X' [P][T][C] (_wino_product, _wino_output)."""
+    if out is None:
+        # pixel rows on 128-byte lines: a 304-channel map (the decoder's first data gradient) with ld = 304 shares every other
+        # cache line between two pixels that different waves write (0.99 -> 0.94 ms at 2 x 512 x 1024, tools/bench_wino_r04.py)
+        out = Act.empty(N, H, W, ww.K, xt.device, ld=_round_up(ww.K, 32) if ww.K % 32 else None)
+    yt = _wino_product(xt, ww, dropped)
+    if keep_xt is not None:
+        keep_xt["xt"] = xt
+    del xt
+    return _wino_output(yt, N, H, W, ww.K, dil, ww.tile, res, out, want_stats)
 
 
 def packed_wino_pair(p1, p2, tile):
@@ -667,29 +651,8 @@ def packed_wino_pair(p1, p2, tile):
 
 
 def conv3x3_pair_tile(x, w1, w2, dil1, dil2):
-    """Tile edge when two 3x3 / stride-1 layers on the SAME input (ASPP's dilated branches) can share one batched GEMM launch
-    and it pays, else 0: same Winograd tile and tile count, K a multiple of 128, and the joint launch fills its rounds of
-    workgroup slots better than each alone -- the one-image eval forward: 64 x 1152 x 4096 -> 256 is 1152 narrow tiles = 1.5
-    rounds of 768 slots (106 TFLOP/s), the pair exactly 3 (MSS_WINO_PAIR=0 switches it off)."""
-    if os.environ.get("MSS_WINO_PAIR", "1") == "0" or _tile_hook is not None or w1.shape != w2.shape:
-        return 0
-    k, c = w1.shape[0], w1.shape[1]
-    t1, t2 = wino_tile(x.H, x.W, dil1), wino_tile(x.H, x.W, dil2)
-    if t1 != t2 or not t1 or not use_winograd(c, k, 1, None, t1) or k % 128:
-        return 0
-    T1 = _lib.value("mss_wino_num_tiles", x.N, x.H, x.W, dil1, t1)
-    if T1 != _lib.value("mss_wino_num_tiles", x.N, x.H, x.W, dil2, t1):
-        return 0
-    P = (t1 + 2) ** 2
-
-    def eff(positions):                 # the better of the wide (k / 256 column tiles, 512 slots) and narrow (k / 128, 768) launches
-        best = 0.0
-        for bn, slots in ((256, 512), (128, 768)):
-            if k % bn == 0:
-                tiles = positions * -(-T1 // 128) * (k // bn)
-                best = max(best, tiles / (-(-tiles // slots) * slots))
-        return best
-    return t1 if eff(2 * P) > eff(P) + 0.1 else 0
+    """aspp_plan.pair_tile for two weights on the map x: the tile edge when the two layers share one product launch, else 0."""
+    return aspp_plan.pair_tile(x.N, x.H, x.W, w1.shape, w2.shape, dil1, dil2, _tile_hook is not None)
 
 
 def conv3x3_pair(x, w1, w2, dil1, dil2, out1, out2, tile, want_stats=False, xt=None):
@@ -698,36 +661,20 @@ def conv3x3_pair(x, w1, w2, dil1, dil2, out1, out2, tile, want_stats=False, xt=N
     ww = packed_wino_pair(w1, w2, tile)
     N, H, W, C, Ko = x.N, x.H, x.W, ww.C, ww.K
     P = (tile + 2) ** 2
-    dev = x.buf.device
     T = _lib.value("mss_wino_num_tiles", N, H, W, dil1, tile)
     with _Timed("conv_winograd", 2 * 2.0 * N * H * W * Ko * C * 9, (N, H, W, C, 2 * Ko, 3, 1, (dil1, dil2))):
         if xt is None:
-            xt = torch.empty((2 * P, T, C), device=dev, dtype=torch.float32)
+            xt = torch.empty((2 * P, T, C), device=x.buf.device, dtype=torch.float32)
             for j, d in enumerate((dil1, dil2)):
                 with _Timed("wino_transform", 4.0 * (N * H * W * C + P * T * C), ("input", N, H, W, C, d, tile)):
                     call("mss_wino_input_transform_f32", x.ptr, x.ld, N, H, W, C, d, tile, None, None, 0, ptr(xt[j * P:(j + 1) * P]))
         else:
             assert tuple(xt.shape) == (2 * P, T, C)
-        yt = torch.empty((2 * P, T, Ko), device=dev, dtype=torch.float32)
-        a = MssConvArgs()
-        a.x, a.y = ptr(xt), ptr(yt)
-        a.w_split = w_split_of(ww)
-        a.N, a.H, a.W, a.C, a.ldx = 1, 1, T, C, C
-        a.OH, a.OW, a.K, a.Kpad, a.ldy = 1, T, Ko, ww.Kpad, Ko
-        a.R, a.S, a.stride, a.dil, a.pad = 1, 1, 1, 1, 0
-        a.batch, a.x_bs, a.w_bs, a.y_bs = 2 * P, T * C, ww.Kpad * ww.Cp, T * Ko
-        _set_wino_w(a, ww)
-        with _Timed(_fwd_kind(a), 2.0 * 2 * P * T * C * Ko, (2 * P, 1, T, C, Ko, 1, 1, 1)):
-            call("mss_conv2d_forward_f32", ctypes.byref(a))
+        assert Ko % 128 == 0                      # (conv3x3_pair_tile's rule: no narrow tail, so ONE launch)
+        yt = _wino_product(xt, ww)
         del xt
         for j, (d, out) in enumerate(((dil1, out1), (dil2, out2))):
-            out.stats = None
-            if want_stats and out.C == Ko:
-                out.stats = torch.empty((_lib.value("mss_wino_output_stats_parts", N, H, W, Ko, d, tile), 2, Ko), device=dev,
-                                        dtype=torch.float32)
-            with _Timed("wino_transform", 4.0 * (P * T * Ko + N * H * W * Ko), ("output", N, H, W, Ko, d, tile)):
-                call("mss_wino_output_transform_f32", ptr(yt[j * P:(j + 1) * P]), N, H, W, Ko, d, tile, None, 0, out.ptr, out.ld,
-                     ptr(out.stats))
+            _wino_output(yt[j * P:(j + 1) * P], N, H, W, Ko, d, tile, None, out, want_stats)
     return out1, out2
 
 
@@ -763,22 +710,34 @@ class FactoredAct:
 
 
 def aspp_compose_wanted():
-    """The switch of the composed ASPP route (MSS_ASPP_COMPOSE, default 1): taken under the Winograd policy without a tile hook; the
-    shapes are the caller's to check (deepv3.DeepWV3Plus._aspp_compose_gate)."""
-    return os.environ.get("MSS_ASPP_COMPOSE", "1") != "0" and _tile_hook is None and os.environ.get("MSS_WINOGRAD", "1") != "0"
+    """aspp_plan.compose_wanted under the current tile hook: the switch of the composed ASPP route."""
+    return aspp_plan.compose_wanted(_tile_hook is not None)
 
 
 def aspp_tiles(H, W, C, rates, weights):
-    """The tile edges of the three dilated ASPP branches where the single-read transforms apply -- rates (d, 2d, 3d), every tile 4
-    or 6 under the Winograd policy, no tile hook -- else None."""
-    d = rates[0]
-    if _tile_hook is not None or tuple(rates) != (d, 2 * d, 3 * d):
-        return None
-    tiles = [wino_tile(H, W, r) for r in rates]
-    for w, t in zip(weights, tiles):
-        if t not in (4, 6) or w.shape[1] != C or not use_winograd(w.shape[1], w.shape[0], 1, None, t):
-            return None
-    return tiles
+    """aspp_plan.tiles for three weights under the current tile hook: the tile edges where the single-read transforms apply, or None."""
+    return aspp_plan.tiles(H, W, C, rates, [w.shape for w in weights], _tile_hook is not None)
+
+
+def _factored_facts(x):
+    """What aspp_plan wants to know of a FactoredAct (nothing of an Act)."""
+    if not isinstance(x, FactoredAct):
+        return {}
+    return dict(factored=True, c0=x.a0.C, aff_dims=(x.aff0[0].dim(), x.aff1[0].dim()),
+                mask=x.mask is not None and tuple(x.mask.shape) == (x.N, x.a1.C))
+
+
+def aspp_dropped_wanted(fx, weights):
+    """aspp_plan.dropped_wanted for a FactoredAct and the three dilated branches' weights under the current GEMM route."""
+    f = _factored_facts(fx)
+    return bool(f) and aspp_plan.dropped_wanted(gemm_route(), f["c0"], fx.a1.C, f["aff_dims"], f["mask"], [w.shape for w in weights])
+
+
+def aspp_plan_for(x, rates, weights, keep=False, wgrad=(False, False, False), budget=aspp_plan.XT_BUDGET_BYTES):
+    """The aspp_plan.AsppPlan of one head forward on the map x (an Act or a FactoredAct) with the three dilated branches' weights:
+    the facts of x, the GEMM route and the tile hook, read here once."""
+    return aspp_plan.plan(x.N, x.H, x.W, x.C, [w.shape for w in weights], rates, keep=keep, wgrad=wgrad, route=gemm_route(),
+                          hook=_tile_hook is not None, budget=budget, **_factored_facts(x))
 
 
 class AsppDropped:
@@ -806,38 +765,72 @@ class AsppDropped:
         return float(self.N * self.C0 + 16 * int(self.k_steps.sum().item()))
 
 
-def aspp_dropped_wanted(fx, weights):
-    """True where the composed ASPP route leaves the Dropout2d-zeroed channels of its second factor out of the three dilated branches
-    (MSS_ASPP_DROPOUT_COMPACT, default 1): native route, a train-mode mask with its per-sample affine, C0 % 16 == 0, 48 <= C1 <= 2048,
-    C1 % 16 == 0, (C0 + C1) % 128 == 0, every weight's K a multiple of 128 and at most 4096. Everything else keeps the dense products."""
-    if os.environ.get("MSS_ASPP_DROPOUT_COMPACT", "1") == "0" or gemm_route() == "bf16x3":
-        return False
-    if not isinstance(fx, FactoredAct) or fx.mask is None or fx.aff1[0].dim() != 2 or fx.aff0[0].dim() != 1:
-        return False
-    c0, c1 = fx.a0.C, fx.a1.C
-    if c0 % 16 or c1 % 16 or c1 < 48 or c1 > 2048 or (c0 + c1) % 128 or tuple(fx.mask.shape) != (fx.N, c1):
-        return False
-    return all(w.shape[0] % 128 == 0 and w.shape[0] <= 4096 and w.shape[1] == c0 + c1 for w in weights)
+class AsppXt:
+    """The Winograd-domain inputs of the three dilated ASPP branches: xts, the three X' [P][T][C]; both, the ONE [2P][T][C] buffer
+    the first two are the halves of when the plan pairs their products (kernels.conv3x3_pair), else None. A branch takes its X':
+    the layer owns it then (kept for the weight gradient, or freed)."""
+    __slots__ = ("xts", "both")
+
+    def __init__(self, plan, C, dev):
+        def empty(m, n=1):
+            return torch.empty((n * plan.Ps[m], plan.Ts[m], C), device=dev, dtype=torch.float32)
+        self.both = empty(0, 2) if plan.pair_tile else None
+        assert self.both is None or (plan.Ts[0] == plan.Ts[1] and plan.tiles[0] == plan.tiles[1] == plan.pair_tile)
+        self.xts = ([self.both[:plan.Ps[0]], self.both[plan.Ps[0]:]] if plan.pair_tile else [empty(0), empty(1)]) + [empty(2)]
+
+    def take_pair(self):
+        both, self.both, self.xts[0], self.xts[1] = self.both, None, None, None
+        return both
+
+    def take(self, m):
+        xt, self.xts[m] = self.xts[m], None
+        return xt
 
 
-def aspp_dropped_separate_transforms(fx, rates, weights, dropped, max_bytes=None):
-    """The second formulation of the dropped-channel transform (MSS_WINO_ASPP3=0, as for the dense route): the compacted map
-    [u ; compacted v] is materialised with its 4096-column pitch and each dilation runs the plain input transform on it; GAP(w) comes
-    from the two-source kernel's sums-only mode. The columns an image's rows hold get the bits of the single-read kernel; the columns
-    behind them are transformed too (zeros), which nothing reads. (xts, gap) or (None, None) outside the same bounds."""
+def aspp_transforms(x, rates, plan, dropped=None):
+    """(AsppXt, gap): X' of the ONE map `x` for the three dilated 3x3 branches of ASPP (deepv3.py:84-92; rates d, 2d, 3d) from a
+    single read of x (mss_wino_input_transform_aspp3_f32): bit-identical to the three separate input transforms, 1 x instead of
+    3 x 1.07 GB read at 2 x 128 x 256 x 4096; gap is None. x a FactoredAct: the two-source kernel
+    (mss_wino_input_transform_aspp3_src2_f32) on the map that is never stored, gap [N, C] its global average from the same kernel;
+    where the plan takes no X' from it (not single_read: MSS_WINO_ASPP3=0, over budget) the kernel runs in its sums-only mode and the
+    answer is (None, gap). dropped (the plan's AsppDropped): mss_wino_input_transform_aspp3_dropped_f32, image n's rows hold
+    [u ; kept channels of v] only. The plan (aspp_plan_for) says single_read or gap_from_kernel: a refusal of the kernel is an error."""
+    factored = isinstance(x, FactoredAct)
+    assert (plan.gap_from_kernel and (plan.single_read or dropped is None)) if factored else (plan.single_read and dropped is None)
+    N, H, W, C, d = x.N, x.H, x.W, x.C, rates[0]
+    dev = x.buf.device
+    out = AsppXt(plan, C, dev) if plan.single_read else None
+    xts = [ptr(t) for t in out.xts] if out else [None, None, None]
+    ctiles = (ctypes.c_int * 3)(*plan.tiles)
+    nbytes = 4.0 * (N * H * W * C + (sum(p * t for p, t in zip(plan.Ps, plan.Ts)) * C if out else 0))
+    tag = ("input_aspp3" if out else "aspp_gap", N, H, W, C, d, tuple(plan.tiles)) + (("dropped",) if dropped is not None else ())
+    if not factored:
+        with _Timed("wino_transform", nbytes, tag):
+            call("mss_wino_input_transform_aspp3_f32", x.ptr, x.ld, N, H, W, C, d, ctiles, *xts)
+        return out, None
+    sums = torch.empty((N, d * d, C), device=dev, dtype=torch.float32)       # fully overwritten by the kernel
+    gap = torch.empty((N, C), device=dev, dtype=torch.float32)
+    (sc0, sh0), (sc1, sh1) = x.aff0, x.aff1
+    assert all(t.is_contiguous() and t.shape[-1] == a.C for a, ts in ((x.a0, x.aff0), (x.a1, x.aff1)) for t in ts)
+    src0 = (x.a0.ptr, x.a0.ld, x.a0.C, ptr(sc0), ptr(sh0), x.a0.C if sc0.dim() == 2 else 0)
+    with _Timed("wino_transform", nbytes, tag):
+        if dropped is not None:
+            call("mss_wino_input_transform_aspp3_dropped_f32", *src0, dropped.xc.ptr, dropped.xc.ld, x.a1.C, ptr(dropped.place),
+                 ptr(dropped.k_steps), N, H, W, d, ctiles, *xts, ptr(sums), ptr(gap))
+        else:
+            call("mss_wino_input_transform_aspp3_src2_f32", *src0, x.a1.ptr, x.a1.ld, x.a1.C, ptr(sc1), ptr(sh1),
+                 x.a1.C if sc1.dim() == 2 else 0, N, H, W, d, ctiles, *xts, ptr(sums), ptr(gap))
+    return out, gap
+
+
+def aspp_dropped_separate_transforms(fx, rates, plan, dropped):
+    """The second formulation of the dropped-channel transform (the plan's dropped_separate: MSS_WINO_ASPP3=0, as for the dense
+    route): the compacted map [u ; compacted v] is materialised with its 4096-column pitch and each dilation runs the plain input
+    transform on it; GAP(w) comes from the two-source kernel's sums-only mode. The columns an image's rows hold get the bits of the
+    single-read kernel; the columns behind them are transformed too (zeros), which nothing reads. (AsppXt, gap) as above."""
+    assert plan.dropped_separate and not plan.pair_tile
     N, H, W, C = fx.N, fx.H, fx.W, fx.C
-    tiles = aspp_tiles(H, W, C, rates, weights)
-    if tiles is None:
-        return None, None
-    Ts = [_lib.value("mss_wino_num_tiles", N, H, W, r, t) for r, t in zip(rates, tiles)]
-    Ps = [(t + 2) ** 2 for t in tiles]
-    if any(4 * p * t * C >= 0xffffffff or t % N or p * N > 65535 for p, t in zip(Ps, Ts)):
-        return None, None
-    if max_bytes is not None and 4.0 * sum(p * t for p, t in zip(Ps, Ts)) * C > max_bytes:
-        return None, None
-    _none, gap = aspp_input_transforms(fx, rates, weights, 0, max_bytes=0, want_gap=True)
-    if gap is None:
-        return None, None
+    _none, gap = aspp_transforms(fx, rates, plan)                # (no single_read on this plan: the sums alone)
     dev = fx.buf.device
     wm = Act.zeros(N, H, W, C, dev)
     u = wm.slice(0, fx.a0.C)
@@ -850,87 +843,11 @@ def aspp_dropped_separate_transforms(fx, rates, weights, dropped, max_bytes=None
     call("mss_chan_compact_act_f32", fx.a1.ptr, fx.a1.ld, xc0.ptr, xc0.ld, N, hw, fx.a1.C, ptr(dropped.place), ptr(ks), ptr(fx.aff1[0]),
          ptr(fx.aff1[1]))
     wm.buf[..., fx.a0.C:] = xc0.buf
-    xts = []
-    for r, t, p, T in zip(rates, tiles, Ps, Ts):
-        xt = torch.empty((p, T, C), device=dev, dtype=torch.float32)
-        with _Timed("wino_transform", 4.0 * (N * hw * C + p * T * C), ("input", N, H, W, C, r, t)):
+    out = AsppXt(plan, C, dev)
+    for r, t, xt in zip(rates, plan.tiles, out.xts):
+        with _Timed("wino_transform", 4.0 * (N * hw * C + xt.numel()), ("input", N, H, W, C, r, t)):
             call("mss_wino_input_transform_f32", wm.ptr, wm.ld, N, H, W, C, r, t, None, None, 0, ptr(xt))
-        xts.append(xt)
-    return xts, gap
-
-
-def aspp_input_transforms(x, rates, weights, pair_tile=0, max_bytes=None, want_gap=False, dropped=None):
-    """X' of the ONE map `x` for the three dilated 3x3 branches of ASPP (deepv3.py:84-92; rates d, 2d, 3d) from a single read of x
-    (mss_wino_input_transform_aspp3_f32): bit-identical to the three separate input transforms, 1 x instead of 3 x 1.07 GB read at
-    2 x 128 x 256 x 4096. Returns [xt_d, xt_2d, xt_3d] -- with pair_tile (conv3x3_pair_tile) the first two are the halves of ONE
-    [2P, T, C] buffer, returned as its first element with None second -- or None when the policy / shapes do not take the fused
-    kernel (a tile edge of 2, Winograd off, a tile hook, sub-grids too large for LDS; MSS_WINO_ASPP3=0 switches it off).
-    x a FactoredAct: the two-source kernel (mss_wino_input_transform_aspp3_src2_f32) on the map that is never stored; with
-    want_gap the answer is (xts or None, gap [N, C] or None), the global average of that map from the same kernel -- from its
-    sums-only mode when X' is not taken here (MSS_WINO_ASPP3=0, over budget), None only where the kernel refuses the shape."""
-    factored = isinstance(x, FactoredAct)
-    assert factored or not want_gap
-    d = rates[0]
-    N, H, W, C = x.N, x.H, x.W, x.C
-    dev = x.buf.device
-    tiles = aspp_tiles(H, W, C, rates, weights)
-    want_xt = tiles is not None and os.environ.get("MSS_WINO_ASPP3", "1") != "0"
-    if want_xt and pair_tile and (tiles[0] != pair_tile or tiles[1] != pair_tile):
-        want_xt = False
-    Ts = Ps = None
-    if want_xt:
-        Ts = [_lib.value("mss_wino_num_tiles", N, H, W, r, t) for r, t in zip(rates, tiles)]
-        Ps = [(t + 2) ** 2 for t in tiles]
-        # all three X' are live at once here (2.25-4x the map each: 10.6 GB at 2 x 1024 x 2048); a caller that does not keep them for
-        # the backward passes its budget, beyond which each branch transforms for itself again with one X' live at a time (ADVICE r04)
-        if max_bytes is not None and 4.0 * sum(p * t for p, t in zip(Ps, Ts)) * C > max_bytes:
-            want_xt = False
-    if dropped is not None:
-        # the 32-bit operand offsets of the per-image products and their 65535 batch entries: outside them the dense form runs
-        if not want_xt or pair_tile or not want_gap or any(4 * p * t * C >= 0xffffffff or t % N or p * N > 65535 for p, t in zip(Ps, Ts)):
-            return None, None
-    if not want_xt and not (want_gap and tiles is not None):
-        return (None, None) if want_gap else None
-    both, xts = None, [None, None, None]
-    if want_xt:
-        if pair_tile:
-            assert Ts[0] == Ts[1]
-            both = torch.empty((2 * Ps[0], Ts[0], C), device=dev, dtype=torch.float32)
-            xts = [both[:Ps[0]], both[Ps[0]:], torch.empty((Ps[2], Ts[2], C), device=dev, dtype=torch.float32)]
-        else:
-            xts = [torch.empty((p, t, C), device=dev, dtype=torch.float32) for p, t in zip(Ps, Ts)]
-    nbytes = 4.0 * (N * H * W * C + (sum(p * t for p, t in zip(Ps, Ts)) * C if want_xt else 0))
-    ctiles = (ctypes.c_int * 3)(*tiles)
-    gap = None
-    if factored:
-        name = "mss_wino_input_transform_aspp3_src2_f32"
-        sums = None
-        if want_gap:
-            sums = torch.empty((N, d * d, C), device=dev, dtype=torch.float32)       # fully overwritten by the kernel
-            gap = torch.empty((N, C), device=dev, dtype=torch.float32)
-        (sc0, sh0), (sc1, sh1) = x.aff0, x.aff1
-        assert all(t.is_contiguous() and t.shape[-1] == a.C for a, ts in ((x.a0, x.aff0), (x.a1, x.aff1)) for t in ts)
-        if dropped is not None:
-            name = "mss_wino_input_transform_aspp3_dropped_f32"
-            with _Timed("wino_transform", nbytes, ("input_aspp3", N, H, W, C, d, tuple(tiles), "dropped")):
-                rc = _lib.status(name, x.a0.ptr, x.a0.ld, x.a0.C, ptr(sc0), ptr(sh0), x.a0.C if sc0.dim() == 2 else 0,
-                                 dropped.xc.ptr, dropped.xc.ld, x.a1.C, ptr(dropped.place), ptr(dropped.k_steps),
-                                 N, H, W, d, ctiles, ptr(xts[0]), ptr(xts[1]), ptr(xts[2]), ptr(sums), ptr(gap))
-        else:
-            with _Timed("wino_transform", nbytes, ("input_aspp3" if want_xt else "aspp_gap", N, H, W, C, d, tuple(tiles))):
-                rc = _lib.status(name, x.a0.ptr, x.a0.ld, x.a0.C, ptr(sc0), ptr(sh0), x.a0.C if sc0.dim() == 2 else 0,
-                                 x.a1.ptr, x.a1.ld, x.a1.C, ptr(sc1), ptr(sh1), x.a1.C if sc1.dim() == 2 else 0,
-                                 N, H, W, d, ctiles, ptr(xts[0]), ptr(xts[1]), ptr(xts[2]), ptr(sums), ptr(gap))
-    else:
-        name = "mss_wino_input_transform_aspp3_f32"
-        with _Timed("wino_transform", nbytes, ("input_aspp3", N, H, W, C, d, tuple(tiles))):
-            rc = _lib.status(name, x.ptr, x.ld, N, H, W, C, d, ctiles, ptr(xts[0]), ptr(xts[1]), ptr(xts[2]))
-    if rc == _lib.MSS_ERR_UNSUPPORTED:
-        return (None, None) if want_gap else None
-    if rc != 0:
-        raise _lib.MssError(f"{name} failed with code {rc}")
-    out = None if not want_xt else ([both, None, xts[2]] if pair_tile else xts)
-    return (out, gap) if want_gap else out
+    return out, gap
 
 
 def conv2d_wgrad_winograd(x, dy, K, C, dil=1, in_affine=None, in_relu=False, xt=None, tile=None):
@@ -957,12 +874,7 @@ def conv2d_wgrad_winograd(x, dy, K, C, dil=1, in_affine=None, in_relu=False, xt=
         with _Timed("wino_transform", 4.0 * (N * H * W * K + P * T * K), ("grad_output", N, H, W, K, dil, ts)):
             call("mss_wino_grad_output_transform_f32", dy.ptr, dy.ld, N, H, W, K, dil, ts, ptr(dyt))
         du = torch.empty((P, Kpad, Cp), device=dev, dtype=torch.float32)     # fully overwritten by the kernel
-        a = MssConvArgs()
-        a.x = ptr(xt)
-        a.N, a.H, a.W, a.C, a.ldx = 1, 1, T, C, C
-        a.OH, a.OW, a.K, a.Kpad = 1, T, K, Kpad
-        a.R, a.S, a.stride, a.dil, a.pad = 1, 1, 1, 1, 0
-        a.batch, a.x_bs, a.y_bs = P, T * C, T * K
+        a = _wino_args(xt, T, C, K, Kpad, P)
         a.route = 1 if gemm_route() == "bf16x3" else 0
         ws, ws_bytes = _wgrad_workspace(a, Cp, dev)
         with _Timed(_wgrad_kind(a, K), 2.0 * P * T * K * C, (P, 1, T, C, K, 1, 1, 1)):
@@ -988,8 +900,9 @@ def aspp_dropped_weights(rows, K, C, Kpad, ld, tile, dropped):
 
 
 def conv3x3_dropped(x, ww, dil, out, keep_xt, want_stats, xt, dropped):
-    """One dilated ASPP branch on the dropped-channel X' (aspp_input_transforms(..., dropped=)) with aspp_dropped_weights."""
+    """One dilated ASPP branch on the dropped-channel X' (aspp_transforms(..., dropped=)) with aspp_dropped_weights."""
     N, H, W, C, K = x.N, x.H, x.W, ww.C, ww.K
+    assert dropped.N == N
     with _Timed("conv_winograd", 2.0 * N * H * W * K * C * 9, (N, H, W, C, K, 3, 1, dil)):
         return _wino_gemm_and_output(xt, ww, N, H, W, dil, None, out, keep_xt, want_stats, dropped=dropped)
 
@@ -1010,13 +923,7 @@ def conv3x3_wgrad_dropped(x, dy, K, C, dil, xt, dropped):
         with _Timed("wino_transform", 4.0 * (N * H * W * K + P * T * K), ("grad_output", N, H, W, K, dil, ts)):
             call("mss_wino_grad_output_transform_f32", dy.ptr, dy.ld, N, H, W, K, dil, ts, ptr(dyt))
         du = torch.empty((P, N * K, C), device=dev, dtype=torch.float32)     # tiles behind an image's extent stay unwritten, and unread
-        a = MssConvArgs()
-        a.x = ptr(xt)
-        a.N, a.H, a.W, a.C, a.ldx = 1, 1, Ti, C, C
-        a.OH, a.OW, a.K, a.Kpad = 1, Ti, K, K
-        a.R, a.S, a.stride, a.dil, a.pad = 1, 1, 1, 1, 0
-        a.batch, a.x_bs, a.y_bs = P * N, Ti * C, Ti * K
-        a.k_steps, a.k_base, a.k_imgs = ptr(dropped.k_steps), dropped.C0 // 16, N
+        a = _wino_args(xt, Ti, C, K, K, P * N, dropped)
         # optional scratch: with it the packed job plan cuts its last, partial round by rows
         ws = torch.empty(_lib.MSS_WGRAD_PERIMG_TAIL_BYTES // 4, device=dev, dtype=torch.float32)
         with _Timed("conv_wgrad", 2.0 * P * Ti * K * dropped.columns(), ("aspp_dropped", P, N, Ti, C, K)):

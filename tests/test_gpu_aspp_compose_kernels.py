@@ -111,6 +111,10 @@ def test_two_source_transform_refuses_what_it_does_not_take():
     assert run(tiles=(2, 4, 4)) == _lib.MSS_ERR_UNSUPPORTED                      # a 2 x 2 tile
     big = torch.zeros(1, 512, 1024, 8, device="cuda")                            # 43 x 86 base sub-grids: more than LDS holds
     assert run(tiles=(6, 6, 6), C0=4, C1=4, H=512, W=1024, d=12, src=big, ld=8) == _lib.MSS_ERR_UNSUPPORTED
+    # the host query says so beforehand (what aspp_plan asks, so that no caller meets the refusal at a launch)
+    assert _lib.value("mss_wino_aspp3_supported", 1, 512, 1024, 8, 12, (ctypes.c_int * 3)(6, 6, 6), 1) == 0
+    assert _lib.value("mss_wino_aspp3_supported", 1, 16, 16, 16, 4, (ctypes.c_int * 3)(2, 4, 4), 1) == 0
+    assert _lib.value("mss_wino_aspp3_supported", 1, 16, 16, 16, 4, (ctypes.c_int * 3)(4, 4, 4), 1) == 1
     assert run(null_tiles=True) == _lib.MSS_ERR_BAD_ARG
     assert run(scale=None) == _lib.MSS_ERR_BAD_ARG                               # both sources carry a prologue
     assert run(C0=6, C1=8) == _lib.MSS_ERR_BAD_ARG                               # channel counts in quads

@@ -276,9 +276,8 @@ def test_gate_leaves_other_shapes_and_the_split_route_dense(monkeypatch):
         assert not K.aspp_dropped_wanted(_factored(2, 8, 8, 128, 128), w)
     finally:
         K.set_gemm_route(None)
-    # a map outside the transform's gate (a tile edge of 2: the transform is not taken at all) answers None, None: the caller's
-    # dense path; nothing raises
-    fx = _factored(2, 8, 8, 128, 128)
-    drop = K.AsppDropped(fx)
-    assert K.aspp_input_transforms(fx, (12, 24, 36), w, 0, want_gap=True, dropped=drop)[0] is None
+    # a map outside the transform's gate (a tile edge of 2: the transform is not taken at all) plans the caller's dense path: no
+    # dropped products, no X' and no average from the kernel; nothing raises
+    plan = K.aspp_plan_for(_factored(2, 8, 8, 128, 128), (12, 24, 36), w)
+    assert plan.tiles is None and not plan.dropped and not plan.single_read and not plan.gap_from_kernel and plan.materialise
     torch.cuda.synchronize()

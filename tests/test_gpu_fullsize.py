@@ -454,7 +454,7 @@ def test_ood_tail_16x700x700_vs_oracle():
 @pytest.mark.parametrize("tag,pairs,h,w,tiles", [("c3_2x1024x2048", 1, 1024, 2048, [6, 6, 4]), ("c2_4x700x700", 2, 700, 700, [4, 4, 4])])
 def test_aspp_single_read_transform_changes_no_bit(deeplab_params, monkeypatch, tag, pairs, h, w, tiles):
     """The three dilated ASPP branches get their Winograd-domain inputs from ONE kernel that reads the 4096-channel map once
-    (kernels.aspp_input_transforms, round 4) -- against the three separate transforms (MSS_WINO_ASPP3=0): a stage-2
+    (kernels.aspp_transforms, round 4) -- against the three separate transforms (MSS_WINO_ASPP3=0): a stage-2
     forward/backward (X' kept for the weight gradients) and the one-image eval forward (dilations 12 / 24 in one paired GEMM)
     give identical bits, and the fused kernel is really the one taken at these sizes."""
     from multishiftseg_amd import kernels as K, synth

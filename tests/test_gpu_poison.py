@@ -202,9 +202,9 @@ def test_winograd_pair_and_aspp_transform(K, tile, gemm_route):
         o1, o2 = out_window(K, n, h, w, k, c0=0), out_window(K, n, h, w, k, c0=0)
         K.conv3x3_pair(xa, w1, w2, 1, 2, o1, o2, tile, want_stats=True)
         outs = [o1.nchw(), o2.nchw(), o1.stats, o2.stats]
-        xts = K.aspp_input_transforms(xa, (1, 2, 3), (w1, w2, w3))
-        if xts is not None:
-            for p, d, xt in zip((w1, w2, w3), (1, 2, 3), xts):
+        plan = K.aspp_plan_for(xa, (1, 2, 3), (w1, w2, w3))
+        if plan.single_read:
+            for p, d, xt in zip((w1, w2, w3), (1, 2, 3), K.aspp_transforms(xa, (1, 2, 3), plan)[0].xts):
                 outs.append(K.conv3x3(xa, p, dil=d, xt=xt).nchw())
         return outs
 
