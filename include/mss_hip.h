@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 23     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 24     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -56,7 +56,9 @@ extern "C" {
                                   MSS_WGRAD_PERIMG_TAIL_BYTES (the packed job plan's row-split last round);
                                   22: mss_m2f_targets_from_labels added (the Mask2Former target pack built from the label maps on the device); mss_peak_clock
                                   removed to make room (only a diagnostic tool called it);
-                                  23 (additive): mss_wino_aspp3_supported, the host query of what the three single-read ASPP transforms refuse */
+                                  23 (additive): mss_wino_aspp3_supported, the host query of what the three single-read ASPP transforms refuse;
+                                  24: no entry point or struct changes; mss_conv2d_forward_f32 takes the 7x7 / stride-2 / 4 -> 64 stem of the ResNet-50
+                                  backbone (csrc/stem7.hip), which it answered MSS_ERR_UNSUPPORTED before; mss_conv2d_forward_route labels it 5 */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -154,7 +156,15 @@ int mss_msda_prepare_ld_f32(const float* offsets, long long ld_offsets, const fl
  *        lib/network/deepv3/deepv3.py:258-285 and lib/network/deepv3/wider_resnet.py:169-182)      */
 
 /* One bias-free 2-D convolution as an implicit GEMM on fp32 MFMA.
- * replaces nn.Conv2d forward at deepv3.py:62-72,79-81,235-250 and wider_resnet.py:104-137,303-305 */
+ * replaces nn.Conv2d forward at deepv3.py:62-72,79-81,235-250 and wider_resnet.py:104-137,303-305
+ * Shapes: C % 16 == 0, ldx % 4 == 0, 1 <= R * S <= 9 -- and ONE more, the stem of the Mask2Former ResNet-50 backbone
+ * (detectron2 BasicStem.conv1; csrc/stem7.hip, v_mfma_f32_16x16x4_f32, one filter tap per instruction):
+ *   R == S == 7, stride == 2, pad == 3, dil == 1; C == 4 and ldx == 4 (the image as mss_nchw_to_nhwc_pad_f32 writes it with Cp = 4:
+ *   three colour channels and one ZERO channel, which is the caller's contract); K == 64, Kpad >= 64, w [49][Kpad][4] from
+ *   mss_conv2d_pack_weights_f32(K = 64, C = 3, R = S = 7, Cp = 4); batch <= 1; no prologue affine, res, stats, w_split or k_steps;
+ *   OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, ldy >= 64, ldy % 4 == 0, x and y 16-byte aligned. out_scale / out_shift and out_relu
+ *   are honoured; columns of y from 64 on are not written. Every other combination with C % 16 != 0 or R * S > 9 is
+ *   MSS_ERR_UNSUPPORTED as before. */
 typedef struct MssConvArgs {
   const float* x;          /* input  NHWC [N,H,W,>=C], pixel stride ldx                         */
   const float* w;          /* packed weights [R*S][Kpad][C] from mss_conv2d_pack_weights_f32     */
@@ -225,7 +235,8 @@ int mss_chan_compact_weights_f32(const float* w, float* out, int N, int Kpad, in
 int mss_conv2d_kpad(int K);
 /* 1 if mss_conv2d_forward_f32 runs these arguments on the persistent GEMM kernel (csrc/gemm.hip: 1x1, stride 1,
  * more than 64 output channels, or 33..64 of them over >= 16 384 rows), 2 for the few-rows kernel (1x1 over <= 8 pixels, nothing fused), 3 for the
- * split-bf16 form of the persistent GEMM kernel (args->w_split set and the shape eligible), 4 for its implicit-GEMM form, 0 for the native implicit-GEMM kernel. Profiling label only. */
+ * split-bf16 form of the persistent GEMM kernel (args->w_split set and the shape eligible), 4 for its implicit-GEMM form, 5 for the 7x7 stem kernel
+ * (csrc/stem7.hip; the shape listed above MssConvArgs), 0 for the native implicit-GEMM kernel. Profiling label only. */
 int mss_conv2d_forward_route(const MssConvArgs* args);
 /* The split-bf16 form of packed weights for MssConvArgs.w_split: w [batch][Kpad][C] fp32 (batch stride w_bs floats; what
  * mss_conv2d_pack_weights_f32 with R = S = 1 or mss_wino_pack_weights_f32 produce, Kpad % 128 == 0, C % 16 == 0) -> `planes`,

@@ -23,6 +23,12 @@ def __getattr__(name):
     if name in ("prepare_targets", "M2FTargets"):
         from . import m2f_targets
         return getattr(m2f_targets, name)
+    if name in ("ResNet", "build_resnet_backbone"):
+        from . import resnet
+        return getattr(resnet, name)
+    if name == "MaskFormer":
+        from .maskformer import MaskFormer
+        return MaskFormer
     if name in _M2F_TRAINER:
         from . import m2f_trainer
         return getattr(m2f_trainer, name)
@@ -30,4 +36,4 @@ def __getattr__(name):
 
 
 __all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention",
-           "prepare_targets", "M2FTargets", *_M2F_TRAINER]
+           "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER]

@@ -27,6 +27,8 @@ bool mss_gemm_few_rows(const MssConvArgs& p);
 bool mss_gemm_nt_bf16x3_eligible(const MssConvArgs& p);   // gemm_bf16x3.hip
 bool mss_conv_bf16x3_eligible(const MssConvArgs& p);
 int mss_conv_bf16x3_launch(MssConvArgs p, void* stream);
+bool mss_stem7_eligible(const MssConvArgs& p);            // stem7.hip: the 7x7 / stride-2 / 4 -> 64 stem of the ResNet-50 backbone
+int mss_stem7_launch(MssConvArgs p, void* stream);
 
 namespace {
 
@@ -370,6 +372,7 @@ extern "C" {
 int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
   MssConvArgs p = *args;
   if (!p.x || !p.w || !p.y) return MSS_ERR_BAD_ARG;
+  if (mss_stem7_eligible(p)) return mss_stem7_launch(p, stream);    // the one shape with C == 4 and 49 taps (route 5)
   if (p.C % 16 || p.ldx % 4 || p.R * p.S > 9 || p.R * p.S < 1) return MSS_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w)) & 15) return MSS_ERR_BAD_ARG;
   if (p.in_scale && ((reinterpret_cast<uintptr_t>(p.in_scale) | reinterpret_cast<uintptr_t>(p.in_shift)) & 15))
@@ -400,9 +403,10 @@ int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
 }
 
 // Which kernel mss_conv2d_forward_f32 runs for these arguments: 1 = gemm_nt_kernel (gemm.hip), 0 = conv_igemm_kernel, 2 = gemm_few_rows_kernel,
-// 3 = gemm_nt_bf16x3_kernel, 4 = its implicit-GEMM / per-sample-affine instantiations (args->w_split set).
+// 3 = gemm_nt_bf16x3_kernel, 4 = its implicit-GEMM / per-sample-affine instantiations (args->w_split set), 5 = stem7_conv_kernel (stem7.hip).
 int mss_conv2d_forward_route(const MssConvArgs* args) {
   MssConvArgs p = *args;
+  if (mss_stem7_eligible(p)) return 5;
   p.M = p.N * p.OH * p.OW;
   if (p.k_steps) return 1;
   if (!MSS_ENV_INT("MSS_GEMM", 1)) return mss_conv_bf16x3_eligible(p) ? 4 : 0;      // as the forward: MSS_GEMM=0 only skips the NT dispatch

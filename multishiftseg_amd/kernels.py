@@ -247,7 +247,7 @@ def _fwd_kind(a):
     """Profiling label of a forward launch: which of the two MFMA kernels the C side picks."""
     if _profile is None:
         return "conv_igemm"
-    return ("conv_igemm", "gemm_nt", "gemm_few_rows", "gemm_nt_bf16x3", "conv_igemm_bf16x3")[_lib.value("mss_conv2d_forward_route", ctypes.byref(a))]
+    return ("conv_igemm", "gemm_nt", "gemm_few_rows", "gemm_nt_bf16x3", "conv_igemm_bf16x3", "conv_stem7")[_lib.value("mss_conv2d_forward_route", ctypes.byref(a))]
 
 
 def _wgrad_kind(a, lddy):
@@ -982,6 +982,33 @@ def packed_stem(param):
         w[:, :27, 0, 0] = param.detach().reshape(k, 27)
         return pack_weight(w)
     return _cached_pack(param, ("stem",), make)
+
+
+def packed_stem7(param):
+    """stem.conv1.weight [64,3,7,7] as the [49][64][4] pack of the 7x7 stem kernel (csrc/stem7.hip): the fourth input channel is zero."""
+    def make():
+        w = param.detach().contiguous()
+        t = torch.empty((49, 64, 4), device=w.device, dtype=torch.float32)
+        call("mss_conv2d_pack_weights_f32", ptr(w), ptr(t), 64, 3, 7, 7, 64, 4, 0, None, 0, 0)
+        return PackedWeight(t, 64, 3, 7, 7, 64, 4)
+    return _cached_pack(param, ("stem7",), make)
+
+
+def stem7_conv(img_nchw, weight, out_affine, relu=True):
+    """[N,3,H,W] NCHW image, stem.conv1.weight [64,3,7,7] -> Act [N,(H-1)//2+1,(W-1)//2+1,64] = relu(conv7x7(img, stride 2, padding 3) *
+    scale + shift) (detectron2 BasicStem before its max-pool) on the 16x16x4 fp32 MFMA, one filter tap per instruction. The image
+    goes through image_to_nhwc(Cp=4); the kernel's contract is that this pad channel is zero."""
+    n, c, h, w = img_nchw.shape
+    if c != 3 or tuple(weight.shape) != (64, 3, 7, 7):
+        raise ValueError(f"the 7x7 stem expects a 3-channel image and a [64,3,7,7] weight, got {tuple(img_nchw.shape)} / {tuple(weight.shape)}")
+    if weight.dtype != torch.float32 or not weight.is_cuda or img_nchw.dtype != torch.float32 or not img_nchw.is_cuda:
+        raise TypeError("stem7_conv needs float32 CUDA tensors")
+    x = image_to_nhwc(img_nchw, Cp=4)
+    pw = packed_stem7(weight)
+    OH, OW = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    out = Act.empty(n, OH, OW, 64, img_nchw.device)
+    _conv_launch(x, pw, out, OH, OW, 2, 1, 3, None, False, out_affine, relu, None)
+    return out
 
 
 class BNState:

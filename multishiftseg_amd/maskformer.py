@@ -1,0 +1,75 @@
+"""The evaluation shell of Mask2Former: image batch -> anomaly score, and the validation / test sweep around it.
+
+Host-side mirror of the inference branch of ``MaskFormer.forward`` (lib/network/mask2former/maskformer_model.py:229-234,
+260-277) together with the score the trainer forms from its output (train_m2f.py:387-407). The children keep the reference's
+names -- ``backbone``, ``sem_seg_head.pixel_decoder``, ``sem_seg_head.predictor`` -- so a MaskFormer checkpoint's keys line up and
+m2f_trainer.build_m2f_param_groups finds "backbone" in the module names.
+
+The shell adds no arithmetic of its own: it zero-pads the batch bottom/right to the size divisibility (ImageList.from_tensors;
+there is no pixel normalisation, the reference fork has none either), runs backbone -> pixel_decoder.forward_features -> predictor
+with ``fuse_score`` and hands back what kernels.m2f_score_fused returns, already cropped to the images' own size.
+Not built: the per-class ``sem_seg`` map of semantic_inference (the reference's evaluation reads only its shape).
+"""
+import torch
+from torch import nn
+
+from .metric import OODMeter
+
+
+def padded_size(size, divisibility):
+    """ImageList.from_tensors: the next multiple of `divisibility` (<= 1: the size itself)."""
+    if divisibility <= 1:
+        return int(size)
+    return (int(size) + divisibility - 1) // divisibility * divisibility
+
+
+class _SemSegHead(nn.Module):
+    """MaskFormerHead's two children under its names (mask_former_head.py: pixel_decoder, predictor)."""
+
+    def __init__(self, pixel_decoder, predictor):
+        super().__init__()
+        self.pixel_decoder = pixel_decoder
+        self.predictor = predictor
+
+
+class MaskFormer(nn.Module):
+    def __init__(self, backbone, pixel_decoder, predictor, size_divisibility=32):
+        super().__init__()
+        self.backbone = backbone
+        self.sem_seg_head = _SemSegHead(pixel_decoder, predictor)
+        if size_divisibility < 0:
+            size_divisibility = getattr(backbone, "size_divisibility", 32)             # maskformer_model.py:77-79
+        self.size_divisibility = size_divisibility
+
+    def pad(self, images):
+        """[B, 3, H, W] -> [B, 3, Hp, Wp], zeros at the bottom and the right; the batch itself where nothing is to pad."""
+        H, W = images.shape[-2:]
+        Hp, Wp = padded_size(H, self.size_divisibility), padded_size(W, self.size_divisibility)
+        if (Hp, Wp) == (H, W):
+            return images
+        out = images.new_zeros(images.shape[:-2] + (Hp, Wp))
+        out[..., :H, :W] = images
+        return out
+
+    def forward(self, images):
+        """The predictor's dict for the padded batch, with "ood_score" [B, H, W] at the images' own size."""
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"MaskFormer takes [B, 3, H, W] image batches, got {tuple(images.shape)}")
+        H, W = images.shape[-2:]
+        with torch.no_grad():
+            x = self.pad(images.float())
+            features = self.backbone(x)
+            mask_features, _, multi_scale = self.sem_seg_head.pixel_decoder.forward_features(features)
+            return self.sem_seg_head.predictor(multi_scale, mask_features, None, fuse_score=(x.shape[-2], x.shape[-1], H, W))
+
+    def ood_score(self, images):
+        """Anomaly score [B, H, W] (train_m2f.py:387-407 on maskformer_model.py:260-277)."""
+        return self.forward(images)["ood_score"]
+
+    def evaluate(self, batches, meter=None):
+        """valid_batch / test (train_m2f.py:469-509, test_m2f.py:109-158) with no copy to the host: `batches` yields (images, target);
+        every score map goes to OODMeter.update on the device. Returns meter.compute()."""
+        meter = OODMeter() if meter is None else meter
+        for images, target in batches:
+            meter.update(self.ood_score(images), target)
+        return meter.compute()

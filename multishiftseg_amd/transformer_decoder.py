@@ -228,7 +228,8 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
     def forward(self, x, mask_features, mask=None, *, fuse_score=None, return_attn_bits=False):
         """As the reference's forward. fuse_score=(H, W): the last step's pixel-major mask logits go straight to
         kernels.m2f_score_fused with pred_logits_ood; the anomaly score [B, H, W] is returned as "ood_score" and the last step's
-        NCHW "pred_masks" / "pred_masks_ood" are not materialised (None). return_attn_bits: "attn_bits" = per layer the packed
+        NCHW "pred_masks" / "pred_masks_ood" are not materialised (None). fuse_score=(Hp, Wp, H, W): upsample to the padded image
+        size (Hp, Wp) and keep the top-left (H, W) of it (maskformer_model.py:264-277 + sem_seg_postprocess). return_attn_bits: "attn_bits" = per layer the packed
         mask words [B, 2, HW, ceil(Q/32)] (int32; bit q of [b, 0 | 1, key] set = query q does not attend to that key in the
         foreground | background attention) as the attention kernel applied them, i.e. after the rescue rule."""
         del mask                                                     # "disable mask, it does not affect performance" (:445)
@@ -415,7 +416,8 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
             "pred_logits_ood": ood_c[-1], "pred_masks_ood": ood_m[-1],
         }
         if fuse_score is not None:
-            out["ood_score"] = K.m2f_score_fused(ood_c[-1].detach(), last_logits, tuple(fuse_score))
+            fs = tuple(fuse_score)
+            out["ood_score"] = K.m2f_score_fused(ood_c[-1].detach(), last_logits, fs[:2], fs[2:] if len(fs) == 4 else None)
         if return_attn_bits:
             out["attn_bits"] = [bits & allowed.unsqueeze(2) for bits, allowed in bits_used]
         return out
