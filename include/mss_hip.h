@@ -609,7 +609,8 @@ int mss_m2f_fused_score_ws_f32(const float* cls, const float* logit, int B, int 
  *   allowed [B][2][W] words: bit q set <=> query q has at least one un-masked key (cleared by this call before the launch). A
  *           query whose bit is clear ignores its mask in mss_m2f_masked_attention_f32: the reference's
  *           attn_mask[where(attn_mask.sum(-1) == HW)] = False (:476-477) without the host round trip.
- * The mask is shared by the 8 heads.
+ * The mask is shared by the 8 heads. The bits of a last word past Q are clear in `bits` and unspecified in `allowed` (no reader
+ * looks at them).
  *
  * mss_m2f_masked_attention_f32: out[b, q, a, head, :] = softmax_key(scale * <q, k> + mask) v for 8 heads of 32 channels and A
  * attentions in one launch. q [B*Q, ldq], k [B*NK, ldk], v [B*NK, ldv], out [B*Q, ldo] row-major fp32; attention a, head hd use
