@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 24     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 25     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -58,7 +58,10 @@ extern "C" {
                                   removed to make room (only a diagnostic tool called it);
                                   23 (additive): mss_wino_aspp3_supported, the host query of what the three single-read ASPP transforms refuse;
                                   24: no entry point or struct changes; mss_conv2d_forward_f32 takes the 7x7 / stride-2 / 4 -> 64 stem of the ResNet-50
-                                  backbone (csrc/stem7.hip), which it answered MSS_ERR_UNSUPPORTED before; mss_conv2d_forward_route labels it 5 */
+                                  backbone (csrc/stem7.hip), which it answered MSS_ERR_UNSUPPORTED before; mss_conv2d_forward_route labels it 5;
+                                  25: no entry point or struct changes; mss_conv2d_forward_f32 takes MssConvArgs.stride == -2, the data gradient of a
+                                  stride-2 convolution (csrc/conv_dgrad_s2.hip; no caller passed a negative stride before);
+                                  mss_conv2d_forward_route labels it 6 */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -164,7 +167,21 @@ int mss_msda_prepare_ld_f32(const float* offsets, long long ld_offsets, const fl
  *   mss_conv2d_pack_weights_f32(K = 64, C = 3, R = S = 7, Cp = 4); batch <= 1; no prologue affine, res, stats, w_split or k_steps;
  *   OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, ldy >= 64, ldy % 4 == 0, x and y 16-byte aligned. out_scale / out_shift and out_relu
  *   are honoured; columns of y from 64 on are not written. Every other combination with C % 16 != 0 or R * S > 9 is
- *   MSS_ERR_UNSUPPORTED as before. */
+ *   MSS_ERR_UNSUPPORTED as before.
+ * stride == -2: the DATA GRADIENT of a stride-2 convolution (csrc/conv_dgrad_s2.hip; the backward of res3.0 / res4.0 / res5.0 of the
+ * ResNet-50 backbone), gather form, no atomics, bit-reproducible:
+ *   x = dz [N, H, W, C]: the strided convolution's output grid and its output channels; C % 16 == 0, ldx % 4 == 0.
+ *   w = the data-gradient filter from mss_conv2d_pack_weights_f32(flip = 1), [R*S][Kpad][C].
+ *   y = dx [N, OH, OW, K]: the strided convolution's input. OH and OW are the CALLER's, because the forward's floor loses one row or
+ *       column: MSS_ERR_BAD_ARG unless H == (OH + 2 * pad - R) / 2 + 1 and W == (OW + 2 * pad - S) / 2 + 1.
+ *   Shapes: R == S == 3 with pad == 1, R == S == 1 with pad == 0; dil == 1.
+ *   Honoured: in_scale / in_shift with in_ss_stride == 0 and in_relu, applied to in-grid operand rows only; res / ldres, added or
+ *       gating (res_mask); out_scale / out_shift; out_relu.
+ *   MSS_ERR_UNSUPPORTED: stats, batch > 1, k_steps, a per-sample prologue (in_ss_stride != 0), any other R, S, pad or dil.
+ *   w_split is ignored: the product runs on the native fp32 MFMA whatever the route.
+ *   The output pixels are enumerated per parity class (oy & 1, ox & 1), so a tile's live filter taps are block-uniform and exactly the
+ *   non-zero ones (3x3: 1 + 2 + 2 + 4 = 9 taps over the four classes; 1x1: one tap in class (0, 0)). A class without a live tap still
+ *   writes epilogue(0) -- res, the gate, or zero: EVERY element of y in columns [0, K) is written on every call. */
 typedef struct MssConvArgs {
   const float* x;          /* input  NHWC [N,H,W,>=C], pixel stride ldx                         */
   const float* w;          /* packed weights [R*S][Kpad][C] from mss_conv2d_pack_weights_f32     */
@@ -236,7 +253,8 @@ int mss_conv2d_kpad(int K);
 /* 1 if mss_conv2d_forward_f32 runs these arguments on the persistent GEMM kernel (csrc/gemm.hip: 1x1, stride 1,
  * more than 64 output channels, or 33..64 of them over >= 16 384 rows), 2 for the few-rows kernel (1x1 over <= 8 pixels, nothing fused), 3 for the
  * split-bf16 form of the persistent GEMM kernel (args->w_split set and the shape eligible), 4 for its implicit-GEMM form, 5 for the 7x7 stem kernel
- * (csrc/stem7.hip; the shape listed above MssConvArgs), 0 for the native implicit-GEMM kernel. Profiling label only. */
+ * (csrc/stem7.hip; the shape listed above MssConvArgs), 6 for the stride-2 data-gradient kernel (csrc/conv_dgrad_s2.hip; stride == -2),
+ * 0 for the native implicit-GEMM kernel. Profiling label only. */
 int mss_conv2d_forward_route(const MssConvArgs* args);
 /* The split-bf16 form of packed weights for MssConvArgs.w_split: w [batch][Kpad][C] fp32 (batch stride w_bs floats; what
  * mss_conv2d_pack_weights_f32 with R = S = 1 or mss_wino_pack_weights_f32 produce, Kpad % 128 == 0, C % 16 == 0) -> `planes`,

@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "masked_attention":
         from .kernels import masked_attention
         return masked_attention
+    if name == "conv2d_dgrad_s2":
+        from .kernels import conv2d_dgrad_s2
+        return conv2d_dgrad_s2
     if name in ("prepare_targets", "M2FTargets"):
         from . import m2f_targets
         return getattr(m2f_targets, name)
@@ -36,4 +39,4 @@ def __getattr__(name):
 
 
 __all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention",
-           "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER]
+           "conv2d_dgrad_s2", "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER]

@@ -29,6 +29,8 @@ bool mss_conv_bf16x3_eligible(const MssConvArgs& p);
 int mss_conv_bf16x3_launch(MssConvArgs p, void* stream);
 bool mss_stem7_eligible(const MssConvArgs& p);            // stem7.hip: the 7x7 / stride-2 / 4 -> 64 stem of the ResNet-50 backbone
 int mss_stem7_launch(MssConvArgs p, void* stream);
+bool mss_conv_dgrad_s2_wanted(const MssConvArgs& p);      // conv_dgrad_s2.hip: args->stride == -2, the data gradient of a stride-2 convolution
+int mss_conv_dgrad_s2_launch(MssConvArgs p, void* stream);
 
 namespace {
 
@@ -372,6 +374,7 @@ extern "C" {
 int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
   MssConvArgs p = *args;
   if (!p.x || !p.w || !p.y) return MSS_ERR_BAD_ARG;
+  if (mss_conv_dgrad_s2_wanted(p)) return mss_conv_dgrad_s2_launch(p, stream);    // stride == -2 (route 6): checks its own shapes, ignores w_split
   if (mss_stem7_eligible(p)) return mss_stem7_launch(p, stream);    // the one shape with C == 4 and 49 taps (route 5)
   if (p.C % 16 || p.ldx % 4 || p.R * p.S > 9 || p.R * p.S < 1) return MSS_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w)) & 15) return MSS_ERR_BAD_ARG;
@@ -403,9 +406,11 @@ int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
 }
 
 // Which kernel mss_conv2d_forward_f32 runs for these arguments: 1 = gemm_nt_kernel (gemm.hip), 0 = conv_igemm_kernel, 2 = gemm_few_rows_kernel,
-// 3 = gemm_nt_bf16x3_kernel, 4 = its implicit-GEMM / per-sample-affine instantiations (args->w_split set), 5 = stem7_conv_kernel (stem7.hip).
+// 3 = gemm_nt_bf16x3_kernel, 4 = its implicit-GEMM / per-sample-affine instantiations (args->w_split set), 5 = stem7_conv_kernel (stem7.hip),
+// 6 = conv_dgrad_s2_kernel (conv_dgrad_s2.hip; args->stride == -2, on either route).
 int mss_conv2d_forward_route(const MssConvArgs* args) {
   MssConvArgs p = *args;
+  if (mss_conv_dgrad_s2_wanted(p)) return 6;
   if (mss_stem7_eligible(p)) return 5;
   p.M = p.N * p.OH * p.OW;
   if (p.k_steps) return 1;

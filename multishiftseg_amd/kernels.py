@@ -182,6 +182,18 @@ def ones(n, device):
     return t
 
 
+_ZEROS = {}
+
+
+def zeros(n, device):
+    """The shared all-zeros counterpart of ones() (the zero shift of a scale-only prologue): a constant, never written."""
+    key = (int(n), str(device))
+    t = _ZEROS.get(key)
+    if t is None:
+        t = _ZEROS[key] = torch.zeros(int(n), device=device, dtype=torch.float32)
+    return t
+
+
 def packed(param, flip=False):
     """Cached pack_weight of an nn.Parameter."""
     return _cached_pack(param, ("direct", flip), lambda: pack_weight(param, flip))
@@ -247,7 +259,7 @@ def _fwd_kind(a):
     """Profiling label of a forward launch: which of the two MFMA kernels the C side picks."""
     if _profile is None:
         return "conv_igemm"
-    return ("conv_igemm", "gemm_nt", "gemm_few_rows", "gemm_nt_bf16x3", "conv_igemm_bf16x3", "conv_stem7")[_lib.value("mss_conv2d_forward_route", ctypes.byref(a))]
+    return ("conv_igemm", "gemm_nt", "gemm_few_rows", "gemm_nt_bf16x3", "conv_igemm_bf16x3", "conv_stem7", "conv_dgrad_s2")[_lib.value("mss_conv2d_forward_route", ctypes.byref(a))]
 
 
 def _wgrad_kind(a, lddy):
@@ -261,10 +273,10 @@ def conv_out_size(h, r, stride, dil, pad):
     return (h + 2 * pad - dil * (r - 1) - 1) // stride + 1
 
 
-def _conv_args(x, pw, y, stride, dil, pad, in_affine, in_relu, out_affine, out_relu, res, res_mask=False):
+def _conv_args(x, pw, y, stride, dil, pad, in_affine, in_relu, out_affine, out_relu, res, res_mask=False, split=True):
     a = MssConvArgs()
     a.x, a.w, a.y = x.ptr, ptr(pw.t), (y.ptr if y is not None else None)
-    a.w_split = w_split_of(pw)
+    a.w_split = w_split_of(pw) if split else None
     if in_affine is not None:
         sc, sh = in_affine
         a.in_scale, a.in_shift = ptr(sc), ptr(sh)
@@ -319,6 +331,31 @@ def _conv_launch(x, pw, out, OH, OW, stride, dil, pad, in_affine, in_relu, out_a
     with _Timed(_fwd_kind(a), 2.0 * x.N * OH * OW * pw.K * pw.C * pw.R * pw.S,
                 (x.N, x.H, x.W, pw.C, pw.K, pw.R, stride, dil)):
         call("mss_conv2d_forward_f32", ctypes.byref(a))
+
+
+def conv2d_dgrad_s2(dz, pw_flipped, out_hw, in_affine=None, res=None, res_mask=False, out=None):
+    """dx = epilogue(data gradient of a stride-2 convolution (3x3 / padding 1 or 1x1 / padding 0) at prologue(dz)): the gather-form
+    kernel of csrc/conv_dgrad_s2.hip (MssConvArgs.stride == -2). dz: Act on the strided convolution's output grid with its output
+    channels; pw_flipped: pack_weight(w, flip=True) / packed(w, flip=True); out_hw: (OH, OW) of dx -- the caller's, because the
+    forward's floor loses a row or column. in_affine (one per-channel affine, in-grid rows only), res / res_mask and out as conv2d's.
+    Native fp32 MFMA on either gemm route; every element of dx's channels is written."""
+    pw = pw_flipped
+    assert dz.C == pw.Cp or (dz.C >= pw.C and dz.C <= pw.Cp and dz.c0 + pw.Cp <= dz.ld), (dz.C, pw.C, pw.Cp)
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    k_total = pw.K + (pw.tail.K if pw.tail is not None else 0)
+    if out is None:
+        out = Act.empty(dz.N, OH, OW, k_total, dz.buf.device, ld=_round_up(k_total, 4))
+    assert (out.N, out.H, out.W) == (dz.N, OH, OW) and out.C >= k_total
+    parts = [(pw, 0)] if pw.tail is None else [(pw.tail, pw.K), (pw, 0)]
+    for part, lo in parts:
+        sub_out = out if pw.tail is None else out.slice(lo, part.K)
+        sub_res = res if (res is None or pw.tail is None) else res.slice(lo, part.K)
+        a = _conv_args(dz, part, sub_out, -2, 1, (part.R - 1) // 2, in_affine, False, None, False, sub_res, res_mask, split=False)
+        a.OH, a.OW, a.ldy = OH, OW, sub_out.ld
+        sub_out.stats = None
+        with _Timed(_fwd_kind(a), 2.0 * dz.M * part.K * part.C * part.R * part.S, (dz.N, OH, OW, part.C, part.K, part.R, -2, 1)):
+            call("mss_conv2d_forward_f32", ctypes.byref(a))
+    return out
 
 
 def dropout_compact_wanted(x, pw, in_affine, res=None):

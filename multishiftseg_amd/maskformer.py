@@ -1,4 +1,5 @@
-"""The evaluation shell of Mask2Former: image batch -> anomaly score, and the validation / test sweep around it.
+"""The shell of Mask2Former: image batch -> anomaly score with the validation / test sweep around it, and, after set_trainable(),
+image batch -> the predictor's training outputs for a whole-model stage-2 step.
 
 Host-side mirror of the inference branch of ``MaskFormer.forward`` (lib/network/mask2former/maskformer_model.py:229-234,
 260-277) together with the score the trainer forms from its output (train_m2f.py:387-407). The children keep the reference's
@@ -8,6 +9,10 @@ m2f_trainer.build_m2f_param_groups finds "backbone" in the module names.
 The shell adds no arithmetic of its own: it zero-pads the batch bottom/right to the size divisibility (ImageList.from_tensors;
 there is no pixel normalisation, the reference fork has none either), runs backbone -> pixel_decoder.forward_features -> predictor
 with ``fuse_score`` and hands back what kernels.m2f_score_fused returns, already cropped to the images' own size.
+Training (maskformer_model.py:235-258 without the criterion, which m2f_trainer.M2FTrainStep applies): ``set_trainable()`` switches
+the backbone (ResNet.set_trainable) and the predictor; with it on and grad mode enabled forward() runs pad -> backbone ->
+pixel_decoder.forward_features -> predictor on their autograd nodes, without ``fuse_score``, and returns the predictor's training
+outputs dict for the padded batch. Off, or under torch.no_grad(), the shell is the evaluation shell.
 Not built: the per-class ``sem_seg`` map of semantic_inference (the reference's evaluation reads only its shape).
 """
 import torch
@@ -40,6 +45,16 @@ class MaskFormer(nn.Module):
         if size_divisibility < 0:
             size_divisibility = getattr(backbone, "size_divisibility", 32)             # maskformer_model.py:77-79
         self.size_divisibility = size_divisibility
+        self._trainable = False
+
+    def set_trainable(self, flag=True):
+        """Opt in to (or out of) the differentiable path of the backbone and the predictor (the pixel decoder has no switch: it follows
+        its parameters' requires_grad). With it on and grad mode enabled forward() returns the predictor's training outputs for the
+        padded batch, so M2FTrainStep(head=model, ...) runs a whole-model step; off, or under torch.no_grad(), nothing changes."""
+        self._trainable = bool(flag)
+        self.backbone.set_trainable(flag)
+        self.sem_seg_head.predictor.set_trainable(flag)
+        return self
 
     def pad(self, images):
         """[B, 3, H, W] -> [B, 3, Hp, Wp], zeros at the bottom and the right; the batch itself where nothing is to pad."""
@@ -52,10 +67,15 @@ class MaskFormer(nn.Module):
         return out
 
     def forward(self, images):
-        """The predictor's dict for the padded batch, with "ood_score" [B, H, W] at the images' own size."""
+        """The predictor's dict for the padded batch, with "ood_score" [B, H, W] at the images' own size -- or, after set_trainable()
+        and with grad mode enabled, its training outputs (no "ood_score": fuse_score is inference-only)."""
         if images.dim() != 4 or images.shape[1] != 3:
             raise ValueError(f"MaskFormer takes [B, 3, H, W] image batches, got {tuple(images.shape)}")
         H, W = images.shape[-2:]
+        if self._trainable and torch.is_grad_enabled():
+            features = self.backbone(self.pad(images.float()))
+            mask_features, _, multi_scale = self.sem_seg_head.pixel_decoder.forward_features(features)
+            return self.sem_seg_head.predictor(multi_scale, mask_features, None)
         with torch.no_grad():
             x = self.pad(images.float())
             features = self.backbone(x)

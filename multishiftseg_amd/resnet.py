@@ -18,7 +18,21 @@ What runs (all in libmss_hip.so, NHWC inside, NCHW at the boundary as MSDeformAt
   * stem: kernels.stem7_conv (csrc/stem7.hip) with the folded norm and the ReLU, then kernels.maxpool3s2;
   * per block three or four kernels.conv2d calls, the norm as ``out_affine``, the ReLU as ``out_relu``; conv3 takes ``res=`` the
     shortcut and the final ReLU. The 3x3 layers take the direct implicit-GEMM route.
-Not built: train-mode BatchNorm and the backward (stage 2 fine-tunes the backbone at 0.1 x lr).
+
+Training (stage 2 fine-tunes the whole model, the backbone at 0.1 x lr with its norms in eval mode): opt-in, as the GMA
+decoder's. ``ResNet.set_trainable()`` with grad mode enabled runs the SAME forward calls inside one autograd node (_BackboneFn: the
+image and the res2..res5 parameters that require a gradient in, the requested NCHW maps out -- bit-identical to the frozen path) and
+keeps ``a1``, ``a2`` and ``out`` of every block from the first trainable block on. Its backward walks the blocks in reverse:
+  * dz3 = g_out * [out > 0] (the eval-mode form of kernels.bn_relu_backward: unit scale, zero shift);
+  * per convolution G = kernels.conv2d_wgrad(input, dz); dW = s * G with s = gamma * rstd the folded norm scale,
+    dbeta = sum_pixels dz (kernels.colsum), dgamma = rstd * (<W, G> - running_mean * dbeta) -- the pre-norm output is linear in W, so
+    it is neither stored nor recomputed and nothing is divided by gamma (float64 on the device for the small reductions);
+  * data gradients: the forward kernels on flip-packed weights with s as the PROLOGUE scale (the flipped pack depends on the weight
+    alone), gated by the stored activation through ``res_mask`` (a2 after conv3, a1 after conv2), summed at the block input through
+    ``res=``; conv2 and shortcut of res3.0 / res4.0 / res5.0 run kernels.conv2d_dgrad_s2 (csrc/conv_dgrad_s2.hip);
+  * only what the ``requires_grad`` pattern asks for; nothing in front of the first trainable block.
+Not built: train-mode BatchNorm; a gradient for the image; a trainable stem (its weight gradient needs a 7x7 wgrad kernel and a
+max-pool backward). Without set_trainable() a backbone with trainable parameters raises under grad mode, as before.
 """
 import torch
 from torch import nn
@@ -69,6 +83,119 @@ class BottleneckBlock(nn.Module):
         y = K.conv2d(y, K.packed(self.conv2.weight), stride=s, pad=1, out_affine=_folded(self.conv2), out_relu=True)
         return K.conv2d(y, K.packed(self.conv3.weight), out_affine=_folded(self.conv3), out_relu=True, res=sc)
 
+    def forward_act_saving(self, x, tape):
+        """forward_act through the same calls; (block, x, a1, a2, out) goes onto `tape` for backward_act."""
+        s = self.stride
+        sc = x if self.shortcut is None else K.conv2d(x, K.packed(self.shortcut.weight), stride=s, out_affine=_folded(self.shortcut))
+        a1 = K.conv2d(x, K.packed(self.conv1.weight), out_affine=_folded(self.conv1), out_relu=True)
+        a2 = K.conv2d(a1, K.packed(self.conv2.weight), stride=s, pad=1, out_affine=_folded(self.conv2), out_relu=True)
+        out = K.conv2d(a2, K.packed(self.conv3.weight), out_affine=_folded(self.conv3), out_relu=True, res=sc)
+        tape.append((self, x, a1, a2, out))
+        return out
+
+    def backward_act(self, g, x, a1, a2, out, need_dx, grads):
+        """g: gradient at the block's output (Act). Fills `grads` (parameter -> gradient) for this block's parameters that require
+        one and returns the gradient at the block's input (Act), or None without need_dx. Formulas: the module docstring."""
+        s = self.stride
+        dz3 = _relu_gate(g, out)
+        _param_grads(self.conv3, a2, dz3, 1, 0, grads)
+        if self.shortcut is not None:
+            _param_grads(self.shortcut, x, dz3, s, 0, grads)
+        below = need_dx or _wants(self.conv1)
+        if not (below or _wants(self.conv2)):
+            return None
+        dz2 = _dgrad(self.conv3, dz3, 1, None, res=a2, res_mask=True)
+        _param_grads(self.conv2, a1, dz2, s, 1, grads)
+        if not below:
+            return None
+        dz1 = _dgrad(self.conv2, dz2, s, (a1.H, a1.W), res=a1, res_mask=True)
+        _param_grads(self.conv1, x, dz1, 1, 0, grads)
+        if not need_dx:
+            return None
+        through = dz3 if self.shortcut is None else _dgrad(self.shortcut, dz3, s, (x.H, x.W))
+        return _dgrad(self.conv1, dz1, 1, None, res=through)
+
+
+def _wants(conv):
+    return conv.weight.requires_grad or conv.norm.weight.requires_grad or conv.norm.bias.requires_grad
+
+
+def _relu_gate(g, out):
+    """g * [out > 0]: the backward of the block's last ReLU from its stored OUTPUT -- kernels.bn_relu_backward in eval mode with unit
+    scale and zero shift."""
+    st = K.BNState()
+    dev = out.buf.device
+    st.scale, st.shift, st.train = K.ones(out.C, dev), K.zeros(out.C, dev), False
+    st.save_mean = st.save_invstd = None
+    return K.bn_relu_backward(g, out, st)[0]
+
+
+def _dgrad(conv, dz, stride, out_hw, res=None, res_mask=False):
+    """Data gradient of norm(conv(.)) at dz: the forward kernel (stride 1) or kernels.conv2d_dgrad_s2 (stride 2) on the flip-packed
+    weight, the folded norm scale as the prologue scale of dz; `res` added, or gating with res_mask."""
+    pw = K.packed(conv.weight, flip=True)
+    aff = (_folded(conv)[0], K.zeros(conv.weight.shape[0], conv.weight.device))
+    if stride == 2:
+        return K.conv2d_dgrad_s2(dz, pw, out_hw, in_affine=aff, res=res, res_mask=res_mask)
+    return K.conv2d(dz, pw, pad=conv.weight.shape[2] // 2, in_affine=aff, res=res, res_mask=res_mask)
+
+
+def _param_grads(conv, x, dz, stride, pad, grads):
+    """dW = s * G, dbeta = sum dz, dgamma = rstd * (<W, G> - running_mean * dbeta) of y = norm(conv(x)), G = wgrad(x, dz); each only
+    where the parameter requires a gradient. The per-channel reductions and the subtraction run in float64 on the device."""
+    bn = conv.norm
+    need_w, need_g, need_b = conv.weight.requires_grad, bn.weight.requires_grad, bn.bias.requires_grad
+    if not (need_w or need_g or need_b):
+        return
+    if need_w or need_g:
+        k, c, r, _ = conv.weight.shape
+        G = K.conv2d_wgrad(x, dz, k, c, r, r, stride=stride, pad=pad)
+    if need_w:
+        grads[conv.weight] = G * _folded(conv)[0].view(-1, 1, 1, 1)
+    if need_g or need_b:
+        dbeta = K.colsum(dz).double().sum(0)
+    if need_b:
+        grads[bn.bias] = dbeta.float()
+    if need_g:
+        rstd = (bn.running_var.double() + bn.eps).rsqrt()
+        wg = (conv.weight.detach().double() * G.double()).sum((1, 2, 3))
+        grads[bn.weight] = (rstd * (wg - bn.running_mean.double() * dbeta)).float()
+
+
+class _BackboneFn(torch.autograd.Function):
+    """image, the res2..res5 parameters that require a gradient -> the requested NCHW maps. The Acts between the blocks never become
+    tensors; the tape holds (block, x, a1, a2, out) from the first trainable block on."""
+
+    @staticmethod
+    def forward(ctx, model, x, *params):
+        tape = []
+        out = model._run(x, tape, params)
+        ctx.model, ctx.tape, ctx.params = model, tape, params
+        ctx.ends = [id(getattr(model, n)[-1]) for n in out]          # the block whose `out` each returned map is
+        return tuple(out.values())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gouts):
+        tape, grads = ctx.tape, {}
+        entering = {end: g for end, g in zip(ctx.ends, gouts) if g is not None}
+        g = None
+        for i in range(len(tape) - 1, -1, -1):
+            blk, x, a1, a2, out = tape[i]
+            tape[i] = None                                           # the stored activations go as the walk passes them
+            gin = entering.get(id(blk))
+            if gin is not None:                                      # a returned map: its gradient joins the next stage's data gradient
+                if g is None:
+                    g = K.Act.empty(out.N, out.H, out.W, out.C, out.buf.device)
+                    K.nchw_into_rows(gin, g.ptr, g.ld, g.H * g.W * g.ld)
+                else:
+                    K.nchw_into_rows(gin, g.ptr, g.ld, g.H * g.W * g.ld, accumulate=True)
+            if g is None:
+                continue
+            g = blk.backward_act(g, x, a1, a2, out, i > 0, grads)
+        ctx.tape = None
+        return (None, None) + tuple(grads.get(p) for p in ctx.params)
+
 
 def _load_without_counters(module, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
     """A FrozenBatchNorm2d checkpoint has no num_batches_tracked: keep the module's own counter instead of reporting it missing."""
@@ -98,38 +225,93 @@ class ResNet(nn.Module):
         if bad:
             raise NotImplementedError(f"ResNet (multishiftseg_amd): out_features among {self.stage_names}, got {bad}")
         self._out_features = list(out_features)
+        self._trainable = False
         self.register_load_state_dict_pre_hook(_load_without_counters)
+
+    def set_trainable(self, flag=True):
+        """Opt in to (or out of) the differentiable path: with the switch on, in eval mode and with grad mode enabled, forward() runs
+        as one autograd node over the same kernels and the res2..res5 parameters that require a gradient receive one. Off (the
+        default) the backbone is forward-only, as before; under torch.no_grad() the switch makes no difference."""
+        self._trainable = bool(flag)
+        return self
+
+    def freeze(self, freeze_at=0, norms=False):
+        """detectron2's ResNet.freeze: the stem for freeze_at >= 1, then res2 ... by index (freeze_at >= 2 freezes res2, ...):
+        requires_grad=False on the convolution weights AND the norm parameters of the frozen parts. norms=True also freezes the
+        norm parameters of every other part. Returns self.
+
+        The reference config (anomaly_ft.yaml: FREEZE_AT 5, NORM "BN") turns every backbone norm into a FrozenBatchNorm2d, whose
+        affine is a buffer, and stage 2's trainable_params_name_update ["."] then re-enables the convolution weights only. The
+        faithful stage-2 set-up here is therefore ``freeze(1, norms=True)``: all norm parameters frozen, stem.conv1.weight frozen
+        (the one deviation: a trainable stem is not built), the res2..res5 convolution weights trainable. Norm-parameter gradients
+        are built all the same, for users who keep the norms' affines as parameters."""
+        for idx, part in enumerate([self.stem] + [getattr(self, n) for n in self.stage_names], start=1):
+            if freeze_at >= idx:
+                for p in part.parameters():
+                    p.requires_grad_(False)
+        if norms:
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    for p in m.parameters():
+                        p.requires_grad_(False)
+        return self
 
     def output_shape(self):
         return {n: ShapeSpec(channels=self._out_feature_channels[n], stride=self._out_feature_strides[n]) for n in self._out_features}
 
     def _check_mode(self, x):
+        """Raises what is not built; returns the parameters the differentiable path returns gradients for (empty: frozen path)."""
         if self.training:
             raise NotImplementedError("ResNet (multishiftseg_amd): train-mode BatchNorm is not built (the reference keeps the backbone "
                                       "in eval mode, train_m2f.py:409-412); call .eval()")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            return ()
+        if not self._trainable:
             raise NotImplementedError("ResNet (multishiftseg_amd): no backward (forward only); freeze the backbone's parameters or call "
                                       "under torch.no_grad()")
+        if x.requires_grad:
+            raise NotImplementedError("ResNet (multishiftseg_amd): no gradient for the image is built (the data gradient stops at the "
+                                      "first trainable block); detach the image")
+        stem = [n for n, p in self.stem.named_parameters() if p.requires_grad]
+        if stem:
+            raise NotImplementedError(f"ResNet (multishiftseg_amd): a trainable stem is not built (stem.{stem[0]} requires a gradient: "
+                                      "its weight gradient needs a 7x7 wgrad kernel and a max-pool backward); freeze(1) freezes it")
+        return tuple(p for name in self._run_stages() for p in getattr(self, name).parameters() if p.requires_grad)
+
+    def _run_stages(self):
+        """The stages forward() runs: up to the last requested one."""
+        last = max(self.stage_names.index(f) for f in self._out_features)
+        return self.stage_names[:last + 1]
+
+    def _run(self, x, tape=None, params=()):
+        """stem -> stages -> {name: NCHW map}. tape (a list): from the first block that owns one of `params` on, every block leaves
+        (block, x, a1, a2, out) there -- the same kernel calls either way."""
+        conv1 = self.stem.conv1
+        y = K.maxpool3s2(K.stem7_conv(x.float(), conv1.weight, _folded(conv1), relu=True))
+        wanted = {id(p) for p in params}
+        out = {}
+        for name in self._run_stages():
+            for blk in getattr(self, name):
+                if tape is not None and (tape or any(id(p) in wanted for p in blk.parameters())):
+                    y = blk.forward_act_saving(y, tape)
+                else:
+                    y = blk.forward_act(y)
+            if name in self._out_features:
+                out[name] = K.nhwc_to_nchw(y)
+        return out
 
     # ---- reference API ----------------------------------------------------------------------------------------------------
     def forward(self, x):
-        self._check_mode(x)
+        params = self._check_mode(x)
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError(f"ResNet takes [N, 3, H, W] images, got {tuple(x.shape)}")
         if not x.is_cuda:
             raise RuntimeError("ResNet (multishiftseg_amd) runs on an MI355X only; there is no CPU path")
+        if params:
+            maps = _BackboneFn.apply(self, x, *params)
+            return dict(zip([n for n in self._run_stages() if n in self._out_features], maps))
         with torch.no_grad():
-            conv1 = self.stem.conv1
-            y = K.maxpool3s2(K.stem7_conv(x.float(), conv1.weight, _folded(conv1), relu=True))
-            out = {}
-            for name in self.stage_names:
-                for blk in getattr(self, name):
-                    y = blk.forward_act(y)
-                if name in self._out_features:
-                    out[name] = K.nhwc_to_nchw(y)
-                if len(out) == len(self._out_features):
-                    break
-            return out
+            return self._run(x)
 
 
 def build_resnet_backbone(depth=50, out_features=("res2", "res3", "res4", "res5"), stem_out_channels=64, res2_out_channels=256,

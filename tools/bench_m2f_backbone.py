@@ -4,6 +4,12 @@
             the whole wrapper (NCHW -> NHWC + convolution), against F.conv2d for the same layer and F.relu(F.batch_norm(F.conv2d)).
   backbone: ResNet.forward against the tests/ref_resnet.py restatement in float32 with stock torch.
 
+  --backward: forward + backward of the trainable backbone (ResNet.set_trainable(), the faithful stage-2 freezing pattern
+            freeze(1, norms=True): the 52 res2..res5 convolution weights) against stock-torch float32 autograd of the same
+            restatement on the same device, at 8 x 3 x 384 x 768 (the reference's 380 x 760 crop padded to 32, batch 8) and
+            2 x 3 x 1024 x 2048; and, separately, the six stride-2 data gradients (conv2 and shortcut of res3.0 / res4.0 / res5.0) on
+            kernels.conv2d_dgrad_s2 against the zero-insertion form through the stride-1 kernel (with and without its insertion pass).
+
 Each pair alternates inside one process: per round every contender runs `iters` times between two device events; the figure is the
 median over the rounds, with min and max beside it. Every shape is warmed first. The outputs of both sides are compared at the timed
 size. Reported, not gated: python tools/bench_m2f_backbone.py --out profiles/m2f_backbone/bench.json"""
@@ -21,6 +27,7 @@ import torch                                    # noqa: E402
 import torch.nn.functional as F                 # noqa: E402
 
 SIZES = [(2, 1024, 2048), (16, 704, 704)]
+BACKWARD_SIZES = [(8, 384, 768), (2, 1024, 2048)]
 
 
 def timed(fns, rounds, iters, warm):
@@ -42,14 +49,91 @@ def timed(fns, rounds, iters, warm):
     return {k: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v)) for k, v in ms.items()}
 
 
+def backward_bench(args):
+    import ref_resnet as R
+    from multishiftseg_amd import build_resnet_backbone, kernels as K
+    sizes = BACKWARD_SIZES if args.sizes is None else [tuple(int(v) for v in s.split("x")) for s in args.sizes.split(",")]
+    model = R.randomize_(build_resnet_backbone(), 7).eval().cuda().set_trainable().freeze(1, norms=True)
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    params = [p for _, p in named]
+    sd = R.cast(model.state_dict(), torch.float32)
+    leaves = [sd[n].requires_grad_(True) for n, _ in named]                 # the same 52 tensors, stock torch's own copies
+    names = ("res2", "res3", "res4", "res5")
+    result = dict(device=torch.cuda.get_device_name(0), rounds=args.rounds, pattern="freeze(1, norms=True): 52 convolution weights", shapes=[])
+    for n, h, w in sizes:
+        img = torch.randn((n, 3, h, w), device="cuda")
+        with torch.no_grad():
+            gm = [torch.randn_like(t) for t in model(img).values()]
+
+        def hip_step():
+            return torch.autograd.grad(list(model(img).values()), params, gm)
+
+        def torch_step():
+            out = R.resnet50(img, sd)
+            return torch.autograd.grad([out[k] for k in names], leaves, gm)
+
+        def hip_forward():
+            with torch.no_grad():
+                return model(img)
+        step = timed({"resnet50_hip_fwd_bwd": hip_step, "resnet50_torch_f32_fwd_bwd": torch_step, "resnet50_hip_fwd": hip_forward},
+                     args.rounds, iters=3, warm=2)
+        ours, ref = hip_step(), torch_step()
+        diffs = [float((a - b).abs().max() / b.abs().max()) for a, b in zip(ours, ref)]
+        del ours, ref
+        # the six strided data gradients alone: the parity-class kernel against zero insertion + the stride-1 kernel
+        strided = []
+        for stage in ("res3", "res4", "res5"):
+            blk = getattr(model, stage)[0]
+            div = model._out_feature_strides[stage] // 2                       # the block's input stride
+            ih, iw = h // div, w // div
+            for conv in (blk.conv2, blk.shortcut):
+                cz, cx, r, _ = conv.weight.shape
+                pw = K.packed(conv.weight, flip=True)
+                dz = K.Act(torch.randn((n, ih // 2, iw // 2, cz), device="cuda"))
+                up = K.Act.zeros(n, ih, iw, cz, "cuda")
+
+                def insert():
+                    up.buf.zero_()
+                    up.buf[:, ::2, ::2, :] = dz.buf
+                t = timed({"dgrad_s2": lambda: K.conv2d_dgrad_s2(dz, pw, (ih, iw)),
+                           "zero_insertion_product": lambda: K.conv2d(up, pw, pad=r // 2),
+                           "zero_insertion_with_pass": lambda: (insert(), K.conv2d(up, pw, pad=r // 2))}, args.rounds, iters=10, warm=3)
+                insert()
+                diff = float((K.conv2d_dgrad_s2(dz, pw, (ih, iw)).buf - K.conv2d(up, pw, pad=r // 2).buf).abs().max())
+                flop = 2.0 * n * (ih // 2) * (iw // 2) * cz * cx * r * r
+                strided.append(dict(layer=f"{stage}.0.{'conv2' if r == 3 else 'shortcut'}", dz=[n, ih // 2, iw // 2, cz], dx=[n, ih, iw, cx],
+                                    kernel=r, TFLOP=flop / 1e12, times=t, useful_TFLOP_per_s=flop / t["dgrad_s2"]["median_ms"] / 1e9,
+                                    max_abs_diff_vs_zero_insertion=diff))
+                del dz, up
+        entry = dict(shape=[n, 3, h, w], step=step,
+                     hip_over_torch=step["resnet50_hip_fwd_bwd"]["median_ms"] / step["resnet50_torch_f32_fwd_bwd"]["median_ms"],
+                     hip_fwd_bwd_over_hip_fwd=step["resnet50_hip_fwd_bwd"]["median_ms"] / step["resnet50_hip_fwd"]["median_ms"],
+                     weight_grad_rel_max_diff_vs_torch_f32=dict(max=max(diffs), median=statistics.median(diffs)),
+                     strided_dgrads=strided,
+                     strided_dgrads_ms=dict(dgrad_s2=sum(e["times"]["dgrad_s2"]["median_ms"] for e in strided),
+                                            zero_insertion_product=sum(e["times"]["zero_insertion_product"]["median_ms"] for e in strided),
+                                            zero_insertion_with_pass=sum(e["times"]["zero_insertion_with_pass"]["median_ms"] for e in strided)))
+        result["shapes"].append(entry)
+        print(json.dumps(entry), flush=True)
+        del img, gm
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--backward", action="store_true", help="time forward + backward and the strided data gradients instead")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--sizes", default=None, help="e.g. 1x64x96,2x70x100 (default: the two sizes the reference trains and tests at)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_m2f_backbone.py measures on the GPU only")
+    if args.backward:
+        return backward_bench(args)
     import ref_resnet as R
     from multishiftseg_amd import build_resnet_backbone, kernels as K
     from multishiftseg_amd.resnet import _folded
