@@ -367,6 +367,150 @@ __global__ void unpack_wgrad_kernel(const float* __restrict__ src, float* __rest
   }
 }
 
+// The same two movements by lines: one workgroup owns one k and WP_CH channels. Its part of [K][C][R][S] is ONE contiguous
+// run of channels * taps floats, its part of the tap-major side taps runs of `channels` floats; the run is transposed through LDS
+// (tile[tap][channel]), so every global access of a wave is contiguous -- except a gathered column, which stays a 4-byte access
+// (per-image compacted side: runs of `taps` floats). The flat loops above touched every 128-byte line of the [K][C][R][S] side in
+// R * S far-apart passes and divided 64-bit indices per element. They keep flip = 1, one tap (the two layouts differ by the padding only:
+// the flat loop is contiguous on both sides), rows of fewer than WP_MIN_C channels (the stem's 64 x 3 x 7 x 7: 16-byte runs on the
+// tap-major side) and more than WP_MAX_TAPS taps.
+constexpr int WP_CH = 128;
+constexpr int WP_MIN_C = 32;
+constexpr int WP_ILP = 4;                // elements a thread has in flight
+constexpr int WP_COL_IMGS = 2;           // images whose column index a gather-sum workgroup keeps in LDS (the train step has 2)
+constexpr int WP_MAX_TAPS = 121;          // 121 x (128 + 4) floats = 63 888 B of LDS
+
+// LDS row pitch: the [K][C][R][S]-side loop walks tile[t * pitch + c] tap-fastest; pitch = 4 (mod 32) keeps 3 x 3 taps x 4 channels
+// of a half-wave on 32 different banks but for 4, pitch = 1 (mod 32) does so for 32 taps and more of one channel
+__host__ __device__ static inline int wp_pitch(int taps) { return WP_CH + (taps > 16 ? 1 : 4); }
+static inline bool wp_by_lines(int channels, int taps) { return channels >= WP_MIN_C && taps >= 2 && taps <= WP_MAX_TAPS; }
+
+// element j = tid + 256 * i of a run of [channels][taps]: (c, t) of the first one by one 32-bit division per thread, the following by adding
+struct WpRunIndex {
+  int c, t, dc, dt, taps;
+  __device__ WpRunIndex(int tid, int taps_) : c(tid / taps_), t(tid % taps_), dc(256 / taps_), dt(256 % taps_), taps(taps_) {}
+  __device__ void next() {
+    c += dc; t += dt;
+    if (t >= taps) { t -= taps; ++c; }
+  }
+};
+
+// [K][C][T] -> [T][Kpad][Cp], zero padded; col: the gather-sum of pack_weights_kernel. grid = Kpad * ceil(Cp / WP_CH), 256 threads.
+__global__ __launch_bounds__(256) void pack_weights_lines_kernel(const float* __restrict__ src, float* __restrict__ dst, int K, int C, int T,
+                                                                  int Kpad, int Cp, const int* __restrict__ col, int n_img, int c0) {
+  extern __shared__ float wp_tile[];
+  const int chunks = (Cp + WP_CH - 1) / WP_CH, pitch = wp_pitch(T), tid = threadIdx.x;
+  const int k = blockIdx.x / chunks, cb = (blockIdx.x - k * chunks) * WP_CH;
+  const int nc_dst = Cp - cb < WP_CH ? Cp - cb : WP_CH;                       // columns of the destination rows
+  const int nc_src = k < K && C > cb ? (C - cb < WP_CH ? C - cb : WP_CH) : 0;  // of them: channels that exist
+  const int run = nc_src * T;
+  const float* base = src + ((size_t)(k < K ? k : 0) * C + cb) * T;
+  // gather-sum: the channel of image n's tensor that holds channel c (-1: none), looked up once per workgroup for the first images
+  __shared__ int wp_col[WP_COL_IMGS][WP_CH];
+  auto source_channel = [&](int n, int c) {
+    if (c < c0) return c;
+    const int cc = col[(size_t)n * (C - c0) + c - c0];
+    return cc >= 0 ? c0 + cc : -1;
+  };
+  if (col && run > 0) {
+    for (int i = tid; i < WP_COL_IMGS * WP_CH; i += 256) {
+      const int n = i / WP_CH, c = i - n * WP_CH;
+      wp_col[n][c] = n < n_img && c < nc_src ? source_channel(n, cb + c) : -1;
+    }
+    __syncthreads();
+  }
+  // WP_ILP elements per thread and pass: their loads are issued together, then their LDS stores (a workgroup moves only a few KB, so
+  // what it waits for is the latency of its loads, not their bytes)
+  WpRunIndex at(tid, T);
+  for (int j0 = tid; j0 < run; j0 += WP_ILP * 256) {
+    int cs[WP_ILP], ts[WP_ILP];
+    float v[WP_ILP];
+#pragma unroll
+    for (int u = 0; u < WP_ILP; ++u) { cs[u] = at.c; ts[u] = at.t; at.next(); }
+    if (!col) {
+#pragma unroll
+      for (int u = 0; u < WP_ILP; ++u) v[u] = j0 + u * 256 < run ? base[j0 + u * 256] : 0.f;
+    } else {
+      // two images' loads in flight, added in ascending n from 0.f as the flat loop adds them
+#pragma unroll
+      for (int u = 0; u < WP_ILP; ++u) v[u] = 0.f;
+      for (int n = 0; n < n_img; n += 2) {
+        float a[2][WP_ILP];
+        bool has[2][WP_ILP];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int u = 0; u < WP_ILP; ++u) {
+            int sc = -1;
+            if (n + m < n_img && j0 + u * 256 < run) sc = n + m < WP_COL_IMGS ? wp_col[n + m][cs[u]] : source_channel(n + m, cb + cs[u]);
+            has[m][u] = sc >= 0;
+            a[m][u] = sc >= 0 ? src[(((size_t)(n + m) * K + k) * C + sc) * T + ts[u]] : 0.f;
+          }
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int u = 0; u < WP_ILP; ++u)
+            if (has[m][u]) v[u] += a[m][u];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < WP_ILP; ++u)
+      if (j0 + u * 256 < run) wp_tile[ts[u] * pitch + cs[u]] = v[u];
+  }
+  __syncthreads();
+  const int c = tid & (WP_CH - 1);
+  if (c < nc_dst)
+    for (int t = tid / WP_CH; t < T; t += 256 / WP_CH)
+      dst[((size_t)t * Kpad + k) * Cp + cb + c] = c < nc_src ? wp_tile[t * pitch + c] : 0.f;
+}
+
+// [T][Kpad][Cp] -> [K][C][T] (n_img of them with `place`, as unpack_wgrad_kernel). grid = images * K * ceil(C / WP_CH), 256 threads.
+__global__ __launch_bounds__(256) void unpack_wgrad_lines_kernel(const float* __restrict__ src, float* __restrict__ dst, int K, int C, int T,
+                                                                  int Kpad, int Cp, int accumulate, const int* __restrict__ place,
+                                                                  const int* __restrict__ k_steps, int c0) {
+  extern __shared__ float wp_tile[];
+  const int chunks = (C + WP_CH - 1) / WP_CH, pitch = wp_pitch(T), tid = threadIdx.x;
+  const int nk = blockIdx.x / chunks, cb = (blockIdx.x - nk * chunks) * WP_CH;
+  const int n = nk / K, k = nk - n * K;
+  const int nc = C - cb < WP_CH ? C - cb : WP_CH;
+  const int c = tid & (WP_CH - 1);
+  if (c < nc) {
+    int sc = cb + c;                                       // source channel, -1: a zero column
+    if (place && sc >= c0) {
+      const int pc = sc - c0 < 16 * k_steps[n] ? place[(size_t)n * (C - c0) + sc - c0] : -1;
+      sc = pc >= 0 ? c0 + pc : -1;
+    }
+    constexpr int DT = 256 / WP_CH;
+    for (int t0 = tid / WP_CH; t0 < T; t0 += WP_ILP * DT) {
+      float v[WP_ILP];
+#pragma unroll
+      for (int u = 0; u < WP_ILP; ++u) v[u] = sc >= 0 && t0 + u * DT < T ? src[((size_t)(t0 + u * DT) * Kpad + k) * Cp + sc] : 0.f;
+#pragma unroll
+      for (int u = 0; u < WP_ILP; ++u)
+        if (t0 + u * DT < T) wp_tile[(t0 + u * DT) * pitch + c] = v[u];
+    }
+  }
+  __syncthreads();
+  float* base = dst + ((size_t)nk * C + cb) * T;
+  const int run = nc * T;
+  WpRunIndex at(tid, T);
+  for (int j0 = tid; j0 < run; j0 += WP_ILP * 256) {
+    float v[WP_ILP], before[WP_ILP];
+#pragma unroll
+    for (int u = 0; u < WP_ILP; ++u) {
+      v[u] = j0 + u * 256 < run ? wp_tile[at.t * pitch + at.c] : 0.f;
+      at.next();
+    }
+    if (accumulate) {
+#pragma unroll
+      for (int u = 0; u < WP_ILP; ++u) before[u] = j0 + u * 256 < run ? base[j0 + u * 256] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < WP_ILP; ++u)
+      if (j0 + u * 256 < run) base[j0 + u * 256] = accumulate ? before[u] + v[u] : v[u];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -428,6 +572,12 @@ int mss_conv2d_pack_weights_f32(const float* w, float* packed, int K, int C, int
                                 int flip, const int* col, int n_img, int c0, void* stream) {
   if (!w || !packed) return MSS_ERR_BAD_ARG;
   if (col && (flip || n_img < 1 || c0 < 0 || c0 >= C)) return MSS_ERR_BAD_ARG;
+  const long long wgs = (long long)Kpad * ((Cp + WP_CH - 1) / WP_CH);
+  if (!flip && wp_by_lines(Cp, R * S) && wgs >= 1 && wgs <= 0x7fffffffll) {
+    hipLaunchKernelGGL(pack_weights_lines_kernel, dim3((unsigned)wgs), dim3(256), (size_t)R * S * wp_pitch(R * S) * sizeof(float),
+                       static_cast<hipStream_t>(stream), w, packed, K, C, R * S, Kpad, Cp, col, n_img, c0);
+    return mss_launch_status();
+  }
   const size_t total = (size_t)R * S * Kpad * Cp;
   int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), w,
@@ -439,7 +589,13 @@ int mss_conv2d_unpack_wgrad_f32(const float* packed, float* grad, int K, int C, 
                                 int accumulate, const int* place, const int* k_steps, int n_img, int c0, void* stream) {
   if (!grad || !packed) return MSS_ERR_BAD_ARG;
   if (place && (accumulate || !k_steps || n_img < 1 || c0 < 0 || c0 >= C)) return MSS_ERR_BAD_ARG;
-  const size_t total = (size_t)K * C * R * S * (place ? n_img : 1);
+  const long long wgs = (long long)(place ? n_img : 1) * K * ((C + WP_CH - 1) / WP_CH);
+  if (wp_by_lines(C, R * S) && wgs >= 1 && wgs <= 0x7fffffffll) {
+    hipLaunchKernelGGL(unpack_wgrad_lines_kernel, dim3((unsigned)wgs), dim3(256), (size_t)R * S * wp_pitch(R * S) * sizeof(float),
+                       static_cast<hipStream_t>(stream), packed, grad, K, C, R * S, Kpad, Cp, accumulate, place, k_steps, c0);
+    return mss_launch_status();
+  }
+  const size_t total =(size_t)K * C * R * S * (place ? n_img : 1);
   int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), packed,
                      grad, K, C, R, S, Kpad, Cp, accumulate, place, k_steps, n_img, c0);

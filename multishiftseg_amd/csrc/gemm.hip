@@ -17,6 +17,7 @@
 // same L2.
 #include "mss_epilogue.h"
 #include "mss_gemm_tiles.h"
+#include "gemm_rounds.h"
 #include <stdlib.h>
 
 namespace {
@@ -324,17 +325,7 @@ int launch_gemm(const MssConvArgs& p, hipStream_t stream, long long first = 0, l
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_nt_kernel<AFFINE, VARIANT, BN, PERIMG>, NT, smem) != hipSuccess || n < 1) n = 3;
     per_cu_max = n;
   }
-  // Every workgroup walks ceil(total / grid) tiles: pick the residency (per_cu_max or one less) whose last round is
-  // fuller, e.g. 4608 tiles = 6 full rounds of 768 but 4.5 rounds of 1024.
-  int grid = 0;
-  double best = -1.0;
-  for (int per_cu = per_cu_max; per_cu >= (per_cu_max > 1 ? per_cu_max - 1 : 1); --per_cu) {
-    const long long slots = (long long)per_cu * cus;
-    const long long g = total < slots ? total : slots;
-    const long long rounds = (total + g - 1) / g;
-    const double eff = (double)total / (double)(rounds * g);
-    if (eff > best + 0.02) { best = eff; grid = (int)g; }     // (r06: re-measured, 36 x 4096 x 512 -> 512 at one per CU 133.5 vs 125 TFLOP/s forced to two; the split kernel differs)
-  }
+  const int grid = mss_gemm_grid(total, per_cu_max, cus);   // gemm_rounds.h: the residency whose last round is fuller
   // the square-ish tile order only for whole launches: the hybrid wide + narrow split (MSS_GEMM_TAIL) relies on tile ranges
   const int group_m = (first == 0 && end == (long long)tiles_per_batch * batch) ? MSS_ENV_INT("MSS_GEMM_GROUP_M", GEMM_GROUP_M_DEFAULT) : 0;
   hipLaunchKernelGGL((gemm_nt_kernel<AFFINE, VARIANT, BN, PERIMG>), dim3(grid), dim3(NT), smem, stream, p, first, end, tiles_per_batch, group_m);
@@ -458,41 +449,30 @@ int mss_gemm_nt_dispatch(MssConvArgs p, void* stream) {
   const bool v3 = MSS_ENV_INT("MSS_GEMM_VARIANT", 3) == 3 && p.C / BK >= 3 &&
                   (unsigned long long)((nb3 - 1) * p.x_bs + (long long)p.M * p.ldx) * 4ull < 0xffffffffull &&
                   (unsigned long long)((nb3 - 1) * p.w_bs + (long long)p.Kpad * p.C) * 4ull < 0xffffffffull;
-  // 256-wide tiles when the output channels split evenly, the reduction is long enough and there is work for two rounds of
-  // the 512 slots. Measured (tools/bench_bgemm.py, bench_1x1.py): 1x1 2048 -> 4096
+  // Tile width and rounds (gemm_rounds.h, mss_gemm_rounds). 256-wide tiles when the output channels split evenly, the reduction is
+  // long enough and there is work for two rounds of the 512 slots. Measured (tools/bench_bgemm.py, bench_1x1.py): 1x1 2048 -> 4096
   // 127 -> 133, ASPP 4096 -> 256 123 -> 131, 1024 -> 2048 136 -> 138, C = 304 122 -> 126 TFLOP/s; C = 256: 122 -> 121 (not taken).
-  const long long tiles256 = (long long)p.mtiles * (p.K / 256) * (p.batch > 1 ? p.batch : 1);
-  bool wide = p.K % 256 == 0 && tiles256 >= 1024 && p.C >= 256;
-  if (wide) {
-    // ... unless the last round of wide tiles is mostly idle while the narrow tiles fill theirs: 64 x 18 x 1 wide tiles (ASPP
-    // dilation 12 / 24 through F(6x6): 2304 tiles x 4096 -> 256) are 2.25 rounds of the 512 slots but exactly 3 rounds of the
-    // 768 narrow slots -- measured 119.5 (wide) against 133.4 TFLOP/s (narrow)
-    auto eff = [](long long total, long long slots) {
-      const long long rounds = (total + slots - 1) / slots;
-      return (double)total / (double)(rounds * slots);
-    };
-    const double ew = eff(tiles256, 512), en = eff(2 * tiles256, 768);
-    if (ew < 0.8 && en > ew + 0.15) wide = false;
-  }
-  if (wide) {
-    // Hybrid last round, OPT-IN (MSS_GEMM_TAIL=1): when the wide tiles leave a partial last round that is at most 3/4
-    // full, the whole rounds run on wide tiles and the remainder as twice as many narrow tiles in a second launch --
-    // narrow tile 2w + {0, 1} is wide tile w's left / right half in the same n-fastest order -- e.g. 64 x 15 x 2 = 1920
-    // wide tiles (mod4 through F(6x6)): 3 wide rounds + exactly one round of 768 narrow tiles instead of 3.75 -> 4.
-    // Bit-identical results. Measured: isolated 0.582 -> 0.558 ms (64 x 1892 x 512 -> 512) and 1.172 -> 1.129 ms (64 x 2112 x
-    // 512 -> 1024); in the step 67.3 -> 67.1 ms of gemm_nt (the narrow round is slower per FLOP and costs a second launch).
-    // Off by default: 0.2 ms per step does not pay for one GEMM call becoming two kernel launches in every profile.
-    // r03: a default rule for nearly-empty last rounds (rem <= 128; only one-image eval products qualify) measured +-0 on the eval
-    // forward (42.15 -> 42.15 ms): it stays opt-in. The two launches use the variant-3 kernels where the shape allows.
-    // r04 default rule (-1): single-position products with at most four whole rounds, where the idle part of the last round is a
-    // visible share of the launch -- the pixel decoder's Linears over 16 x 10 164 tokens are 1271 wide tiles = 2.48 rounds: decoder
-    // forward + backward 66.15 -> 65.78 ms with the hybrid, bit-identical; no product of the DeepLab step or of its eval forward
-    // qualifies (their tile counts are whole rounds), so the per-launch accounting of bench.py is unchanged. 0: never, 1: always.
-    const int tail_mode = MSS_ENV_INT("MSS_GEMM_TAIL", -1);
-    const long long full = (tiles256 / 512) * 512, rem = tiles256 - full;
+  //
+  // Hybrid last round (MSS_GEMM_TAIL: -1 default rules, 0 never, 1 wherever it fits): when the wide tiles leave a partial last round
+  // that is at most 3/4 full, the whole rounds run on wide tiles and the remainder as twice as many narrow tiles in a second launch
+  // -- narrow tile 2w + {0, 1} is wide tile w's left / right half in the same n-fastest order -- e.g. 64 x 15 x 2 = 1920
+  // wide tiles (mod4 through F(6x6)): 3 wide rounds + exactly one round of 768 narrow tiles instead of 3.75 -> 4.
+  // Bit-identical results. Measured: isolated 0.582 -> 0.558 ms (64 x 1892 x 512 -> 512) and 1.172 -> 1.129 ms (64 x 2112 x
+  // 512 -> 1024); in the step 67.3 -> 67.1 ms of gemm_nt (the narrow round is slower per FLOP and costs a second launch): for
+  // batched products it stays opt-in (MSS_GEMM_TAIL=1), 0.2 ms per step does not pay for one GEMM call becoming two kernel launches.
+  // r03: a default rule for nearly-empty last rounds (rem <= 128; only one-image eval products qualify) measured +-0 on the eval
+  // forward (42.15 -> 42.15 ms). The two launches use the variant-3 kernels where the shape allows.
+  // r04 default rule: single-position products with at most four whole rounds, where the idle part of the last round is a
+  // visible share of the launch -- the pixel decoder's Linears over 16 x 10 164 tokens are 1271 wide tiles = 2.48 rounds: decoder
+  // forward + backward 66.15 -> 65.78 ms with the hybrid, bit-identical.
+  // Default rule for single-position products between one and two wide rounds: one wide round, then at most one narrow
+  // round, where all-narrow tiles (MSS_GEMM_TAIL=0 keeps them) walk uneven chains -- the composed ASPP head's compose and project
+  // products, 7168 x 4096 -> 4096 = 896 wide tiles = 512 + 384. Still one C call and one trace row.
+  const MssGemmRounds rounds = mss_gemm_rounds(p.mtiles, p.K, p.C, p.batch, MSS_ENV_INT("MSS_GEMM_TAIL", -1));
+  if (rounds.mode != MSS_GEMM_NARROW) {
     const int nw = p.K / 256;
-    const long long rem_max = tail_mode == 1 ? 384 : (tail_mode == -1 && p.batch <= 1 && full <= 4 * 512) ? 384 : 0;
-    if (full > 0 && rem > 0 && rem <= rem_max) {
+    if (rounds.mode == MSS_GEMM_HYBRID) {
+      const long long full = rounds.full, tiles256 = rounds.full + rounds.rem;
       MssConvArgs q = p;
       q.ntiles = nw;
       int rc = v3 ? (p.in_scale ? launch_gemm<true, 3, 256>(q, s, 0, full) : launch_gemm<false, 3, 256>(q, s, 0, full))

@@ -99,6 +99,32 @@ class _ASPP(nn.Module):
                                       nn.ReLU(inplace=True))
 
 
+class _ComposedWeight:
+    """One composed ASPP weight W_d o M as the compose GEMM left it: `rows`, its tap-major rows [R*S][kp][ld] (a view of the one result
+    buffer), and the dense [K][C][R][S] tensor, which is unpacked when a consumer first asks for it -- eval, the dense route and
+    GraphedEval do; the dropped-channel route reads the rows alone (kernels.aspp_dropped_weights) and never pays for that pass."""
+    __slots__ = ("shape", "rows", "ld", "kp", "_dense")
+
+    def __init__(self, shape, rows, ld, kp):
+        self.shape, self.rows, self.ld, self.kp, self._dense = torch.Size(shape), rows, ld, kp, None
+
+    def dense(self):
+        if self._dense is None:
+            k, c, r, s_ = self.shape
+            g = torch.empty(tuple(self.shape), device=self.rows.device, dtype=torch.float32)
+            K.call("mss_conv2d_unpack_wgrad_f32", K.ptr(self.rows), K.ptr(g), k, c, r, s_, self.kp, self.ld, 0, None, None, 0, 0)
+            self._dense = g
+        return self._dense
+
+    def made(self):
+        """The dense tensor if a consumer has asked for it, else None (what GraphedEval keeps alive)."""
+        return self._dense
+
+
+def _dense(w):
+    return w.dense() if isinstance(w, _ComposedWeight) else w
+
+
 class _HeadFn(torch.autograd.Function):
     """Decoder + heads (deepv3.py:270-283) as one differentiable node."""
 
@@ -283,12 +309,12 @@ class DeepWV3Plus(nn.Module):
             return False
         return K.aspp_tiles(a.H, a.W, c_out, _ASPP_RATES, [feats[i][0].weight for i in (1, 2, 3)]) is not None
 
-    def _aspp_rows(self, tensors, pw, dropped=None, keep_rows=None):
-        """The four ASPP-shaped tensors [K][C][R][S] packed tap-major ([R*S][Kpad][C] each, 7168 rows of C in all), one 1x1 product
-        of the rows with `pw`, and the result unpacked into four tensors of the same shapes. A five-dimensional tensor is a weight
-        gradient of the dropped-channel products ([N][K][C][3][3] in per-image compacted columns, kernels.conv3x3_wgrad_dropped): its
-        pack gathers the columns back to their channels and adds the images (`dropped`: that step's kernels.AsppDropped).
-        keep_rows (a list): also receives (rows of the product, row pitch, Kpad) per tensor, views of the one result buffer."""
+    def _aspp_rows(self, tensors, pw, dropped=None):
+        """The four ASPP-shaped tensors [K][C][R][S] packed tap-major ([R*S][Kpad][C] each, 7168 rows of C in all) and one 1x1 product
+        of the rows with `pw`: one _ComposedWeight per tensor, whose rows are views of the one result buffer and whose dense() is the
+        result in the tensor's own layout. A five-dimensional tensor is a weight gradient of the dropped-channel products
+        ([N][K][C][3][3] in per-image compacted columns, kernels.conv3x3_wgrad_dropped): its pack gathers the columns back to their
+        channels and adds the images (`dropped`: that step's kernels.AsppDropped)."""
         dev = tensors[0].device
         C = tensors[0].shape[-3]
         geo = [(t.shape[-4], t.shape[-2], t.shape[-1], K._lib.value("mss_conv2d_kpad", t.shape[-4])) for t in tensors]
@@ -305,17 +331,14 @@ class DeepWV3Plus(nn.Module):
             r0 += n
         dst = K.conv2d(src, pw)
         out, r0 = [], 0
-        for t, (k, r, s_, kp), n in zip(tensors, geo, rows):
-            g = torch.empty((k, pw.K, r, s_), device=dev, dtype=torch.float32)
-            K.call("mss_conv2d_unpack_wgrad_f32", K.ptr(dst.buf[0, 0, r0:r0 + n]), K.ptr(g), k, pw.K, r, s_, kp, dst.ld, 0, None, None, 0, 0)
-            out.append(g)
-            if keep_rows is not None:
-                keep_rows.append((dst.buf[0, 0, r0:r0 + n], dst.ld, kp))
+        for (k, r, s_, kp), n in zip(geo, rows):
+            out.append(_ComposedWeight((k, pw.K, r, s_), dst.buf[0, 0, r0:r0 + n], dst.ld, kp))
             r0 += n
         return out
 
     def _aspp_composed(self, blk):
-        """The composed ASPP weights W_d o M ([256, 4096, 1, 1] as its two K-halves, three [256, 4096, 3, 3]) and the packed M / M^T.
+        """The composed ASPP weights W_d o M ([256, 4096, 1, 1] as its two K-halves, three [256, 4096, 3, 3] as _ComposedWeight: rows now,
+        the dense tensor on first use) and the packed M / M^T.
         M is packed once (the trunk is frozen); the composition is redone when an ASPP weight or a trunk factor has changed
         ((version, data_ptr), as _heads_weight): every step in stage 2, once in stage 1 and in eval."""
         wp, w3 = blk.proj_conv.weight, blk.convs.conv3.weight
@@ -329,10 +352,11 @@ class DeepWV3Plus(nn.Module):
         wkey = tuple((t._version, t.data_ptr()) for t in ws)
         if cc["wkey"] != wkey:
             with K._Timed("aspp_compose", 2.0 * sum(t.numel() for t in ws) * cc["Mt"].K, ("compose", len(ws))):
-                rows = []
-                wc = self._aspp_rows(ws, cc["Mt"], keep_rows=rows)
+                wc = self._aspp_rows(ws, cc["Mt"])
+                w0 = wc[0].dense()                 # the 1x1 branch is always read as its two packed K-halves
             c0 = cc["c0"]
-            cc.update(wkey=wkey, wc=wc, rows=rows, half0=K.pack_weight(wc[0][:, :c0].contiguous()), half1=K.pack_weight(wc[0][:, c0:].contiguous()))
+            cc.update(wkey=wkey, wc=wc, rows=[(w.rows, w.ld, w.kp) for w in wc], half0=K.pack_weight(w0[:, :c0].contiguous()),
+                      half1=K.pack_weight(w0[:, c0:].contiguous()))
         return cc
 
     # ---- decoder + heads -------------------------------------------------------------------------
@@ -406,7 +430,7 @@ class DeepWV3Plus(nn.Module):
             elif plan.pair_tile and i in (1, 2):
                 if i == 1:
                     sl2 = raw.slice(256 * 3, 256)          # ONE object: conv3x3_pair leaves the batch statistics on it
-                    K.conv3x3_pair(x, wts[1], wts[2], _ASPP_RATES[0], _ASPP_RATES[1], sl,
+                    K.conv3x3_pair(x, _dense(wts[1]), _dense(wts[2]), _ASPP_RATES[0], _ASPP_RATES[1], sl,
                                    sl2, plan.pair_tile, want_stats=train, xt=pre.take_pair() if pre else None)
                     pair_slices = {1: sl, 2: sl2}
                 sl = pair_slices[i]              # carries the statistics the producing transform left (train-mode BatchNorm)
@@ -421,7 +445,7 @@ class DeepWV3Plus(nn.Module):
                     K.conv3x3_dropped(x, ww, rate, sl, kx, train, xt, drop)
                     del ww
                 else:
-                    K.conv3x3(x, wts[i], dil=rate, out=sl, keep_xt=kx, want_stats=train, xt=xt)
+                    K.conv3x3(x, _dense(wts[i]), dil=rate, out=sl, keep_xt=kx, want_stats=train, xt=xt)
                 del xt
                 if kx:
                     aspp_xt[i] = kx["xt"]
@@ -577,7 +601,7 @@ class DeepWV3Plus(nn.Module):
                         flops = 2.0 * sum(held[k].numel() // (held[k].shape[0] if held[k].dim() == 5 else 1) for k in keys) * comp["M"].K
                         with K._Timed("aspp_compose", flops, ("project", len(keys))):
                             for k, g in zip(keys, self._aspp_rows([held[k] for k in keys], comp["M"], dropped=drop)):
-                                held[k] = g
+                                held[k] = g.dense()
                     for k, g in held.items():
                         grads[k] = g
                 # image-pooling branch: the broadcast's transpose is a column sum

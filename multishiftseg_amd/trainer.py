@@ -141,8 +141,10 @@ class GraphedEval:
         # own what the graph reads: the packed forms current right now (+ the fused heads weight of the model)
         self._keep = [dict(p.__dict__.get("_mss_packed", {})) for p in self.model.parameters()] + [self.model._heads_cache]
         cc = getattr(self.model, "_compose_cache", None)
-        if cc is not None:          # the composed ASPP weights (made in the warm-up, never inside the capture) and their packed forms
-            self._keep += [dict(cc)] + [dict(t.__dict__.get("_mss_packed", {})) for t in cc.get("wc", ())]
+        if cc is not None:          # the composed ASPP weights (made in the warm-up, never inside the capture: rows, and the dense tensors
+            # the warm-up's forward asked for) and their packed forms
+            dense = [t.made() for t in cc.get("wc", ())]
+            self._keep += [dict(cc), dense] + [dict(t.__dict__.get("_mss_packed", {})) for t in dense if t is not None]
         self._sig = self._signature()
         self.captures += 1
 

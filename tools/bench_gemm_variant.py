@@ -1,5 +1,7 @@
 """A/B of the two gemm_nt loader variants (MSS_GEMM_VARIANT=2: pointers, the r02 loader; 3: 32-bit offsets, branch-free advance
-and interleave, r03) on the step's products.  python tools/bench_gemm_variant.py [a,b]   (default 2,3)"""
+and interleave, r03) on the step's products.  python tools/bench_gemm_variant.py [a,b]   (default 2,3)
+A third and fourth argument name another switch and other products, e.g. the composed ASPP head's compose / project product with and
+without the mid-rounds hybrid:  python tools/bench_gemm_variant.py 0,-1 MSS_GEMM_TAIL 1:7168:4096:4096"""
 import sys, os, json, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -10,6 +12,8 @@ CASES = [(1, 65536, 2048, 1024), (36, 65536, 128, 128), (36, 16384, 256, 256), (
          (64, 2304, 4096, 256), (36, 5184, 4096, 256), (64, 29412, 304, 256), (64, 29412, 256, 256), (1, 65536, 2048, 4096), (1, 65536, 1024, 2048)]
 VA, VB = (sys.argv[1].split(",") if len(sys.argv) > 1 else ["2", "3"])
 VAR = sys.argv[2] if len(sys.argv) > 2 else "MSS_GEMM_VARIANT"        # e.g. `bench_gemm_variant.py 0,8 MSS_GEMM_GROUP_M`
+if len(sys.argv) > 3:
+    CASES = [tuple(int(v) for v in c.split(":")) for c in sys.argv[3].split(",")]
 for (P, T, C, Ko) in CASES:
     Kpad = _lib.value("mss_conv2d_kpad", Ko)
     w = torch.randn(P, Kpad, C, device="cuda")
