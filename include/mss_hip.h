@@ -752,7 +752,10 @@ int mss_upsample_bilinear_bwd_nhwc_f32(const float* dy, int lddy, int N, int OH,
 int mss_nchw_to_nhwc_strided_f32(const float* g, int N, int C, int HW, float* dst, int ldd, long long d_sample_stride,
                                  int accumulate, void* stream);
 /* FPN top-down step (msdeformattn.py:344): y = lat + F.interpolate(top, size=(OH, OW), mode="bilinear",
- * align_corners=False); NHWC with pixel strides (top also with a sample stride: a level inside the token buffer). */
+ * align_corners=False); NHWC with pixel strides (top also with a sample stride: a level inside the token buffer).
+ * lat == NULL: the interpolation alone, y = F.interpolate(top, ...), no lateral read and no add; ldl is ignored. Same source
+ * coordinates and blend as the add form, whose result over an all-zero lat it equals. Mask2Former stage 1 takes the decoder's
+ * pixel-major mask logits [n, hm, wm, ldq] to the padded image size with it (kernels.m2f_semantic_inference). */
 int mss_upsample_bilinear_add_nhwc_f32(const float* top, int ldt, long long top_sample_stride, int N, int IH, int IW,
                                        const float* lat, int ldl, float* y, int ldy, int OH, int OW, int C, void* stream);
 /* NHWC (pixel stride ldx, sample stride x_sample_stride floats) -> contiguous NCHW: the decoder returns NCHW maps like
@@ -862,7 +865,10 @@ int mss_m2f_loss_label_backward_f32(const MssM2fSteps* cls, const int* tclass, c
  *   values: the lowest class index (torch.max leaves that unspecified).
  * backward: dmasks in the layout of masks (the pad columns of a pixel-major layout written as 0) = sigmoid'(x) sum_c prob dmix;
  *   dcls [B,Q,C+1] = the softmax backward with the dropped column of dP[b,q,c] = sum_p dmix[b,c,p] sigmoid(x[b,q,p]), summed per
- *   workgroup (mss_m2f_mix_backward_chunks(h*w) workgroups per image) into partial [B, chunks, Q, C] double and folded in index order. */
+ *   workgroup (mss_m2f_mix_backward_chunks(h*w) workgroups per image) into partial [B, chunks, Q, C] double and folded in index order
+ *   (partial is scratch: the fold leaves each image's sums in the slot of its chunk 0).
+ *   dmasks == NULL (frozen masks, Mask2Former stage 1): neither the sigmoid'(x) sum_c prob dmix work nor the store of a tensor of
+ *   the size of masks; dcls is bit-identical to the full call's (the same partial sums, folded in the same order). */
 int mss_m2f_mix_backward_chunks(long long hw);
 int mss_m2f_mix_forward_f32(const float* cls, const float* masks, long long img_stride, long long query_stride, long long pixel_stride,
                             int B, int Q, int C, int h, int w, float* prob, float* mix, void* stream);

@@ -1,7 +1,8 @@
 """multishiftseg_amd: the MultiShiftSeg networks on hand-written HIP kernels for the MI355X. Sub-modules are imported on demand
 (`from multishiftseg_amd import kernels`); the names below are the package's module-level mirrors of reference classes."""
 
-_M2F_TRAINER = ("build_m2f_param_groups", "build_m2f_optimizer", "m2f_weight_dict", "weighted_losses", "M2FTrainStep")
+_M2F_TRAINER = ("build_m2f_param_groups", "build_m2f_optimizer", "m2f_weight_dict", "weighted_losses", "M2FTrainStep", "M2FStage1Step")
+_STAGE1_KERNELS = ("m2f_semantic_inference", "upsample_bilinear_nhwc", "stage1_chunks")
 
 
 def __getattr__(name):
@@ -32,6 +33,9 @@ def __getattr__(name):
     if name == "MaskFormer":
         from .maskformer import MaskFormer
         return MaskFormer
+    if name in _STAGE1_KERNELS:
+        from . import kernels
+        return getattr(kernels, name)
     if name in _M2F_TRAINER:
         from . import m2f_trainer
         return getattr(m2f_trainer, name)
@@ -39,4 +43,5 @@ def __getattr__(name):
 
 
 __all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention",
-           "conv2d_dgrad_s2", "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER]
+           "conv2d_dgrad_s2", "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER,
+           *_STAGE1_KERNELS]

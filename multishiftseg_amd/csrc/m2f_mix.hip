@@ -12,8 +12,10 @@
 //   mix_upsample_backward_kernel dM [B,C,h,w] in gather form: a thread owns a low-resolution pixel and walks, in one fixed order, the
 //                                output pixels of the crop whose taps contain it; for ds it recomputes the C interpolated values of
 //                                the output pixel and gives -ds to the largest (a tie: the lowest class index)
-//   mix_backward_kernel          dx in the layout of x, and per-workgroup partial sums of dP[b,q,c] = sum_p dM[b,c,p] sigmoid(x[b,q,p])
-//   mix_backward_cls_kernel      folds the partial sums in index order and applies the softmax backward with the dropped column
+//   mix_backward_kernel          dx in the layout of x, and per-workgroup partial sums of dP[b,q,c] = sum_p dM[b,c,p] sigmoid(x[b,q,p]);
+//                                without dx (dmasks == NULL: Mask2Former stage 1, frozen masks) the partial sums alone, same bits
+//   mix_backward_fold_kernel     folds the partial sums in index order, one thread per (b, q, c)
+//   mix_backward_cls_kernel      applies the softmax backward with the dropped column to the folded sums
 // No float atomics, no memset, no integer buffer: two runs give the same bits. DESIGN.md 3.14 holds the reasoning.
 #include "mss_common.h"
 #include "mss_bilinear.h"
@@ -192,7 +194,9 @@ __global__ __launch_bounds__(MX_T) void mix_upsample_backward_kernel(const float
 }
 
 // grid (chunks, B), chunks = ceil(hw / (MX_TP MX_TILES)). Lane = pixel of the tile, wave = every fourth group of 4 queries.
-template <int CP, bool PM>
+// DX false (frozen masks, stage 1): no dx is formed or stored, so the probability table is not staged, only wave 0 reads dM and the
+// pad columns of a pixel-major layout are not walked; sgs / sdm, the sums over them and their order are those of DX true.
+template <int CP, bool PM, bool DX>
 __global__ __launch_bounds__(MX_T) void mix_backward_kernel(const float* __restrict__ dmix, const float* __restrict__ prob,
                                                              const float* __restrict__ x, long long bs, long long qs, long long ps, int Q,
                                                              int C, long long hw, double* __restrict__ partial, float* __restrict__ dx) {
@@ -200,11 +204,11 @@ __global__ __launch_bounds__(MX_T) void mix_backward_kernel(const float* __restr
   __shared__ float sgs[MX_MAXQ * MX_LD];                    // sigmoid(x[q, p]) of the tile, 0 beyond the image
   __shared__ float sdm[CP * MX_LD];                         // dM[c, p] of the tile, 0 beyond the image
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  mix_stage_prob<CP>(prob, b, Q, C, sp);
+  if (DX) mix_stage_prob<CP>(prob, b, Q, C, sp);
   double pacc[MX_PAIRS];
 #pragma unroll
   for (int k = 0; k < MX_PAIRS; ++k) pacc[k] = 0.;
-  const int nq4 = PM ? (int)(ps >> 2) : (Q + 3) >> 2;       // pixel-major: every column up to ldq is written
+  const int nq4 = (PM && DX) ? (int)(ps >> 2) : (Q + 3) >> 2;       // pixel-major dx: every column up to ldq is written
   for (int t = 0; t < MX_TILES; ++t) {
     const long long p0 = ((long long)blockIdx.x * MX_TILES + t) * MX_TP;
     if (p0 >= hw) break;
@@ -212,8 +216,10 @@ __global__ __launch_bounds__(MX_T) void mix_backward_kernel(const float* __restr
     const long long p = p0 + lane;
     const bool live = p < hw;
     float dm[CP];
+    if (DX || wv == 0) {
 #pragma unroll
-    for (int c = 0; c < CP; ++c) dm[c] = (live && c < C) ? dmix[((long long)b * C + c) * hw + p] : 0.f;
+      for (int c = 0; c < CP; ++c) dm[c] = (live && c < C) ? dmix[((long long)b * C + c) * hw + p] : 0.f;
+    }
     if (wv == 0) {
 #pragma unroll
       for (int c = 0; c < CP; ++c) sdm[c * MX_LD + lane] = dm[c];
@@ -235,14 +241,16 @@ __global__ __launch_bounds__(MX_T) void mix_backward_kernel(const float* __restr
         o[j] = 0.f;                                         // the pad columns Q..ldq-1 of a pixel-major gradient
         if (q >= Q) continue;
         const float sg = mix_sigmoid(xv[j]);
-        const float* pr = sp + q * CP;
-        float dot = 0.f;
+        if (DX) {
+          const float* pr = sp + q * CP;
+          float dot = 0.f;
 #pragma unroll
-        for (int c = 0; c < CP; ++c) dot = __builtin_fmaf(pr[c], dm[c], dot);
-        o[j] = sg * (1.f - sg) * dot;
+          for (int c = 0; c < CP; ++c) dot = __builtin_fmaf(pr[c], dm[c], dot);
+          o[j] = sg * (1.f - sg) * dot;
+        }
         sgs[q * MX_LD + lane] = live ? sg : 0.f;
       }
-      if (!live) continue;
+      if (!DX || !live) continue;
       if (PM) {
         *reinterpret_cast<f32x4*>(dx + off + 4 * q4) = f32x4{o[0], o[1], o[2], o[3]};
       } else {
@@ -270,8 +278,23 @@ __global__ __launch_bounds__(MX_T) void mix_backward_kernel(const float* __restr
   }
 }
 
-// grid ceil(B Q / 256): one query per thread. dP[q, c] = the partial sums folded in chunk order; then the softmax over C + 1 with
-// the dropped column: dcls_j = p_j (g_j - sum_{c<C} p_c g_c), g_C = 0.
+// grid ceil(B Q C / 256): one (image, query, class) per thread, neighbouring threads on neighbouring doubles. Folds the image's
+// partial sums in chunk order, 0 + p_0 + p_1 + ..., and leaves dP[b, q, c] in the slot of chunk 0. A launch of its own because
+// mix_backward_cls_kernel has only one thread per query: folding there meant chunks x C loads, twice, one at a time (a mix at the
+// image's resolution has 968 chunks at 704 x 704: 13 ms of latency for five such images).
+__global__ __launch_bounds__(MX_T) void mix_backward_fold_kernel(double* __restrict__ partial, long long BQC, int QC, int chunks) {
+  const long long i = (long long)blockIdx.x * MX_T + threadIdx.x;
+  if (i >= BQC) return;
+  const long long b = i / QC;
+  double* p = partial + b * chunks * QC + (i - b * QC);
+  double g = 0.;
+#pragma unroll 8
+  for (int k = 0; k < chunks; ++k) g += p[(long long)k * QC];
+  p[0] = g;
+}
+
+// grid ceil(B Q / 256): one query per thread. dP[q, c] = what mix_backward_fold_kernel left in the slot of chunk 0; the softmax over
+// C + 1 with the dropped column: dcls_j = p_j (g_j - sum_{c<C} p_c g_c), g_C = 0.
 __global__ __launch_bounds__(MX_T) void mix_backward_cls_kernel(const float* __restrict__ cls, const double* __restrict__ partial, int B, int Q,
                                                                  int C, int chunks, float* __restrict__ dcls) {
   const long long i = (long long)blockIdx.x * MX_T + threadIdx.x;
@@ -284,17 +307,9 @@ __global__ __launch_bounds__(MX_T) void mix_backward_cls_kernel(const float* __r
   for (int c = 0; c <= C; ++c) se += exp((double)row[c] - (double)m);
   const double* pq = partial + (long long)b * chunks * Q * C + (long long)q * C;
   double dot = 0.;
-  for (int c = 0; c < C; ++c) {
-    double g = 0.;
-    for (int k = 0; k < chunks; ++k) g += pq[(long long)k * Q * C + c];
-    dot += exp((double)row[c] - (double)m) / se * g;
-  }
+  for (int c = 0; c < C; ++c) dot += exp((double)row[c] - (double)m) / se * pq[c];
   float* o = dcls + i * (C + 1);
-  for (int c = 0; c < C; ++c) {
-    double g = 0.;
-    for (int k = 0; k < chunks; ++k) g += pq[(long long)k * Q * C + c];
-    o[c] = (float)(exp((double)row[c] - (double)m) / se * (g - dot));
-  }
+  for (int c = 0; c < C; ++c) o[c] = (float)(exp((double)row[c] - (double)m) / se * (pq[c] - dot));
   o[C] = (float)(exp((double)row[C] - (double)m) / se * -dot);
 }
 
@@ -374,7 +389,7 @@ extern "C" int mss_m2f_mix_upsample_backward_f32(const float* dlogits, const flo
 extern "C" int mss_m2f_mix_backward_f32(const float* dmix, const float* prob, const float* cls, const float* masks, long long img_stride,
                                         long long query_stride, long long pixel_stride, int B, int Q, int C, int h, int w, double* partial,
                                         float* dmasks, float* dcls, void* stream) {
-  if (!dmix || !prob || !cls || !masks || !partial || !dmasks || !dcls) return MSS_ERR_BAD_ARG;
+  if (!dmix || !prob || !cls || !masks || !partial || !dcls) return MSS_ERR_BAD_ARG;
   if (!mix_shape_ok(B, Q, C, h, w)) return MSS_ERR_UNSUPPORTED;
   const long long hw = (long long)h * w;
   const int layout = mix_layout(img_stride, query_stride, pixel_stride, Q, hw);
@@ -382,12 +397,20 @@ extern "C" int mss_m2f_mix_backward_f32(const float* dmix, const float* prob, co
   hipStream_t st = (hipStream_t)stream;
   const int chunks = mss_m2f_mix_backward_chunks(hw);
   const dim3 grid(chunks, B);
-  if (layout)
-    MIX_BY_CP(C, (mix_backward_kernel<CP, true><<<grid, MX_T, 0, st>>>(dmix, prob, masks, img_stride, query_stride, pixel_stride, Q, C, hw, partial,
-                                                                       dmasks)));
+#define MIX_BWD(PM, DX)                                                                                                                        \
+  MIX_BY_CP(C, (mix_backward_kernel<CP, PM, DX><<<grid, MX_T, 0, st>>>(dmix, prob, masks, img_stride, query_stride, pixel_stride, Q, C, hw, \
+                                                                       partial, dmasks)))
+  if (layout && dmasks)
+    MIX_BWD(true, true);
+  else if (layout)
+    MIX_BWD(true, false);               // dmasks == NULL: the masks are frozen, dcls alone
+  else if (dmasks)
+    MIX_BWD(false, true);
   else
-    MIX_BY_CP(C, (mix_backward_kernel<CP, false><<<grid, MX_T, 0, st>>>(dmix, prob, masks, img_stride, query_stride, pixel_stride, Q, C, hw, partial,
-                                                                        dmasks)));
+    MIX_BWD(false, false);
+#undef MIX_BWD
+  const long long BQC = (long long)B * Q * C;
+  mix_backward_fold_kernel<<<mss_cdiv(BQC, MX_T), MX_T, 0, st>>>(partial, BQC, Q * C, chunks);
   mix_backward_cls_kernel<<<mss_cdiv((long long)B * Q, MX_T), MX_T, 0, st>>>(cls, partial, B, Q, C, chunks, dcls);
   return mss_launch_status();
 }

@@ -216,6 +216,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------ FPN top-down add
 // y = lat + bilinear(top -> OH x OW), align_corners=False (half-pixel centres, source index clamped at 0 as ATen's
 // area_pixel_compute_source_index does); grid (ceil(OW * C/4 / 256), OH, N)
+// ADD false: no lateral, y = bilinear(top) alone (lat is never dereferenced); the coordinates and the blend are the same expression
+template <bool ADD>
 __global__ __launch_bounds__(256) void upsample_add_kernel(const float* __restrict__ top, int ldt, long long top_ss, int IH,
                                                            int IW, const float* __restrict__ lat, int ldl,
                                                            float* __restrict__ y, int ldy, int OH, int OW, int C, float sh,
@@ -244,7 +246,10 @@ __global__ __launch_bounds__(256) void upsample_add_kernel(const float* __restri
   const f32x4 v10 = ld4(b + ((long long)y1 * IW + x0) * ldt), v11 = ld4(b + ((long long)y1 * IW + x1) * ldt);
   const long long o = ((long long)(n * OH + oy) * OW + ox);
   const f32x4 up = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
-  st4(y + o * ldy + c, ld4(lat + o * ldl + c) + up);
+  if constexpr (ADD)
+    st4(y + o * ldy + c, ld4(lat + o * ldl + c) + up);
+  else
+    st4(y + o * ldy + c, up);
 }
 
 // ------------------------------------------------------------------------------------------ NHWC -> NCHW
@@ -385,15 +390,21 @@ int mss_groupnorm_nhwc_f32(const float* x, int ldx, long long x_sample_stride, i
   return mss_launch_status();
 }
 
-// y = lat + bilinear(top [N,IH,IW,C] -> OH x OW, align_corners=False); all NHWC with their own pixel strides
+// y = lat + bilinear(top [N,IH,IW,C] -> OH x OW, align_corners=False); all NHWC with their own pixel strides. lat == NULL: the
+// interpolation alone (ldl is ignored), equal to the add form over an all-zero lateral
 int mss_upsample_bilinear_add_nhwc_f32(const float* top, int ldt, long long top_sample_stride, int N, int IH, int IW,
                                        const float* lat, int ldl, float* y, int ldy, int OH, int OW, int C, void* stream) {
-  if (!top || !lat || !y || C % 4 || ldt % 4 || ldl % 4 || ldy % 4) return MSS_ERR_BAD_ARG;
+  if (!top || !y || C % 4 || ldt % 4 || (lat && ldl % 4) || ldy % 4) return MSS_ERR_BAD_ARG;
   if ((long long)N * OH * OW == 0) return MSS_OK;
   if (OH > 65535 || N > 65535) return MSS_ERR_UNSUPPORTED;
   const float sh = (float)IH / (float)OH, sw = (float)IW / (float)OW;     // area_pixel_compute_scale, align_corners=False
-  hipLaunchKernelGGL(upsample_add_kernel, dim3((unsigned)(((long long)OW * (C / 4) + 255) / 256), OH, N), dim3(256), 0,
-                     S_(stream), top, ldt, top_sample_stride, IH, IW, lat, ldl, y, ldy, OH, OW, C, sh, sw);
+  const dim3 grid((unsigned)(((long long)OW * (C / 4) + 255) / 256), OH, N);
+  if (lat)
+    hipLaunchKernelGGL((upsample_add_kernel<true>), grid, dim3(256), 0, S_(stream), top, ldt, top_sample_stride, IH, IW, lat, ldl, y, ldy, OH,
+                       OW, C, sh, sw);
+  else
+    hipLaunchKernelGGL((upsample_add_kernel<false>), grid, dim3(256), 0, S_(stream), top, ldt, top_sample_stride, IH, IW, nullptr, 0, y, ldy,
+                       OH, OW, C, sh, sw);
   return mss_launch_status();
 }
 

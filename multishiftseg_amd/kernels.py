@@ -2017,11 +2017,12 @@ def m2f_mix_upsample_backward(mix, size, crop=None, dlogits=None, dscore=None):
     return dmix
 
 
-def m2f_class_mix_backward(dmix, prob, class_logits, mask_logits, pixel_major=False, Q=None):
+def m2f_class_mix_backward(dmix, prob, class_logits, mask_logits, pixel_major=False, Q=None, want_dmasks=True):
     """d / d (mask_logits, class_logits) of m2f_class_mix from dmix [B,C,h,w]; prob is its second result. -> (dmasks in the layout
     of mask_logits, every pad column Q..ldq-1 of a pixel-major layout 0; dcls [B,Q,C+1]). dmasks = sigmoid'(x) sum_c prob dmix;
     dcls = the softmax backward, with the dropped column, of dP[b,q,c] = sum_p dmix[b,c,p] sigmoid(x[b,q,p]): per-workgroup partial
-    sums folded in index order, no float atomics -- two runs give the same bits, and so do the two layouts."""
+    sums folded in index order, no float atomics -- two runs give the same bits, and so do the two layouts.
+    want_dmasks=False (frozen masks, stage 1): -> (None, dcls) with the same bits of dcls; dmasks is neither computed nor allocated."""
     name = "m2f_class_mix_backward"
     cls, x, strides, B, Q, C, h, w = _mix_inputs(name, class_logits, mask_logits, pixel_major, Q)
     _need_f32_cuda(name, dmix, prob)
@@ -2029,11 +2030,114 @@ def m2f_class_mix_backward(dmix, prob, class_logits, mask_logits, pixel_major=Fa
         raise ValueError(f"{name}: dmix {tuple(dmix.shape)} / prob {tuple(prob.shape)} for B {B}, Q {Q}, C {C}, {h} x {w}")
     chunks = _lib.value("mss_m2f_mix_backward_chunks", h * w)
     partial = torch.empty((B, chunks, Q, C), device=x.device, dtype=torch.float64)
-    dmasks = torch.empty_like(x)
+    dmasks = torch.empty_like(x) if want_dmasks else None
     dcls = torch.empty((B, Q, C + 1), device=x.device, dtype=torch.float32)
     call("mss_m2f_mix_backward_f32", ptr(dmix.contiguous()), ptr(prob.contiguous()), ptr(cls), ptr(x), strides[0], strides[1], strides[2],
          B, Q, C, h, w, ptr(partial), ptr(dmasks), ptr(dcls))
     return dmasks, dcls
+
+
+# ---- Mask2Former stage 1: the per-class sem_seg map and the differentiable anomaly score ---------------------------
+STAGE1_BUDGET_ENV = "MSS_M2F_STAGE1_U_BYTES"
+STAGE1_BUDGET_DEFAULT = 1 << 30
+
+
+def stage1_budget():
+    """Most bytes of upsampled mask logits U alive at once in m2f_semantic_inference: MSS_M2F_STAGE1_U_BYTES, default 1 GiB.
+    A memory cap, not a tuned number: the results do not depend on it."""
+    return int(os.environ.get(STAGE1_BUDGET_ENV, STAGE1_BUDGET_DEFAULT))
+
+
+def stage1_chunks(B, Hp, Wp, ldq, budget=None):
+    """The batch of B images as [(first image, images)] chunks of whole images whose U [images, Hp, Wp, ldq] float32 stays within
+    `budget` bytes; an image that alone exceeds the budget is a chunk of its own. Plain Python."""
+    budget = stage1_budget() if budget is None else int(budget)
+    if B < 1 or Hp < 1 or Wp < 1 or ldq < 1:
+        raise ValueError(f"stage1_chunks: B {B}, {Hp} x {Wp} x {ldq}")
+    per = max(1, min(B, budget // (4 * Hp * Wp * ldq)))
+    return [(s, min(per, B - s)) for s in range(0, B, per)]
+
+
+def _semantic_forward(cls, cls_ood, lg, Q, Hp, Wp, H, W, budget):
+    """-> (sem_seg [B,Cl,H,W], ood_score [B,H,W] or None, prob_ood [B,Q,C] or None, mix_ood [B,C,Hp,Wp] or None), chunk by chunk"""
+    B, _, _, ldq = lg.shape
+    sem, score, probs, mixes = [], [], [], []
+    for s, n in stage1_chunks(B, Hp, Wp, ldq, budget):
+        U = upsample_bilinear_nhwc(lg[s:s + n], (Hp, Wp))
+        mix, _ = m2f_class_mix(cls[s:s + n], U, pixel_major=True, Q=Q)
+        sem.append(m2f_mix_upsample(mix, (Hp, Wp), (H, W), "logits"))          # identity scale: the crop of sem_seg_postprocess
+        if cls_ood is not None:
+            mix_o, prob_o = m2f_class_mix(cls_ood[s:s + n], U, pixel_major=True, Q=Q)
+            score.append(m2f_mix_upsample(mix_o, (Hp, Wp), (H, W), "neg_max"))
+            probs.append(prob_o)
+            mixes.append(mix_o)
+        del U
+    one = len(sem) == 1
+    join = lambda parts: parts[0] if one else torch.cat(parts, 0)
+    if cls_ood is None:
+        return join(sem), None, None, None
+    return join(sem), 1 + join(score), join(probs), join(mixes)                # train_m2f.py:407: 1 - max_c
+
+
+class _SemanticInferenceFn(torch.autograd.Function):
+    """m2f_semantic_inference as one node, differentiable in class_logits_ood only. Saved: the low-resolution logits, prob_ood and
+    mix_ood; U is recomputed per chunk in the backward."""
+
+    @staticmethod
+    def forward(ctx, cls_ood, cls, lg, Q, Hp, Wp, H, W, budget):
+        sem, score, prob, mix = _semantic_forward(cls, cls_ood, lg, Q, Hp, Wp, H, W, budget)
+        ctx.save_for_backward(cls_ood, lg, prob, mix)
+        ctx.cfg = (Q, Hp, Wp, H, W, budget)
+        ctx.mark_non_differentiable(sem)
+        return sem, score
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _gsem, g):
+        cls_ood, lg, prob, mix = ctx.saved_tensors
+        Q, Hp, Wp, H, W, budget = ctx.cfg
+        B, _, _, ldq = lg.shape
+        g = g.contiguous().float()                                              # d (1 + neg_max) / d neg_max = 1
+        dcls = []
+        for s, n in stage1_chunks(B, Hp, Wp, ldq, budget):
+            U = upsample_bilinear_nhwc(lg[s:s + n], (Hp, Wp))
+            dmix = m2f_mix_upsample_backward(mix[s:s + n], (Hp, Wp), (H, W), dscore=g[s:s + n])
+            dcls.append(m2f_class_mix_backward(dmix, prob[s:s + n], cls_ood[s:s + n], U, pixel_major=True, Q=Q, want_dmasks=False)[1])
+            del U, dmix
+        return (dcls[0] if len(dcls) == 1 else torch.cat(dcls, 0)), None, None, None, None, None, None, None, None
+
+
+def m2f_semantic_inference(class_logits, mask_logits_nhwc, image_size, size=None, class_logits_ood=None, Q=None, budget=None):
+    """MaskFormer.semantic_inference on LOW-resolution pixel-major mask logits [B,hm,wm,ldq] in the reference's order
+    (maskformer_model.py:264-277, 343-345; sem_seg_postprocess is the crop): bilinear upsample to the padded `image_size`
+    (align_corners=False), sigmoid, einsum("qc,qhw->chw") with softmax(class_logits)[..., :-1], crop to `size` -> sem_seg
+    [B, min(C,19), H, W] (the reference's per-instance channels beyond the classes are what every caller slices off). With
+    class_logits_ood also the anomaly score of train_m2f.py:387-407 on the upsampled masks, ood_score [B,H,W] = 1 - max_c: ->
+    (sem_seg, ood_score). Q: the queries among the ldq columns (default: those of class_logits). The batch is processed in
+    chunks of whole images (stage1_chunks; `budget` bytes, default the MSS_M2F_STAGE1_U_BYTES switch); every chunking gives the
+    same bits. Differentiable in class_logits_ood only: sem_seg never requires grad, mask logits that require grad raise (stage 1
+    freezes the masks; stage 2 has criterion.class_mix_upsample)."""
+    name = "m2f_semantic_inference"
+    heads = [class_logits] + ([class_logits_ood] if class_logits_ood is not None else [])
+    _need_f32_cuda(name, mask_logits_nhwc, *heads)
+    if torch.is_grad_enabled() and mask_logits_nhwc.requires_grad:
+        raise NotImplementedError(f"{name}: no gradient to the mask logits (stage 1 freezes them; stage 2: criterion.class_mix_upsample)")
+    if mask_logits_nhwc.dim() != 4 or any(c.dim() != 3 or c.shape != class_logits.shape or c.shape[0] != mask_logits_nhwc.shape[0] for c in heads):
+        raise ValueError(f"{name}: class logits {[tuple(c.shape) for c in heads]} / mask logits {tuple(mask_logits_nhwc.shape)}")
+    ldq = mask_logits_nhwc.shape[-1]
+    Q = class_logits.shape[1] if Q is None else int(Q)
+    C = class_logits.shape[2] - 1
+    if Q != class_logits.shape[1] or not 1 <= Q <= min(ldq, MIX_MAX_QUERIES) or ldq % 4 or not 1 <= C <= MIX_MAX_CLASSES:
+        raise ValueError(f"{name}: Q {Q} of class logits {tuple(class_logits.shape)} and a pitch of {ldq} (a multiple of 4; "
+                         f"Q <= {MIX_MAX_QUERIES}, 1 <= C <= {MIX_MAX_CLASSES})")
+    (Hp, Wp), (H, W) = (int(v) for v in image_size), (int(v) for v in (image_size if size is None else size))
+    if not (1 <= H <= Hp and 1 <= W <= Wp):
+        raise ValueError(f"{name}: size {(H, W)} does not lie inside image_size {(Hp, Wp)}")
+    budget = stage1_budget() if budget is None else int(budget)
+    cls, lg = class_logits.detach().contiguous(), mask_logits_nhwc.detach().contiguous()
+    if class_logits_ood is None:
+        return _semantic_forward(cls, None, lg, Q, Hp, Wp, H, W, budget)[0]
+    return _SemanticInferenceFn.apply(class_logits_ood.contiguous(), cls, lg, Q, Hp, Wp, H, W, budget)
 
 
 # ---- Mask2Former pixel-decoder glue (csrc/norm.hip) --------------------------------------------------------------------
@@ -2110,6 +2214,20 @@ def upsample_bilinear_add(top, lat):
     y = Act.empty(lat.N, lat.H, lat.W, lat.C, lat.buf.device)
     tp, tld, tss = _strided(top)
     call("mss_upsample_bilinear_add_nhwc_f32", tp, tld, tss, top.N, top.H, top.W, lat.ptr, lat.ld, y.ptr, y.ld, lat.H, lat.W, lat.C)
+    return y
+
+
+def upsample_bilinear_nhwc(x, size):
+    """F.interpolate(x, size=(OH, OW), mode="bilinear", align_corners=False) of an NHWC float32 tensor [N,IH,IW,C] (C % 4 == 0) ->
+    [N,OH,OW,C]: the kernel of upsample_bilinear_add without a lateral (lat == NULL), equal to it over an all-zero lateral."""
+    _need_f32_cuda("upsample_bilinear_nhwc", x)
+    if x.dim() != 4 or x.shape[-1] % 4:
+        raise ValueError(f"upsample_bilinear_nhwc: {tuple(x.shape)} is not [N,IH,IW,C] with C a multiple of 4")
+    x = x.contiguous()
+    N, IH, IW, C = x.shape
+    OH, OW = int(size[0]), int(size[1])
+    y = torch.empty((N, OH, OW, C), device=x.device, dtype=torch.float32)
+    call("mss_upsample_bilinear_add_nhwc_f32", ptr(x), C, IH * IW * C, N, IH, IW, None, 0, ptr(y), C, OH, OW, C)
     return y
 
 

@@ -1,11 +1,14 @@
 """The stage-2 training step of Mask2Former around the HIP optimizer (optim.AdamW): the parameter groups and the optimizer of
 train_m2f.py:211-299, the weight dict of maskformer_model.py:143-153 and its application :253-258, and M2FTrainStep, which runs
 zero_grad / head / criterion / weighted sum / backward / clipped AdamW step. The reference reads every value from a detectron2
-config; here each is an argument. One process, one GPU: no DDP."""
+config; here each is an argument. One process, one GPU: no DDP.
+Stage 1 (the epochs before warmup_epoch, train_m2f.py:437-447): M2FStage1Step trains class_embed2 alone under optim.Adam with
+RelContrastiveLoss on MaskFormer.stage1_forward's (sem_seg, ood_score)."""
 import torch
 from torch import nn
 
-from .optim import AdamW
+from .optim import Adam, AdamW
+from .trainer import configure_trainable_params
 
 # train_m2f.py:233-244
 NORM_MODULE_TYPES = (
@@ -87,3 +90,26 @@ class M2FTrainStep:
         sum(losses.values()).backward()
         norm = self.optimizer.step()
         return {k: v.detach() for k, v in losses.items()}, norm
+
+
+class M2FStage1Step:
+    """One stage-1 step (train_m2f.py:414-456 for epoch < warmup_epoch; M2F.yaml:9, 24-27): only the parameters whose name contains
+    one of `patterns` train (trainer.configure_trainable_params sets every requires_grad), under the HIP Adam with torch's L2
+    weight decay. __call__(images, target): zero_grad ; (sem_seg, ood_score) = model.stage1_forward(images) ;
+    loss(sem_seg, ood_score, target).mean() ; backward ; step -> the detached loss. `loss` is RelContrastiveLoss (it needs an even
+    batch [orig...; aug...] and changes `target` in place, as the reference's does)."""
+
+    def __init__(self, model, loss, lr=1e-4, weight_decay=1e-4, patterns=("class_embed2",)):
+        self.model, self.loss = model, loss
+        params, self.names = configure_trainable_params(model, tuple(patterns))
+        if not params:
+            raise ValueError(f"M2FStage1Step: no parameter name contains one of {tuple(patterns)}")
+        self.optimizer = Adam(params, lr=lr, weight_decay=weight_decay)
+
+    def __call__(self, images, target):
+        self.optimizer.zero_grad(set_to_none=True)
+        sem_seg, ood_score = self.model.stage1_forward(images)
+        loss = self.loss(sem_seg, ood_score, target).mean()
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach()

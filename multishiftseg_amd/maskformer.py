@@ -13,7 +13,10 @@ Training (maskformer_model.py:235-258 without the criterion, which m2f_trainer.M
 the backbone (ResNet.set_trainable) and the predictor; with it on and grad mode enabled forward() runs pad -> backbone ->
 pixel_decoder.forward_features -> predictor on their autograd nodes, without ``fuse_score``, and returns the predictor's training
 outputs dict for the padded batch. Off, or under torch.no_grad(), the shell is the evaluation shell.
-Not built: the per-class ``sem_seg`` map of semantic_inference (the reference's evaluation reads only its shape).
+Stage 1 (train_m2f.py:437-447, M2F.yaml:9): ``stage1_forward`` runs the backbone and the pixel decoder as in evaluation and the
+predictor with ``semantic``: -> (the first 19 channels of the ``sem_seg`` map of semantic_inference, maskformer_model.py:341-345,
+and the anomaly score of get_anomaly_score on the upsampled ``*_ood`` heads), the score attached to ``class_embed2`` alone.
+``semantic_inference`` is the closed-set prediction by itself.
 """
 import torch
 from torch import nn
@@ -85,6 +88,32 @@ class MaskFormer(nn.Module):
     def ood_score(self, images):
         """Anomaly score [B, H, W] (train_m2f.py:387-407 on maskformer_model.py:260-277)."""
         return self.forward(images)["ood_score"]
+
+    def _semantic(self, images):
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"MaskFormer takes [B, 3, H, W] image batches, got {tuple(images.shape)}")
+        if self._trainable:
+            raise RuntimeError("MaskFormer: sem_seg / stage 1 run on the evaluation path of the backbone and the predictor: "
+                               "set_trainable(False) first")
+        H, W = images.shape[-2:]
+        with torch.no_grad():
+            x = self.pad(images.float())
+            features = self.backbone(x)
+            mask_features, _, multi_scale = self.sem_seg_head.pixel_decoder.forward_features(features)
+        return self.sem_seg_head.predictor(multi_scale, mask_features, None, semantic=(x.shape[-2], x.shape[-1], H, W))
+
+    def semantic_inference(self, images):
+        """The closed-set prediction [B, 19, H, W] at the images' own size: the first 19 channels of the "sem_seg" map of
+        maskformer_model.py:296-301, 341-345 (the per-instance channels behind them are what every caller slices off)."""
+        with torch.no_grad():
+            return self._semantic(images)["sem_seg"]
+
+    def stage1_forward(self, images):
+        """(sem_seg [B, 19, H, W], ood_score [B, H, W]) of train_m2f.py:438-446 at the images' own size. The backbone and the pixel
+        decoder run as in evaluation, under no_grad; the predictor is forward-only apart from class_embed2, the only parameters a
+        backward from ood_score reaches (any other trainable predictor parameter raises there). sem_seg never requires grad."""
+        out = self._semantic(images)
+        return out["sem_seg"], out["ood_score"]
 
     def evaluate(self, batches, meter=None):
         """valid_batch / test (train_m2f.py:469-509, test_m2f.py:109-158) with no copy to the host: `batches` yields (images, target);

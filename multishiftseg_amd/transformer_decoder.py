@@ -21,8 +21,9 @@ What runs (all in libmss_hip.so; tokens are batch-major [B, rows, 256] inside, t
 Supported: pre_norm=False, hidden_dim=256, nheads=8, mask_dim a multiple of 16, <= 128 queries, float32 CUDA inputs. Eval and
 "stage 1" training, where only class_embed2 receives a gradient (train_m2f.py, M2F.yaml:9); every other trainable parameter
 under an enabled grad mode raises, as does anything else outside this list. set_trainable() opts in to the differentiable path
-of stage 2 (_forward_train: the same arithmetic on autograd nodes, the attention's backward in csrc/m2f_attn.hip). There is no CPU
-path and no torch fallback.
+of stage 2 (_forward_train: the same arithmetic on autograd nodes, the attention's backward in csrc/m2f_attn.hip). forward(...,
+semantic=(Hp, Wp, H, W)) adds what stage 1 trains on: "sem_seg" and a differentiable "ood_score" (kernels.m2f_semantic_inference).
+There is no CPU path and no torch fallback.
 """
 import torch
 from torch import nn
@@ -225,27 +226,34 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
                                       f"the other parameters or call under torch.no_grad(); trainable: {bad[:4]} ... ({len(bad)})")
 
     # ---- reference API ----------------------------------------------------------------------------------------------------
-    def forward(self, x, mask_features, mask=None, *, fuse_score=None, return_attn_bits=False):
+    def forward(self, x, mask_features, mask=None, *, fuse_score=None, return_attn_bits=False, semantic=None):
         """As the reference's forward. fuse_score=(H, W): the last step's pixel-major mask logits go straight to
         kernels.m2f_score_fused with pred_logits_ood; the anomaly score [B, H, W] is returned as "ood_score" and the last step's
         NCHW "pred_masks" / "pred_masks_ood" are not materialised (None). fuse_score=(Hp, Wp, H, W): upsample to the padded image
         size (Hp, Wp) and keep the top-left (H, W) of it (maskformer_model.py:264-277 + sem_seg_postprocess). return_attn_bits: "attn_bits" = per layer the packed
         mask words [B, 2, HW, ceil(Q/32)] (int32; bit q of [b, 0 | 1, key] set = query q does not attend to that key in the
-        foreground | background attention) as the attention kernel applied them, i.e. after the rescue rule."""
+        foreground | background attention) as the attention kernel applied them, i.e. after the rescue rule.
+        semantic=(Hp, Wp, H, W): the dict gains "sem_seg" [B, min(C,19), H, W] (MaskFormer.semantic_inference of pred_logits on the
+        last step's masks upsampled to (Hp, Wp), cropped to (H, W)) and "ood_score" [B, H, W] (train_m2f.py:387-407 of
+        pred_logits_ood on the same upsampled masks), both from the last step's pixel-major logits through
+        kernels.m2f_semantic_inference. "ood_score" is attached to pred_logits_ood where class_embed2 requires grad (stage 1);
+        "sem_seg" never requires grad. Not together with fuse_score, which names the same key."""
         del mask                                                     # "disable mask, it does not affect performance" (:445)
+        if semantic is not None and (fuse_score is not None or len(tuple(semantic)) != 4):
+            raise ValueError("semantic=(Hp, Wp, H, W), and not together with fuse_score: both name \"ood_score\"")
         if len(x) != self.num_feature_levels:
             raise ValueError(f"expected {self.num_feature_levels} feature levels, got {len(x)}")
         if not mask_features.is_cuda or not all(t.is_cuda for t in x):
             raise RuntimeError("MultiScaleMaskedTransformerDecoder_GMA (multishiftseg_amd) runs on an MI355X only; there is no CPU path")
         if self._trainable and torch.is_grad_enabled():
-            return self._forward_train(x, mask_features, fuse_score, return_attn_bits)
+            return self._forward_train(x, mask_features, fuse_score, return_attn_bits, semantic)
         if mask_features.requires_grad or any(t.requires_grad for t in x):
             if torch.is_grad_enabled():
                 raise NotImplementedError("transformer_decoder (multishiftseg_amd): no backward to the inputs (forward only)")
         self._check_grad_mode()
         with torch.no_grad():
             state = self._forward_frozen(x, mask_features, fuse_score is not None)
-        return self._finish(state, fuse_score, return_attn_bits)
+        return self._finish(state, fuse_score, return_attn_bits, semantic)
 
     def _position(self, x):
         """[1, hw, C] position code of a level, kept per (size, device): it depends on nothing else."""
@@ -315,7 +323,7 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
             masks.append(None if last and skip_last_nchw else K.nhwc_to_nchw(K.Act(logits, C=Q)))
         return norms, masks, logits, bits_used
 
-    def _forward_train(self, x, mask_features, fuse_score, return_attn_bits):
+    def _forward_train(self, x, mask_features, fuse_score, return_attn_bits, semantic=None):
         """The differentiable path (set_trainable): _forward_frozen's arithmetic on autograd nodes -- linear / ffn_relu /
         add_layernorm, kernels.masked_attention, kernels.mask_logits; the stacked projections are torch.cat of the live parameters,
         so autograd splits their gradients; the mask bits come from the detached logits. fuse_score stays inference-only here: the
@@ -393,19 +401,19 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
             ffn = self.transformer_ffn_layers[i]
             tgt = K.add_layernorm(tgt, ffn_relu(tgt, ffn.linear1, ffn.linear2), ffn.norm)
             logits = heads(tgt)
-        return self._assemble(cls, cls_ood, masks, logits.detach(), bits_used, fuse_score, return_attn_bits)
+        return self._assemble(cls, cls_ood, masks, logits.detach(), bits_used, fuse_score, return_attn_bits, semantic)
 
-    def _finish(self, state, fuse_score, return_attn_bits):
+    def _finish(self, state, fuse_score, return_attn_bits, semantic=None):
         norms, masks, last_logits, bits_used = state
         cls, cls_ood = [], []
         for dn in norms:
             c, co = self._class_logits(dn)
             cls.append(c)
             cls_ood.append(co)
-        return self._assemble(cls, cls_ood, masks, last_logits, bits_used, fuse_score, return_attn_bits)
+        return self._assemble(cls, cls_ood, masks, last_logits, bits_used, fuse_score, return_attn_bits, semantic)
 
     @staticmethod
-    def _assemble(cls, cls_ood, masks, last_logits, bits_used, fuse_score, return_attn_bits):
+    def _assemble(cls, cls_ood, masks, last_logits, bits_used, fuse_score, return_attn_bits, semantic=None):
         # the reference runs forward_ood_heads after every layer but not on the initial queries: its OOD lists are one short, and
         # _set_aux_loss zips them against the full lists (:502-521, 563-571) -- aux entry j pairs step j with the OOD heads of layer j
         ood_c, ood_m = cls_ood[1:], masks[1:]
@@ -418,6 +426,10 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
         if fuse_score is not None:
             fs = tuple(fuse_score)
             out["ood_score"] = K.m2f_score_fused(ood_c[-1].detach(), last_logits, fs[:2], fs[2:] if len(fs) == 4 else None)
+        if semantic is not None:
+            Hp, Wp, H, W = (int(v) for v in semantic)
+            out["sem_seg"], out["ood_score"] = K.m2f_semantic_inference(cls[-1], last_logits, (Hp, Wp), (H, W), class_logits_ood=ood_c[-1],
+                                                                        Q=cls[-1].shape[1])
         if return_attn_bits:
             out["attn_bits"] = [bits & allowed.unsqueeze(2) for bits, allowed in bits_used]
         return out
