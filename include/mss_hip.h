@@ -254,7 +254,10 @@ int mss_conv2d_kpad(int K);
  * more than 64 output channels, or 33..64 of them over >= 16 384 rows), 2 for the few-rows kernel (1x1 over <= 8 pixels, nothing fused), 3 for the
  * split-bf16 form of the persistent GEMM kernel (args->w_split set and the shape eligible), 4 for its implicit-GEMM form, 5 for the 7x7 stem kernel
  * (csrc/stem7.hip; the shape listed above MssConvArgs), 6 for the stride-2 data-gradient kernel (csrc/conv_dgrad_s2.hip; stride == -2),
- * 0 for the native implicit-GEMM kernel. Profiling label only. */
+ * 0 for the native implicit-GEMM kernel. It is the launch's own decision (csrc/fwd_route.h). For arguments mss_conv2d_forward_f32
+ * refuses (MSS_ERR_BAD_ARG, MSS_ERR_UNSUPPORTED) it still answers a code 0..6 -- the kernel whose checks refuse them, or the one that
+ * would be asked once the general checks (pointers set and aligned, C % 16, ...) hold: callers label a call before its output
+ * pointer is set. Nothing is launched or dereferenced. */
 int mss_conv2d_forward_route(const MssConvArgs* args);
 /* The split-bf16 form of packed weights for MssConvArgs.w_split: w [batch][Kpad][C] fp32 (batch stride w_bs floats; what
  * mss_conv2d_pack_weights_f32 with R = S = 1 or mss_wino_pack_weights_f32 produce, Kpad % 128 == 0, C % 16 == 0) -> `planes`,

@@ -17,6 +17,7 @@
 // Loader ("issue early / write late", two K-steps ahead), MFMA loop and epilogue order are conv_igemm_kernel's (conv_igemm.hip,
 // mss_epilogue.h); what differs is the row enumeration, the tap geometry and an epilogue that scatters rows through a per-tile table.
 #include "mss_epilogue.h"
+#include "fwd_route.h"
 
 namespace {
 
@@ -284,8 +285,6 @@ int launch_dgrad_s2(MssConvArgs& p, hipStream_t stream) {
     most = t > most ? t : most;
   }
   p.mtiles = 4 * most;
-  p.ntiles = mss_cdiv(p.K, BN);
-  if (p.Kpad < p.ntiles * BN) return MSS_ERR_BAD_ARG;
   if ((long long)p.mtiles * p.ntiles > 0x7fffffffLL) return MSS_ERR_UNSUPPORTED;
   const size_t smem = ((size_t)2 * (BM + BN) * (BK + 4) + 4 + BM) * sizeof(float);
   static_assert(((size_t)2 * (BM + BN) * (BK + 4) + 4 + BM) * sizeof(float) <= 65536, "fits the default dynamic LDS limit");
@@ -299,28 +298,8 @@ int launch_dgrad_s2(MssConvArgs& p, hipStream_t stream) {
 
 }  // namespace
 
-// args->stride == -2: is this one of the taken shapes? (conv_igemm.hip asks before anything else looks at the arguments)
-bool mss_conv_dgrad_s2_wanted(const MssConvArgs& p) { return p.stride == -2; }
-
-int mss_conv_dgrad_s2_launch(MssConvArgs p, void* stream) {
-  if (!p.x || !p.w || !p.y) return MSS_ERR_BAD_ARG;
-  if (p.stats || p.batch > 1 || p.k_steps) return MSS_ERR_UNSUPPORTED;
-  if (p.dil != 1 || p.R != p.S || !((p.R == 3 && p.pad == 1) || (p.R == 1 && p.pad == 0))) return MSS_ERR_UNSUPPORTED;
-  if (p.C <= 0 || p.C % 16 || p.ldx % 4 || p.K <= 0) return MSS_ERR_UNSUPPORTED;
-  if (p.in_scale && p.in_ss_stride) return MSS_ERR_UNSUPPORTED;                  // one prologue affine for all samples
-  if (p.in_scale && !p.in_shift) return MSS_ERR_BAD_ARG;
-  if (p.out_scale && !p.out_shift) return MSS_ERR_BAD_ARG;
-  if (p.res_mask && !p.res) return MSS_ERR_BAD_ARG;
-  if (p.N < 0 || p.OH < 1 || p.OW < 1 || p.H < 1 || p.W < 1 || p.ldx < p.C || p.ldy < p.K || (p.res && p.ldres < p.K)) return MSS_ERR_BAD_ARG;
-  // the forward's floor loses a row / column, so OH and OW are the caller's; they must be a size the forward maps to H x W
-  if (p.H != (p.OH + 2 * p.pad - p.R) / 2 + 1 || p.W != (p.OW + 2 * p.pad - p.S) / 2 + 1) return MSS_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w)) & 15) return MSS_ERR_BAD_ARG;
-  if (p.in_scale && ((reinterpret_cast<uintptr_t>(p.in_scale) | reinterpret_cast<uintptr_t>(p.in_shift)) & 15)) return MSS_ERR_BAD_ARG;
-  if ((long long)p.N * p.OH * p.OW > 0x7fffffffLL || (long long)p.N * p.H * p.W > 0x7fffffffLL) return MSS_ERR_UNSUPPORTED;
-  p.M = p.N * p.OH * p.OW;
-  if (p.M <= 0) return MSS_OK;
+// p as fwd_route.h checked it (fwd_plan_dgrad_s2: shapes, Kpad, alignment) with p.M and p.ntiles filled in; r.BN chooses the tile.
+int mss_conv_dgrad_s2_launch(MssConvArgs p, const FwdRoute& r, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // the tiles of conv_igemm.hip: 256 x 64 for the <= 64-channel packs (Kpad 64), 128 x 128 x 16 otherwise
-  if (p.K <= 64) return launch_dgrad_s2<256, 64, 16, 4, 1>(p, s);
-  return launch_dgrad_s2<128, 128, 16, 2, 2>(p, s);
+  return r.BN == 64 ? launch_dgrad_s2<256, 64, 16, 4, 1>(p, s) : launch_dgrad_s2<128, 128, 16, 2, 2>(p, s);
 }

@@ -21,16 +21,13 @@
 #include "mss_epilogue.h"
 #include <stdlib.h>
 
-int mss_gemm_nt_dispatch(MssConvArgs p, void* stream);   // gemm.hip: persistent GEMM for the 1x1 / stride-1 shapes
-bool mss_gemm_nt_eligible(const MssConvArgs& p);
-bool mss_gemm_few_rows(const MssConvArgs& p);
-bool mss_gemm_nt_bf16x3_eligible(const MssConvArgs& p);   // gemm_bf16x3.hip
-bool mss_conv_bf16x3_eligible(const MssConvArgs& p);
-int mss_conv_bf16x3_launch(MssConvArgs p, void* stream);
-bool mss_stem7_eligible(const MssConvArgs& p);            // stem7.hip: the 7x7 / stride-2 / 4 -> 64 stem of the ResNet-50 backbone
-int mss_stem7_launch(MssConvArgs p, void* stream);
-bool mss_conv_dgrad_s2_wanted(const MssConvArgs& p);      // conv_dgrad_s2.hip: args->stride == -2, the data gradient of a stride-2 convolution
-int mss_conv_dgrad_s2_launch(MssConvArgs p, void* stream);
+#include "fwd_route.h"
+
+// the launchers of the other kernel families: they take the route as decided, and test nothing themselves
+int mss_gemm_nt_launch(MssConvArgs p, const FwdRoute& r, void* stream);          // gemm.hip: few rows, dense, hybrid and per-image launches
+int mss_fwd_bf16x3_launch(MssConvArgs p, const FwdRoute& r, void* stream);       // gemm_bf16x3.hip: the three split-bf16 families
+int mss_stem7_launch(MssConvArgs p, void* stream);                               // stem7.hip
+int mss_conv_dgrad_s2_launch(MssConvArgs p, const FwdRoute& r, void* stream);    // conv_dgrad_s2.hip
 
 namespace {
 
@@ -275,21 +272,7 @@ __global__ __launch_bounds__(NT) void conv_igemm_kernel(MssConvArgs p) {
 }
 
 template <int BM, int BN, int BK, int WM, int WN, bool PS, bool AFF>
-int launch_conv_t(MssConvArgs& p, hipStream_t stream);
-
-template <int BM, int BN, int BK, int WM, int WN>
-int launch_conv(MssConvArgs& p, hipStream_t stream) {
-  if (!p.in_scale) return launch_conv_t<BM, BN, BK, WM, WN, false, false>(p, stream);
-  // a tile can only straddle two images when the image's pixel count is not a multiple of BM
-  if (p.in_ss_stride && (p.OH * p.OW) % BM != 0) return launch_conv_t<BM, BN, BK, WM, WN, true, true>(p, stream);
-  return launch_conv_t<BM, BN, BK, WM, WN, false, true>(p, stream);
-}
-
-template <int BM, int BN, int BK, int WM, int WN, bool PS, bool AFF>
-int launch_conv_t(MssConvArgs& p, hipStream_t stream) {
-  p.mtiles = mss_cdiv(p.M, BM);
-  p.ntiles = mss_cdiv(p.K, BN);
-  if (p.Kpad < p.ntiles * BN) return MSS_ERR_BAD_ARG;
+int launch_conv_t(const MssConvArgs& p, hipStream_t stream) {
   const size_t smem = ((size_t)2 * (BM + BN) * (BK + 4) + 4) * sizeof(float);
   auto kern = conv_igemm_kernel<BM, BN, BK, WM, WN, PS, AFF>;
   if (smem > 65536) {
@@ -299,6 +282,17 @@ int launch_conv_t(MssConvArgs& p, hipStream_t stream) {
   }
   hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles, p.batch > 1 ? p.batch : 1), dim3(NT), smem, stream, p);
   return mss_launch_status();
+}
+
+// the route's (affine, per_sample) on one tile, then its tile: the nine instantiations of conv_igemm_kernel
+template <int BM, int BN, int BK, int WM, int WN>
+int launch_conv_tile(const MssConvArgs& p, const FwdRoute& r, hipStream_t stream) {
+  if (!r.affine) return launch_conv_t<BM, BN, BK, WM, WN, false, false>(p, stream);
+  return r.per_sample ? launch_conv_t<BM, BN, BK, WM, WN, true, true>(p, stream) : launch_conv_t<BM, BN, BK, WM, WN, false, true>(p, stream);
+}
+int launch_conv(const MssConvArgs& p, const FwdRoute& r, hipStream_t stream) {
+  if (r.BN == 64) return launch_conv_tile<256, 64, 16, 4, 1>(p, r, stream);
+  return r.BK == 32 ? launch_conv_tile<128, 128, 32, 2, 2>(p, r, stream) : launch_conv_tile<128, 128, 16, 2, 2>(p, r, stream);
 }
 
 // [K][C][R][S] (PyTorch) -> [R*S][Kpad][Cp], zero padded. flip=1 builds the dgrad weights:
@@ -515,55 +509,33 @@ __global__ __launch_bounds__(256) void unpack_wgrad_lines_kernel(const float* __
 
 extern "C" {
 
-int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
-  MssConvArgs p = *args;
-  if (!p.x || !p.w || !p.y) return MSS_ERR_BAD_ARG;
-  if (mss_conv_dgrad_s2_wanted(p)) return mss_conv_dgrad_s2_launch(p, stream);    // stride == -2 (route 6): checks its own shapes, ignores w_split
-  if (mss_stem7_eligible(p)) return mss_stem7_launch(p, stream);    // the one shape with C == 4 and 49 taps (route 5)
-  if (p.C % 16 || p.ldx % 4 || p.R * p.S > 9 || p.R * p.S < 1) return MSS_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w)) & 15) return MSS_ERR_BAD_ARG;
-  if (p.in_scale && ((reinterpret_cast<uintptr_t>(p.in_scale) | reinterpret_cast<uintptr_t>(p.in_shift)) & 15))
-    return MSS_ERR_BAD_ARG;
-  if (p.batch > 1 && (p.res || p.stats || p.x_bs % 4 || p.w_bs % 4 || p.batch > 65535)) return MSS_ERR_BAD_ARG;
-  if (p.res_mask && !p.res) return MSS_ERR_BAD_ARG;
-  p.M = p.N * p.OH * p.OW;
-  if (p.M <= 0) return MSS_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // read per call (not cached): the parity tests switch routes inside one process (MSS_GEMM=0: every layer on the
-  // implicit-GEMM kernel; tests/test_gpu_fullsize.py compares it with the GEMM/Winograd routes)
-  const int use_gemm = MSS_ENV_INT("MSS_GEMM", 1);
-  if (p.k_steps) {                 // per-image reduction lengths (csrc/chan_compact.hip): gemm_nt_kernel is the only kernel that has them
-    const int rc = mss_gemm_nt_dispatch(p, stream);
-    return rc >= 0 ? rc : MSS_ERR_UNSUPPORTED;
-  }
-  if (use_gemm) {
-    const int rc = mss_gemm_nt_dispatch(p, stream);
-    if (rc >= 0) return rc;
-  }
-  if (mss_conv_bf16x3_eligible(p)) return mss_conv_bf16x3_launch(p, stream);     // the split-bf16 route (args->w_split): gemm_bf16x3.hip, CONV
-  // K-step: 16 (41 KB LDS, 144 registers -> 3 workgroups/CU, 3 waves/SIMD) is the faster choice except
-  // for the ASPP shape (4096 input channels, 256 output channels), where the 32-deep step wins
-  // (measured: 128 vs 119 TFLOP/s).
-  if (p.K <= 64) return launch_conv<256, 64, 16, 4, 1>(p, s);
-  const bool k32 = p.C % 32 == 0 && p.C >= 2048 && p.K <= 256;
-  return k32 ? launch_conv<128, 128, 32, 2, 2>(p, s) : launch_conv<128, 128, 16, 2, 2>(p, s);
+// the switches of fwd_route.h, each cached at its site (mss_common.h) until mss_env_reset()
+static FwdSwitches fwd_switches() {
+  FwdSwitches sw;
+  sw.gemm = MSS_ENV_INT("MSS_GEMM", 1);
+  sw.variant = MSS_ENV_INT("MSS_GEMM_VARIANT", 3);
+  sw.tail = MSS_ENV_INT("MSS_GEMM_TAIL", -1);
+  sw.split_mfma = MSS_ENV_INT("MSS_GEMM_SPLIT_MFMA", 16);
+  return sw;
 }
 
-// Which kernel mss_conv2d_forward_f32 runs for these arguments: 1 = gemm_nt_kernel (gemm.hip), 0 = conv_igemm_kernel, 2 = gemm_few_rows_kernel,
-// 3 = gemm_nt_bf16x3_kernel, 4 = its implicit-GEMM / per-sample-affine instantiations (args->w_split set), 5 = stem7_conv_kernel (stem7.hip),
-// 6 = conv_dgrad_s2_kernel (conv_dgrad_s2.hip; args->stride == -2, on either route).
-int mss_conv2d_forward_route(const MssConvArgs* args) {
+int mss_conv2d_forward_f32(MssConvArgs* args, void* stream) {
   MssConvArgs p = *args;
-  if (mss_conv_dgrad_s2_wanted(p)) return 6;
-  if (mss_stem7_eligible(p)) return 5;
-  p.M = p.N * p.OH * p.OW;
-  if (p.k_steps) return 1;
-  if (!MSS_ENV_INT("MSS_GEMM", 1)) return mss_conv_bf16x3_eligible(p) ? 4 : 0;      // as the forward: MSS_GEMM=0 only skips the NT dispatch
-  if (mss_gemm_few_rows(p)) return 2;                  // (0 implicit-GEMM kernel, 1 gemm_nt_kernel, 2 gemm_few_rows_kernel)
-  if (!mss_gemm_nt_eligible(p)) return mss_conv_bf16x3_eligible(p) ? 4 : 0;
-  p.mtiles = (p.M + 127) / 128;
-  return mss_gemm_nt_bf16x3_eligible(p) ? 3 : 1;
+  const FwdRoute r = fwd_route(p, fwd_switches());
+  if (r.status != MSS_OK) return r.status;
+  if (r.M <= 0) return MSS_OK;
+  fwd_fill_args(p, r);
+  switch (r.kernel) {
+    case FWD_DGRAD_S2: return mss_conv_dgrad_s2_launch(p, r, stream);
+    case FWD_STEM7: return mss_stem7_launch(p, stream);
+    case FWD_FEW_ROWS: case FWD_GEMM_NT: case FWD_GEMM_NT_PERIMG: return mss_gemm_nt_launch(p, r, stream);
+    case FWD_GEMM_NT_BF16X3: case FWD_CONV_BF16X3: case FWD_ROWAFF_BF16X3: return mss_fwd_bf16x3_launch(p, r, stream);
+    default: return launch_conv(p, r, static_cast<hipStream_t>(stream));
+  }
 }
+
+// Which kernel mss_conv2d_forward_f32 runs for these arguments (include/mss_hip.h has the codes): the launch's own decision.
+int mss_conv2d_forward_route(const MssConvArgs* args) { return fwd_route_code(fwd_route(*args, fwd_switches())); }
 
 // Kpad the packed layout must use for a conv with K output channels (multiple of the N tile).
 int mss_conv2d_kpad(int K) { return K <= 64 ? 64 : ((K + 127) / 128) * 128; }

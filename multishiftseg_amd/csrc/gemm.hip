@@ -17,12 +17,12 @@
 // same L2.
 #include "mss_epilogue.h"
 #include "mss_gemm_tiles.h"
-#include "gemm_rounds.h"
+#include "fwd_route.h"
 #include <stdlib.h>
 
 namespace {
 
-constexpr int NT = 256, BM = 128, BK = 16;
+constexpr int NT = 256, BM = MSS_GEMM_BM, BK = MSS_GEMM_BK;
 // LDS rows are 16 floats with NO padding; the four 16-byte chunks of row r are rotated by (r >> 2): a staging write
 // (16 lanes = 4 rows x 4 chunks) and a fragment read (16 lanes = 16 rows x 1 chunk) then both touch 16 disjoint
 // 4-bank spans. (The +4-float padding of conv_igemm is conflict-free for the reads only: PMC showed a third of the
@@ -332,160 +332,37 @@ int launch_gemm(const MssConvArgs& p, hipStream_t stream, long long first = 0, l
   return mss_launch_status();
 }
 
+// The instantiation (affine, variant, bn) of the route -- one of the twelve that exist: the 128 x 64 tile and the per-image mode are
+// variant 3 only, the per-image mode has no prologue (fwd_route.h never asks for another). `bn` is a parameter because a hybrid
+// launches two widths.
+template <int VARIANT, int BN>
+int launch_gemm_affine(const MssConvArgs& p, bool affine, hipStream_t stream, long long first, long long end) {
+  return affine ? launch_gemm<true, VARIANT, BN>(p, stream, first, end) : launch_gemm<false, VARIANT, BN>(p, stream, first, end);
+}
+int launch_gemm_as(const MssConvArgs& p, const FwdRoute& r, int bn, hipStream_t stream, long long first = 0, long long end = -1) {
+  if (r.kernel == FWD_GEMM_NT_PERIMG) return bn == 256 ? launch_gemm<false, 3, 256, true>(p, stream) : launch_gemm<false, 3, 128, true>(p, stream);
+  if (bn == 64) return launch_gemm_affine<3, 64>(p, r.affine, stream, first, end);
+  if (r.variant == 3) return bn == 256 ? launch_gemm_affine<3, 256>(p, r.affine, stream, first, end) : launch_gemm_affine<3, 128>(p, r.affine, stream, first, end);
+  return bn == 256 ? launch_gemm_affine<2, 256>(p, r.affine, stream, first, end) : launch_gemm_affine<2, 128>(p, r.affine, stream, first, end);
+}
+
 }  // namespace
 
-bool mss_gemm_nt_bf16x3_eligible(const MssConvArgs& p);       // gemm_bf16x3.hip: the split-bf16 route (MssConvArgs.w_split)
-int mss_gemm_nt_bf16x3_launch(MssConvArgs p, void* stream);
-
-// Shapes this kernel takes from mss_conv2d_forward_f32 (conv_igemm.hip); p.M is set.
-// 33..64 output channels over many rows (the 48-channel heads and bot_fine, 1 M pixels) on the persistent kernel with a 128 x 64
-// tile instead of conv_igemm's one-tile-per-workgroup 256 x 64 kernel: 0.203 -> 0.184 ms (256 -> 48) and 0.116 -> 0.087 ms
-// (128 -> 48) at 1 x 512 x 1024
-static bool gemm_bn64_wanted(const MssConvArgs& p) {
-  // r05: from K >= 32 (33 before): 256 -> 32 over 162 k rows (the tail of the pixel decoder's
-  // 288-wide projection, 31 TFLOP/s on conv_igemm's 256 x 64 tile)
-  // r06: batched products too (the 48-channel tail of the 304-wide Winograd-domain data gradient of final.0: 64 x 29412 x 256 -> 48,
-  // conv_igemm's one-tile-per-workgroup kernel streamed its 1.9 GB of X' at 2.6 TB/s: 2.58 -> 2.47 ms native, 1.92 -> 1.75 ms on the
-  // split route for the whole 304-wide product)
-  return p.K <= 64 && p.K >= 32 && p.C / BK >= 3 && p.M >= 16384;
-}
-
-bool mss_gemm_nt_eligible(const MssConvArgs& p) {
-  if (p.R * p.S != 1 || p.stride != 1 || p.pad != 0 || p.H != p.OH || p.W != p.OW) return false;
-  if ((p.K <= 64 && !gemm_bn64_wanted(p)) || p.C % BK || p.C < 2 * BK) return false;        // narrow outputs stay on the 256x64 tile
-  if (p.in_relu && !p.in_scale) return false;                      // ReLU without affine: not a shape this path sees
-  if (p.in_scale && p.in_ss_stride && (p.OH * p.OW) % BM) return false;   // per-sample affine: tiles must not straddle images
-  return true;
-}
-
-// Returns -1 when the shape is not handled here (the implicit-GEMM kernel takes it).
-// 1x1 layers over <= 32 pixels with nothing fused (the ASPP image-pooling product: one row per image -- 16 at 16 x 768 x 768, where
-// the MFMA tile path took 0.255 ms): gemm_few_rows_kernel (p.M is set)
-bool mss_gemm_few_rows(const MssConvArgs& p) {
-  return p.R * p.S == 1 && p.stride == 1 && p.pad == 0 && p.H == p.OH && p.W == p.OW && p.M > 0 && p.M <= 32 && p.batch <= 1 &&
-         p.C % 4 == 0 && p.ldx % 4 == 0 && !p.in_scale && !p.in_relu && !p.out_scale && !p.out_relu && !p.res && !p.stats &&
-         ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w)) & 15) == 0;
-}
-
-int mss_gemm_nt_dispatch(MssConvArgs p, void* stream) {
-  if (mss_gemm_few_rows(p)) {
+// The launches of fwd_route.h's FWD_FEW_ROWS, FWD_GEMM_NT and FWD_GEMM_NT_PERIMG; p as fwd_fill_args left it.
+int mss_gemm_nt_launch(MssConvArgs p, const FwdRoute& r, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (r.kernel == FWD_FEW_ROWS) {
     const dim3 grid((p.K + 3) / 4);
-    hipStream_t fs = static_cast<hipStream_t>(stream);
-    if (p.M <= 8) hipLaunchKernelGGL(gemm_few_rows_kernel<8>, grid, dim3(256), 0, fs, p.x, p.ldx, p.w, p.y, p.ldy, p.M, p.C, p.K);
-    else if (p.M <= 16) hipLaunchKernelGGL(gemm_few_rows_kernel<16>, grid, dim3(256), 0, fs, p.x, p.ldx, p.w, p.y, p.ldy, p.M, p.C, p.K);
-    else hipLaunchKernelGGL(gemm_few_rows_kernel<32>, grid, dim3(256), 0, fs, p.x, p.ldx, p.w, p.y, p.ldy, p.M, p.C, p.K);
+    if (r.BM == 8) hipLaunchKernelGGL(gemm_few_rows_kernel<8>, grid, dim3(256), 0, s, p.x, p.ldx, p.w, p.y, p.ldy, p.M, p.C, p.K);
+    else if (r.BM == 16) hipLaunchKernelGGL(gemm_few_rows_kernel<16>, grid, dim3(256), 0, s, p.x, p.ldx, p.w, p.y, p.ldy, p.M, p.C, p.K);
+    else hipLaunchKernelGGL(gemm_few_rows_kernel<32>, grid, dim3(256), 0, s, p.x, p.ldx, p.w, p.y, p.ldy, p.M, p.C, p.K);
     return mss_launch_status();
   }
-  if (p.k_steps) {
-    // the per-image product behind csrc/chan_compact.hip: image n = rows [n * OH * OW, (n + 1) * OH * OW) runs k_steps[n] K-steps
-    // over its own weights w + n * w_img_stride. It exists on this kernel only (variant 3, no prologue: the compaction pass applied
-    // it), so a shape that does not qualify is an error, never another route.
-    if (!mss_gemm_nt_eligible(p) || p.in_scale || p.w_split || p.K <= 64 || p.C / BK < 3 || p.w_img_stride % 4 || p.w_img_stride < 0 ||
-        p.k_base < 0 || p.k_imgs < 0)
-      return MSS_ERR_UNSUPPORTED;
-    hipStream_t ps = static_cast<hipStream_t>(stream);
-    if (p.k_imgs > 0) {
-      // batch entries of one image each (the dropped-channel Winograd-domain products): p.M rows per entry, the last row tile of an
-      // entry partial; k_base + k_steps[b % k_imgs] K-steps, >= 3 since k_steps is
-      if (p.batch < 2 || p.batch % p.k_imgs || p.w_img_stride || p.N != 1 || p.k_base * BK > p.C) return MSS_ERR_UNSUPPORTED;
-      p.H = p.M;
-      p.mtiles = mss_cdiv(p.M, BM);
-      p.ntiles = mss_cdiv(p.K, 128);
-      if (p.Kpad < p.ntiles * 128) return MSS_ERR_BAD_ARG;
-      if ((unsigned long long)((long long)(p.batch - 1) * p.x_bs + (long long)p.M * p.ldx) * 4ull >= 0xffffffffull ||
-          (unsigned long long)((long long)(p.batch - 1) * p.w_bs + (long long)p.Kpad * p.C) * 4ull >= 0xffffffffull)
-        return MSS_ERR_UNSUPPORTED;
-      // tile width: the dense products' rule (below), on this launch's tile counts
-      const long long t256 = (long long)p.mtiles * (p.K / 256) * p.batch;
-      bool wide = p.K % 256 == 0 && t256 >= 1024 && p.C >= 256;
-      if (wide) {
-        const double ew = (double)t256 / (double)(((t256 + 511) / 512) * 512), en = (double)(2 * t256) / (double)(((2 * t256 + 767) / 768) * 768);
-        if (ew < 0.8 && en > ew + 0.15) wide = false;
-      }
-      if (wide) {
-        p.ntiles = p.K / 256;
-        return launch_gemm<false, 3, 256, true>(p, ps);
-      }
-      return launch_gemm<false, 3, 128, true>(p, ps);
-    }
-    if (p.batch > 1 || (p.OH * p.OW) % BM) return MSS_ERR_UNSUPPORTED;
-    p.H = p.OH * p.OW;                                    // rows per image
-    p.mtiles = mss_cdiv(p.M, BM);
-    p.ntiles = mss_cdiv(p.K, 128);
-    if (p.Kpad < p.ntiles * 128) return MSS_ERR_BAD_ARG;
-    if ((unsigned long long)p.M * p.ldx * 4ull >= 0xffffffffull ||
-        (unsigned long long)((long long)(p.N - 1) * p.w_img_stride + (long long)p.Kpad * p.C) * 4ull >= 0xffffffffull)
-      return MSS_ERR_UNSUPPORTED;
-    // tile width: the dense rule below without its last-round refinements (the per-image step counts make rounds uneven anyway)
-    if (p.K % 256 == 0 && (long long)p.mtiles * (p.K / 256) >= 1024 && p.C >= 256) {
-      p.ntiles = p.K / 256;
-      return launch_gemm<false, 3, 256, true>(p, ps);
-    }
-    return launch_gemm<false, 3, 128, true>(p, ps);
-  }
-  if (!mss_gemm_nt_eligible(p)) return -1;
-  p.H = (p.in_scale && p.in_ss_stride) ? p.OH * p.OW : (p.M > 0 ? p.M : 1);   // rows per affine group
-  p.mtiles = mss_cdiv(p.M, BM);
-  if (p.K <= 64) {                                       // (experiment, see gemm_bn64_wanted)
-    p.ntiles = 1;
-    if (p.Kpad < 64) return MSS_ERR_BAD_ARG;
-    const long long nb = p.batch > 1 ? p.batch : 1;       // variant 3: 32-bit byte offsets over the whole batch
-    const long long span_x = ((nb - 1) * p.x_bs + (long long)p.M * p.ldx) * 4, span_w = ((nb - 1) * p.w_bs + (long long)p.Kpad * p.C) * 4;
-    if (span_x >= 0xffffffffll || span_w >= 0xffffffffll) return -1;
-    return p.in_scale ? launch_gemm<true, 3, 64>(p, static_cast<hipStream_t>(stream)) : launch_gemm<false, 3, 64>(p, static_cast<hipStream_t>(stream));
-  }
-  p.ntiles = mss_cdiv(p.K, 128);
-  if (p.Kpad < p.ntiles * 128) return MSS_ERR_BAD_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mss_gemm_nt_bf16x3_eligible(p)) return mss_gemm_nt_bf16x3_launch(p, stream);      // the split-bf16 route, chosen by the caller
-  // measured (tools/bench_bgemm.py, tools/bench_1x1.py, r02): variant 2 is +3-7 % on every shape (C = 128: 82.7 -> 86.9,
-  // 512: 127 -> 132, 1024 -> 2048: 132 -> 136 TFLOP/s; 1x1 2048 -> 4096 with prologue/residual/statistics: 123 -> 128)
-  // r03: variant 3 (32-bit offsets, branch-free advance, loader instructions interleaved with the MFMAs) is +4-6 % from C = 256 up
-  // (36 x 16384 x 256 -> 256: 125 -> 130, 512 -> 512: 128 -> 136, 1024 -> 2048: 133 -> 140, 1x1 2048 -> 4096: 139 -> 146 TFLOP/s) and
-  // +0.5 % at C = 128, bit-identical results (tools/bench_gemm_variant.py, alternating A/B); shapes it does not take fall back to 2
-  // variant 3 addresses its operands with 32-bit byte offsets and needs >= 3 K-steps per tile (see the kernel); MSS_GEMM_VARIANT=2
-  // forces variant 2 everywhere (the reference of the bitwise test)
-  const long long nb3 = p.batch > 1 ? p.batch : 1;
-  const bool v3 = MSS_ENV_INT("MSS_GEMM_VARIANT", 3) == 3 && p.C / BK >= 3 &&
-                  (unsigned long long)((nb3 - 1) * p.x_bs + (long long)p.M * p.ldx) * 4ull < 0xffffffffull &&
-                  (unsigned long long)((nb3 - 1) * p.w_bs + (long long)p.Kpad * p.C) * 4ull < 0xffffffffull;
-  // Tile width and rounds (gemm_rounds.h, mss_gemm_rounds). 256-wide tiles when the output channels split evenly, the reduction is
-  // long enough and there is work for two rounds of the 512 slots. Measured (tools/bench_bgemm.py, bench_1x1.py): 1x1 2048 -> 4096
-  // 127 -> 133, ASPP 4096 -> 256 123 -> 131, 1024 -> 2048 136 -> 138, C = 304 122 -> 126 TFLOP/s; C = 256: 122 -> 121 (not taken).
-  //
-  // Hybrid last round (MSS_GEMM_TAIL: -1 default rules, 0 never, 1 wherever it fits): when the wide tiles leave a partial last round
-  // that is at most 3/4 full, the whole rounds run on wide tiles and the remainder as twice as many narrow tiles in a second launch
-  // -- narrow tile 2w + {0, 1} is wide tile w's left / right half in the same n-fastest order -- e.g. 64 x 15 x 2 = 1920
-  // wide tiles (mod4 through F(6x6)): 3 wide rounds + exactly one round of 768 narrow tiles instead of 3.75 -> 4.
-  // Bit-identical results. Measured: isolated 0.582 -> 0.558 ms (64 x 1892 x 512 -> 512) and 1.172 -> 1.129 ms (64 x 2112 x
-  // 512 -> 1024); in the step 67.3 -> 67.1 ms of gemm_nt (the narrow round is slower per FLOP and costs a second launch): for
-  // batched products it stays opt-in (MSS_GEMM_TAIL=1), 0.2 ms per step does not pay for one GEMM call becoming two kernel launches.
-  // r03: a default rule for nearly-empty last rounds (rem <= 128; only one-image eval products qualify) measured +-0 on the eval
-  // forward (42.15 -> 42.15 ms). The two launches use the variant-3 kernels where the shape allows.
-  // r04 default rule: single-position products with at most four whole rounds, where the idle part of the last round is a
-  // visible share of the launch -- the pixel decoder's Linears over 16 x 10 164 tokens are 1271 wide tiles = 2.48 rounds: decoder
-  // forward + backward 66.15 -> 65.78 ms with the hybrid, bit-identical.
-  // Default rule for single-position products between one and two wide rounds: one wide round, then at most one narrow
-  // round, where all-narrow tiles (MSS_GEMM_TAIL=0 keeps them) walk uneven chains -- the composed ASPP head's compose and project
-  // products, 7168 x 4096 -> 4096 = 896 wide tiles = 512 + 384. Still one C call and one trace row.
-  const MssGemmRounds rounds = mss_gemm_rounds(p.mtiles, p.K, p.C, p.batch, MSS_ENV_INT("MSS_GEMM_TAIL", -1));
-  if (rounds.mode != MSS_GEMM_NARROW) {
-    const int nw = p.K / 256;
-    if (rounds.mode == MSS_GEMM_HYBRID) {
-      const long long full = rounds.full, tiles256 = rounds.full + rounds.rem;
-      MssConvArgs q = p;
-      q.ntiles = nw;
-      int rc = v3 ? (p.in_scale ? launch_gemm<true, 3, 256>(q, s, 0, full) : launch_gemm<false, 3, 256>(q, s, 0, full))
-                  : (p.in_scale ? launch_gemm<true, 2, 256>(q, s, 0, full) : launch_gemm<false, 2, 256>(q, s, 0, full));
-      if (rc) return rc;
-      q.ntiles = 2 * nw;
-      if (v3) return p.in_scale ? launch_gemm<true, 3, 128>(q, s, 2 * full, 2 * tiles256) : launch_gemm<false, 3, 128>(q, s, 2 * full, 2 * tiles256);
-      return p.in_scale ? launch_gemm<true, 2, 128>(q, s, 2 * full, 2 * tiles256) : launch_gemm<false, 2, 128>(q, s, 2 * full, 2 * tiles256);
-    }
-    p.ntiles = nw;
-    if (v3) return p.in_scale ? launch_gemm<true, 3, 256>(p, s) : launch_gemm<false, 3, 256>(p, s);
-    return p.in_scale ? launch_gemm<true, 2, 256>(p, s) : launch_gemm<false, 2, 256>(p, s);
-  }
-  if (v3) return p.in_scale ? launch_gemm<true, 3, 128>(p, s) : launch_gemm<false, 3, 128>(p, s);
-  return p.in_scale ? launch_gemm<true, 2, 128>(p, s) : launch_gemm<false, 2, 128>(p, s);
+  if (r.rounds.mode != MSS_GEMM_HYBRID) return launch_gemm_as(p, r, r.BN, s);
+  // wide tiles [0, full), then narrow tiles [2 * full, 2 * tiles256): narrow tile 2w + {0, 1} is wide tile w's left / right half (gemm_rounds.h)
+  const long long full = r.rounds.full, tiles256 = r.rounds.full + r.rounds.rem;
+  const int rc = launch_gemm_as(p, r, 256, s, 0, full);
+  if (rc) return rc;
+  p.ntiles = 2 * r.ntiles;
+  return launch_gemm_as(p, r, 128, s, 2 * full, 2 * tiles256);
 }

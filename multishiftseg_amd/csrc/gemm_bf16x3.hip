@@ -22,6 +22,7 @@
 #include "mss_gemm_tiles.h"
 #include "mss_bf16x3.h"
 #include "wgrad_route.h"
+#include "fwd_route.h"
 #include <stdlib.h>
 #include <mutex>
 #include <unordered_map>
@@ -111,7 +112,7 @@ namespace {
 // kernels with a prologue, see gemm_nt_bf16x3_kernel). Measured in round 5 with an all-tickets A/B build that round 6 removed
 // (profiles/r05/dynamic_tiles.md): the ticket order equalises the workgroups' lifetimes and changes the launch time by +1 % .. -8 %,
 // because the workgroup the static order leaves alone on its SIMDs runs almost twice as fast there.
-constexpr int NT = 256, BM = 128;
+constexpr int NT = 256, BM = MSS_GEMM_BM;
 using mss_bf16x3::BK;
 using mss_bf16x3::ROW_B;
 using mss_bf16x3::PLANE;
@@ -1047,15 +1048,6 @@ int launch_split_as(const MssConvArgs& p, hipStream_t stream, int* sched) {
   return mss_launch_status();
 }
 
-// what mss_epilogue_store16's 16-byte accesses need
-bool split_mf16_ok(const MssConvArgs& p) {
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (p.K % 4 || p.ldy % 4 || !al(p.y) || (p.batch > 1 && p.y_bs % 4)) return false;
-  if (p.res && (p.ldres % 4 || !al(p.res))) return false;
-  if (p.out_scale && (!al(p.out_scale) || !al(p.out_shift))) return false;
-  return !p.stats || al(p.stats);
-}
-
 thread_local int split_last_mfma = 0;      // mss_gemm_split_last_mfma()
 
 template <bool AFFINE, int BN, bool CONV, bool ROWAFF, int MF>
@@ -1068,56 +1060,28 @@ int launch_split_mf(const MssConvArgs& p, hipStream_t stream) {
   return launch_split_as<AFFINE, BN, CONV, ROWAFF, false, MF>(p, stream, nullptr);   // no slot to be had: the static walk
 }
 
+// the 16x16x32 form exists for the products WITHOUT a prologue (fwd_route.h, FwdSwitches::split_mfma, decides and has the measurements)
 template <bool AFFINE, int BN, bool CONV = false, bool ROWAFF = false>
-int launch_split(const MssConvArgs& p, hipStream_t stream) {
-  // MSS_GEMM_SPLIT_MFMA=32: the round-5 form (one product per v_mfma_f32_32x32x16_bf16) for A/B and for outputs mss_epilogue_store16 cannot take
-  // The 16x16x32 form takes the products WITHOUT a prologue -- the Winograd-domain batches and the plain 1x1 layers / Linears: measured
-  // 1.02-1.08x the 32x32x16 form on the 128 x 256 tile, 1.0-1.07x on the 128-wide one (profiles/r06/split_mfma_ab.md). An MFMA of that
-  // shape holds the SIMD's vector issue for 8 of its 16 cycles, and the BatchNorm + ReLU prologue's ten more registers put the wide
-  // kernel into scratch inside the K-loop (0.96-0.99x): the prologue, implicit-GEMM and per-sample-affine kernels stay on the round-5
-  // form. MSS_GEMM_SPLIT_MFMA=32: that form everywhere (A/B, tests).
-  const int mf = MSS_ENV_INT("MSS_GEMM_SPLIT_MFMA", 16);
+int launch_split(const MssConvArgs& p, const FwdRoute& r, hipStream_t stream) {
   if constexpr (!CONV && !AFFINE)
-    if (mf != 32 && split_mf16_ok(p)) return launch_split_mf<AFFINE, BN, CONV, ROWAFF, 16>(p, stream);
+    if (r.mfma == 16) return launch_split_mf<AFFINE, BN, CONV, ROWAFF, 16>(p, stream);
   return launch_split_mf<AFFINE, BN, CONV, ROWAFF, 32>(p, stream);
+}
+template <bool CONV>
+int launch_split_tile(const MssConvArgs& p, const FwdRoute& r, hipStream_t stream) {
+  if (r.BN == 256) return r.affine ? launch_split<true, 256, CONV>(p, r, stream) : launch_split<false, 256, CONV>(p, r, stream);
+  return r.affine ? launch_split<true, 128, CONV>(p, r, stream) : launch_split<false, 128, CONV>(p, r, stream);
 }
 
 }  // namespace
 
 extern "C" int mss_gemm_split_last_mfma(void) { return split_last_mfma; }
 
-// Shapes the split route takes: what gemm_nt_kernel's 128- / 256-wide variant-3 kernels take (p.M, p.mtiles set by the caller) with
-// the weights' planes inside 32-bit byte offsets.
-bool mss_gemm_nt_bf16x3_eligible(const MssConvArgs& p) {
-  if (!p.w_split || p.K <= 64 || p.C / BK < 3 || p.Kpad % 128) return false;
-  const long long nb = p.batch > 1 ? p.batch : 1;
-  if (p.batch > 1 && p.w_bs != (long long)p.Kpad * p.C) return false;
-  if ((unsigned long long)p.M * p.ldx * 4ull >= 0xffffffffull) return false;             // per batch entry (the entries' bases are 64-bit)
-  if ((unsigned long long)nb * p.Kpad * p.C * 6ull >= 0xffffffffull) return false;
-  return (reinterpret_cast<uintptr_t>(p.w_split) & 15) == 0;
-}
-
-// Called by mss_gemm_nt_dispatch (gemm.hip) with p.H (rows per affine group), p.mtiles set; picks the tile width as the native
-// route does.
-int mss_gemm_nt_bf16x3_launch(MssConvArgs p, void* stream) {
+// The launches of fwd_route.h's FWD_GEMM_NT_BF16X3, FWD_CONV_BF16X3 and FWD_ROWAFF_BF16X3; p as fwd_fill_args left it.
+int mss_fwd_bf16x3_launch(MssConvArgs p, const FwdRoute& r, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const long long nb = p.batch > 1 ? p.batch : 1;
-  const long long tiles256 = (long long)p.mtiles * (p.K / 256) * nb;
-  bool wide = p.K % 256 == 0 && tiles256 >= 1024 && p.C >= 256;
-  if (wide) {
-    auto eff = [](long long total, long long slots) {
-      const long long rounds = (total + slots - 1) / slots;
-      return (double)total / (double)(rounds * slots);
-    };
-    const double ew = eff(tiles256, 512), en = eff(2 * tiles256, 768);
-    if (ew < 0.8 && en > ew + 0.15) wide = false;
-  }
-  if (wide) {
-    p.ntiles = p.K / 256;
-    return p.in_scale ? launch_split<true, 256>(p, s) : launch_split<false, 256>(p, s);
-  }
-  p.ntiles = mss_cdiv(p.K, 128);
-  return p.in_scale ? launch_split<true, 128>(p, s) : launch_split<false, 128>(p, s);
+  if (r.kernel == FWD_ROWAFF_BF16X3) return launch_split<true, 128, false, true>(p, r, s);
+  return r.kernel == FWD_CONV_BF16X3 ? launch_split_tile<true>(p, r, s) : launch_split_tile<false>(p, r, s);
 }
 
 
@@ -1206,48 +1170,6 @@ int mss_wgrad_tn_bf16x3_launch(const MssConvArgs& p, const float* dy, int lddy, 
 #undef TN_LAUNCH
   if (pl.splits > 1) mss_wgrad_reduce_launch(ws, dwp, slab / 4, pl.splits, s);
   return mss_launch_status();
-}
-
-static bool rowaff_eligible(const MssConvArgs& p);
-// The implicit-GEMM layers on the split route: what conv_igemm_kernel takes with > 64 output channels and ONE prologue affine
-bool mss_conv_bf16x3_eligible(const MssConvArgs& p) {
-  if (rowaff_eligible(p)) return true;
-  if (!p.w_split || p.K <= 64 || p.Kpad % 128 || p.C % BK || p.batch > 1 || p.res_mask) return false;
-  const int taps = p.R * p.S;
-  if ((p.S != 1 && p.S != 3) || taps > 9 || taps * (p.C / BK) < 3) return false;
-  if (taps == 1 && p.stride == 1 && p.pad == 0) return false;                       // a plain GEMM: the NT route takes it
-  if (p.in_scale && p.in_ss_stride) return false;                                   // per-sample affines (Dropout2d fold): native
-  if (p.in_relu && !p.in_scale) return false;
-  if ((unsigned long long)p.N * p.H * p.W * p.ldx * 4ull >= 0x7fffffffull) return false;   // signed 32-bit pixel offsets
-  if ((unsigned long long)taps * p.Kpad * p.C * 6ull >= 0xffffffffull) return false;
-  return (reinterpret_cast<uintptr_t>(p.w_split) & 15) == 0;
-}
-
-// 1x1 / stride-1 layers whose prologue affine is per sample while 128-row tiles straddle images ((OH * OW) % 128 != 0: mod6 / mod7's
-// last convolutions at 16 x 700 x 700) -- the one GEMM shape mss_gemm_nt_dispatch leaves to conv_igemm_kernel's PER_SAMPLE path
-static bool rowaff_eligible(const MssConvArgs& p) {
-  if (!p.w_split || p.R * p.S != 1 || p.stride != 1 || p.pad != 0 || p.H != p.OH || p.W != p.OW || p.batch > 1) return false;
-  if (!p.in_scale || !p.in_ss_stride || (p.OH * p.OW) % BM == 0 || p.K <= 64 || p.Kpad % 128 || p.C % BK || p.C / BK < 3) return false;
-  if ((unsigned long long)p.M * p.ldx * 4ull >= 0xffffffffull || (unsigned long long)p.Kpad * p.C * 6ull >= 0xffffffffull) return false;
-  return (reinterpret_cast<uintptr_t>(p.w_split) & 15) == 0;
-}
-
-int mss_conv_bf16x3_launch(MssConvArgs p, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  p.mtiles = mss_cdiv(p.M, BM);
-  if (rowaff_eligible(p)) {
-    p.H = p.OH * p.OW;                                   // rows per image
-    p.ntiles = mss_cdiv(p.K, 128);
-    return launch_split<true, 128, false, true>(p, s);
-  }
-  const long long tiles256 = (long long)p.mtiles * (p.K / 256);
-  const bool wide = p.K % 256 == 0 && tiles256 >= 1024;
-  if (wide) {
-    p.ntiles = p.K / 256;
-    return p.in_scale ? launch_split<true, 256, true>(p, s) : launch_split<false, 256, true>(p, s);
-  }
-  p.ntiles = mss_cdiv(p.K, 128);
-  return p.in_scale ? launch_split<true, 128, true>(p, s) : launch_split<false, 128, true>(p, s);
 }
 
 extern "C" long long mss_gemm_split_weights_bytes(int batch, int Kpad, int C) {

@@ -1,4 +1,4 @@
-// Round arithmetic of gemm_nt_kernel's dense launches (gemm.hip, mss_gemm_nt_dispatch): one text for the launch rule and a host test
+// Round arithmetic of gemm_nt_kernel's dense launches (gemm.hip; fwd_route.h asks it): one text for the launch rule and a host test
 // (tests/gemm_rounds_check.cpp).
 //
 // A product of mtiles row tiles (128 rows) and K output channels runs on 128 x 128 ("narrow", K / 128 column tiles, up to 3 workgroups
@@ -43,7 +43,7 @@ static inline MssGemmRounds mss_gemm_rounds(int mtiles, int K, int C, int batch,
   const long long full = (tiles256 / MSS_GEMM_WIDE_SLOTS) * MSS_GEMM_WIDE_SLOTS, rem = tiles256 - full;
   if (wide) {
     // the last wide round at most 3/4 full: always with MSS_GEMM_TAIL=1; by default for single-position products of at most four
-    // whole rounds, where the idle part of the last round is a visible share of the launch (gemm.hip has the measurements)
+    // whole rounds, where the idle part of the last round is a visible share of the launch (fwd_route.h, FwdSwitches::tail, has the measurements)
     const long long rem_max = tail_mode == 1 ? MSS_GEMM_TAIL_MAX : (tail_mode == -1 && batch <= 1 && full <= 4 * MSS_GEMM_WIDE_SLOTS) ? MSS_GEMM_TAIL_MAX : 0;
     r.mode = MSS_GEMM_WIDE;
     if (full > 0 && rem > 0 && rem <= rem_max) { r.mode = MSS_GEMM_HYBRID; r.full = full; r.rem = rem; }
@@ -57,6 +57,18 @@ static inline MssGemmRounds mss_gemm_rounds(int mtiles, int K, int C, int batch,
   }
   return r;
 }
+
+// The width rule alone (no hybrid): what the launches without a second kernel ask -- the k_imgs form of the per-image products and
+// the split-bf16 GEMM route (fwd_route.h).
+static inline bool mss_gemm_wide(int mtiles, int K, int C, int batch) { return mss_gemm_rounds(mtiles, K, C, batch, 0).mode == MSS_GEMM_WIDE; }
+
+// Two launches keep a rule of their own (unifying them would change which kernel their products get, and nothing is measured for that):
+// the one-batch per-image products (MssConvArgs.k_steps, k_imgs == 0) take the rule above WITHOUT its last-round fill test: the
+// per-image step counts make the rounds uneven anyway
+static inline bool mss_gemm_wide_perimg(int mtiles, int K, int C) { return K % 256 == 0 && (long long)mtiles * (K / 256) >= 2 * MSS_GEMM_WIDE_SLOTS && C >= 256; }
+// the implicit-GEMM layers of the split-bf16 route take the tile count ALONE, neither the fill test nor C >= 256: their reduction
+// is taps * C long (16 input channels of a 3x3 layer are 9 K-steps per tile), and the fill test was measured on the GEMM products only
+static inline bool mss_gemm_wide_split_conv(int mtiles, int K) { return K % 256 == 0 && (long long)mtiles * (K / 256) >= 2 * MSS_GEMM_WIDE_SLOTS; }
 
 // Workgroups of a launch of `total` tiles: every workgroup walks ceil(total / grid) tiles, so of the residencies per_cu_max and one
 // less the one whose last round is fuller, e.g. 4608 tiles = 6 full rounds of 768 but 4.5 rounds of 1024.

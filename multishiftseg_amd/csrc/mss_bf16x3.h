@@ -9,7 +9,7 @@ void mss_sched_init(hipStream_t stream);
 
 namespace mss_bf16x3 {
 
-constexpr int BK = 16;
+constexpr int BK = MSS_GEMM_BK;
 constexpr int ROW_B = BK * 2;                 // bytes per row per plane
 constexpr int PLANE = 128 * ROW_B;            // 4 KB: one plane of a 128-row operand block
 constexpr int OPER = 3 * PLANE;               // 12 KB: hi, mid, lo

@@ -6,9 +6,7 @@
 #include <stdlib.h>
 #include <atomic>
 
-#define MSS_OK 0
-#define MSS_ERR_BAD_ARG 1001     // a precondition of the C-ABI entry point was violated
-#define MSS_ERR_UNSUPPORTED 1002 // shape outside what the kernels are built for
+#include "mss_gemm_dims.h"       // MSS_OK / MSS_ERR_*, shared with host-only code
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -22,7 +22,6 @@
 #include "mss_common.h"
 #include "../../include/mss_hip.h"
 
-bool mss_stem7_eligible(const MssConvArgs& p);
 int mss_stem7_launch(MssConvArgs p, void* stream);
 
 namespace {
@@ -30,7 +29,8 @@ namespace {
 constexpr int S7_TH = 8, S7_TW = 32;                        // output pixels per workgroup
 constexpr int S7_PH = 2 * S7_TH + 5, S7_PW = 2 * S7_TW + 5; // input patch: 21 x 69 pixels
 constexpr int S7_HC = (S7_PW + 1) / 2;                      // 35 columns per parity
-constexpr int S7_TAPS = 49, S7_K = 64;
+constexpr int S7_TAPS = 49;
+static_assert(MSS_STEM7_K == 4 * 16, "four waves of 16 output channels each (fwd_route.h asks for K == MSS_STEM7_K)");
 
 __global__ __launch_bounds__(256, 2) void stem7_conv_kernel(MssConvArgs p, int tiles_x, int tiles_y) {
   __shared__ __attribute__((aligned(16))) float patch[S7_PH * 2 * S7_HC * 4];   // [row][column parity][column / 2][4 channels]
@@ -114,17 +114,7 @@ __global__ __launch_bounds__(256, 2) void stem7_conv_kernel(MssConvArgs p, int t
 
 }  // namespace
 
-// Exactly the shape the backbone's stem has; everything else keeps the answer mss_conv2d_forward_f32 gave before this route existed.
-bool mss_stem7_eligible(const MssConvArgs& p) {
-  if (p.R != 7 || p.S != 7 || p.stride != 2 || p.pad != 3 || p.dil != 1) return false;
-  if (p.C != 4 || p.ldx != 4 || p.K != S7_K || p.Kpad < S7_K || p.batch > 1) return false;
-  if (p.in_scale || p.in_shift || p.res || p.stats || p.w_split || p.k_steps) return false;
-  if (p.N < 0 || p.H <= 0 || p.W <= 0 || p.OH != (p.H - 1) / 2 + 1 || p.OW != (p.W - 1) / 2 + 1) return false;
-  if (p.ldy < S7_K || p.ldy % 4 || ((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.x)) & 15)) return false;
-  if (p.out_scale && !p.out_shift) return false;
-  return true;
-}
-
+// Which calls get here: mss_stem7_eligible (fwd_route.h).
 int mss_stem7_launch(MssConvArgs p, void* stream) {
   if (p.N == 0) return MSS_OK;
   const int tiles_x = mss_cdiv(p.OW, S7_TW), tiles_y = mss_cdiv(p.OH, S7_TH);

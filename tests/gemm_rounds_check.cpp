@@ -7,7 +7,10 @@
 //   plan mode tiles256 full rem grid_first grid_second
 // (the grids at 2 wide / 3 narrow workgroups per CU on 256 CUs; grid_second 0 without a second launch) and exits non-zero with a
 // message at the first violated property.
+// `gemm_rounds_check width` reads `mtiles K C batch` per line and prints the three width rules: `wide wide_perimg wide_split_conv`
+// (tests/test_fwd_route_cpu.py).
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "gemm_rounds.h"
@@ -22,9 +25,14 @@
     }                                                      \
   } while (0)
 
-int main() {
+int main(int argc, char** argv) {
   int line = 0;
   int mtiles, K, C, batch, tail_mode;
+  if (argc == 2 && !std::strcmp(argv[1], "width")) {
+    while (std::scanf("%d %d %d %d", &mtiles, &K, &C, &batch) == 4)
+      std::printf("%d %d %d\n", (int)mss_gemm_wide(mtiles, K, C, batch), (int)mss_gemm_wide_perimg(mtiles, K, C), (int)mss_gemm_wide_split_conv(mtiles, K));
+    return 0;
+  }
   while (std::scanf("%d %d %d %d %d", &mtiles, &K, &C, &batch, &tail_mode) == 5) {
     ++line;
     const MssGemmRounds r = mss_gemm_rounds(mtiles, K, C, batch, tail_mode);

@@ -510,7 +510,7 @@ def test_bf16x3_gemm_is_fp32_accurate(K, rows, c, k, batch):
     (700, 512, 192, 1, 200, 8)])       # padded column tile (192 of 256) inside an aligned window
 def test_bf16x3_gemm_into_an_output_window(K, rows, c, k, batch, pitch, lead):
     """The 16x16x32 split kernels store 16 bytes per lane and are taken only when the output's start, pitch and batch stride sit on the
-    16-byte grid (split_mf16_ok, gemm_bf16x3.hip); everything else goes to the 32x32x16 kernels' 4-byte stores. Both ways the product
+    16-byte grid (split_mf16_ok, fwd_route.h); everything else goes to the 32x32x16 kernels' 4-byte stores. Both ways the product
     lands in a WINDOW of a larger buffer: the window against float64 and against the native route, the rest of the buffer untouched."""
     from multishiftseg_amd import _lib
     torch.manual_seed(rows + k)
