@@ -10,6 +10,9 @@
  *     callers of this ABI must raise on non-zero.
  *   - activations inside the DeepLab path are NHWC fp32 with an explicit pixel stride (`ld*`,
  *     in floats) so that kernels read/write channel slices of concat buffers in place.
+ *   - a process may drive several devices; what a launcher needs to know about a device (occupancy, CU count, a raised
+ *     dynamic-LDS limit) is kept per device for indices 0..15. Every launcher that asks answers MSS_ERR_UNSUPPORTED when the
+ *     current device has another index.
  *
  * Each entry point cites the reference interface it replaces (paths relative to the reference root).
  */

@@ -274,12 +274,8 @@ __global__ __launch_bounds__(NT) void conv_igemm_kernel(MssConvArgs p) {
 template <int BM, int BN, int BK, int WM, int WN, bool PS, bool AFF>
 int launch_conv_t(const MssConvArgs& p, hipStream_t stream) {
   const size_t smem = ((size_t)2 * (BM + BN) * (BK + 4) + 4) * sizeof(float);
-  auto kern = conv_igemm_kernel<BM, BN, BK, WM, WN, PS, AFF>;
-  if (smem > 65536) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  constexpr auto kern = conv_igemm_kernel<BM, BN, BK, WM, WN, PS, AFF>;
+  if (int rc = mss_kernel_info<kern>(NT, smem)) return rc;         // raises the limit for the 128x128x32 tile's 73,744 bytes
   hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles, p.batch > 1 ? p.batch : 1), dim3(NT), smem, stream, p);
   return mss_launch_status();
 }

@@ -1037,15 +1037,9 @@ int launch_wgrad_tn_lds(const WgradRoute& r, const MssConvArgs& p, const float* 
   const bool wide = r.kernel == WG_TN_WIDE;
   const long long a_bs = p.batch > 1 ? p.y_bs : 0, b_bs = p.batch > 1 ? p.x_bs : 0;
   const size_t smem = (size_t)4 * TN_BT * TN_LD * sizeof(float);
-  static int per_cu = 0, cus = 256;
-  if (per_cu == 0) {
-    int dev = 0, n = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_tn_wgrad_kernel, NT, smem) != hipSuccess || n < 1) n = 3;
-    per_cu = n > 3 ? 3 : n;
-  }
-  const long long slots = (long long)(wide ? 2 : per_cu) * cus;
+  MssKernelInfo ki;
+  if (int rc = mss_kernel_info<gemm_tn_wgrad_kernel>(NT, smem, 3, &ki)) return rc;
+  const long long slots = (long long)(wide ? 2 : ki.occ > 3 ? 3 : ki.occ) * ki.cus;
   const int grid = (int)(r.total < slots ? r.total : slots);
   float* out = r.splits > 1 ? ws : dwp;
   if (wide) {

@@ -317,15 +317,10 @@ int launch_gemm(const MssConvArgs& p, hipStream_t stream, long long first = 0, l
   const long long total = end - first;                 // tiles of this launch
   if (total <= 0) return MSS_OK;
   const size_t smem = (size_t)2 * (BM + BN) * LDK * sizeof(float);
-  static int per_cu_max = 0, cus = 256;  // resident workgroups per CU (BN = 128: 4 with 32 KB LDS and <= 128 registers); one static per instantiation
-  if (per_cu_max == 0) {
-    int dev = 0, n = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_nt_kernel<AFFINE, VARIANT, BN, PERIMG>, NT, smem) != hipSuccess || n < 1) n = 3;
-    per_cu_max = n;
-  }
-  const int grid = mss_gemm_grid(total, per_cu_max, cus);   // gemm_rounds.h: the residency whose last round is fuller
+  MssKernelInfo ki;                      // resident workgroups per CU (BN = 128: 4 with 32 KB LDS and <= 128 registers)
+  if (int rc = mss_kernel_info<gemm_nt_kernel<AFFINE, VARIANT, BN, PERIMG>>(NT, smem, 3, &ki)) return rc;
+  // gemm_rounds.h: the residency whose last round is fuller by 2 % (r06: re-measured, 36 x 4096 x 512 -> 512 at one per CU 133.5 vs 125 TFLOP/s forced to two; the split kernel differs)
+  const int grid = mss_gemm_grid(total, ki.occ, ki.cus, 0.02);
   // the square-ish tile order only for whole launches: the hybrid wide + narrow split (MSS_GEMM_TAIL) relies on tile ranges
   const int group_m = (first == 0 && end == (long long)tiles_per_batch * batch) ? MSS_ENV_INT("MSS_GEMM_GROUP_M", GEMM_GROUP_M_DEFAULT) : 0;
   hipLaunchKernelGGL((gemm_nt_kernel<AFFINE, VARIANT, BN, PERIMG>), dim3(grid), dim3(NT), smem, stream, p, first, end, tiles_per_batch, group_m);

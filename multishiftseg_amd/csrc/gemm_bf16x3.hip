@@ -24,9 +24,6 @@
 #include "wgrad_route.h"
 #include "fwd_route.h"
 #include <stdlib.h>
-#include <mutex>
-#include <unordered_map>
-#include <utility>
 
 #ifdef MSS_SPLIT_STAMPS
 // DIAGNOSTIC BUILD ONLY (never in libmss_hip.so as shipped): per workgroup-wave the summed s_memtime deltas of the K-step's eight
@@ -39,72 +36,6 @@ extern "C" int mss_debug_read_stamps(unsigned long long* host, int n) {
 #else
 #define MSS_STAMP(i)
 #endif
-
-// Dynamic tile scheduling of the persistent kernels (round 5): self-resetting counter slots in device memory (eight per-XCD ticket
-// counters + a count of finished workgroups, draw_xcd_ticket; every launch zeroes its slot when its last workgroup leaves).
-// A slot may only be shared by launches that cannot overlap. Ownership (round 6, ADVICE r05 / VERDICT r05 weak 9):
-//  * EAGER launches: every stream has its own ring of 8 slots, used in rotation (launches on a stream run in order);
-//  * launches recorded by a STREAM CAPTURE: the slot address is baked into the graph and the graph may later be replayed on any
-//    stream, beside other graphs and beside eager launches of the stream it was captured on -- so each captured launch gets a PRIVATE
-//    slot out of a region no eager launch ever uses, never handed out twice (a graph exec cannot overlap itself, so its own
-//    replays are ordered). 8192 such slots per device; when they are used up -- or when the pool does not exist yet and the first
-//    launch on the device happens under capture, where nothing may be allocated -- the launcher falls back to the static tile walk
-//    (nullptr here: correct, a few percent slower on the prologue kernels).
-// The pool (64 rings x 8 + 8192 slots of 64 bytes = 544 KB) is allocated and cleared by mss_sched_init, which the weight-plane packers
-// call (a split launch needs planes, so the pool exists before the first launch unless the packing itself was captured), or lazily by
-// the first eager launch. A process with more than 64 streams that launch these kernels gets the static walk on the later ones.
-// A launch that FAULTS leaves its slot dirty; a device fault is sticky in HIP (every later call on the context fails), so there is no
-// later launch to protect.
-namespace {
-constexpr int SCHED_RINGS = 64, SCHED_PAIRS = 8, SCHED_MAXDEV = 16, SCHED_SLOT = 16, SCHED_GRAPH_SLOTS = 8192;   // a slot: 16 ints (64 B)
-std::mutex sched_mu;
-int* sched_pools[SCHED_MAXDEV] = {nullptr};                                           // one pool per device of this process
-int sched_graph_used[SCHED_MAXDEV] = {0};
-std::unordered_map<hipStream_t, std::pair<int, unsigned>> sched_rings[SCHED_MAXDEV];  // stream -> (ring index, launches so far)
-
-bool sched_pool_locked(int dev) {                  // sched_mu held; false: no pool and none can be made right now
-  if (sched_pools[dev]) return true;
-  const size_t bytes = ((size_t)SCHED_RINGS * SCHED_PAIRS + SCHED_GRAPH_SLOTS) * SCHED_SLOT * sizeof(int);
-  int* q = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&q), bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (hipMemset(q, 0, bytes) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(q); return false; }
-  sched_pools[dev] = q;
-  return true;
-}
-bool stream_is_capturing(hipStream_t stream) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return st != hipStreamCaptureStatusNone;
-}
-}  // namespace
-
-// Allocate the ticket pool of the current device now (not under a capture). Idempotent.
-void mss_sched_init(hipStream_t stream) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SCHED_MAXDEV || stream_is_capturing(stream)) return;
-  std::lock_guard<std::mutex> lock(sched_mu);
-  (void)sched_pool_locked(dev);
-}
-
-// nullptr: use the static tile walk for this launch
-int* mss_sched_slot(hipStream_t stream) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SCHED_MAXDEV) return nullptr;
-  const bool capturing = stream_is_capturing(stream);
-  std::lock_guard<std::mutex> lock(sched_mu);
-  if (!sched_pools[dev] && (capturing || !sched_pool_locked(dev))) return nullptr;
-  if (capturing) {
-    if (sched_graph_used[dev] >= SCHED_GRAPH_SLOTS) return nullptr;
-    return sched_pools[dev] + ((size_t)SCHED_RINGS * SCHED_PAIRS + sched_graph_used[dev]++) * SCHED_SLOT;
-  }
-  auto& map = sched_rings[dev];
-  auto it = map.find(stream);
-  if (it == map.end()) {
-    if ((int)map.size() >= SCHED_RINGS) return nullptr;
-    it = map.emplace(stream, std::make_pair((int)map.size(), 0u)).first;
-  }
-  return sched_pools[dev] + ((size_t)it->second.first * SCHED_PAIRS + it->second.second++ % SCHED_PAIRS) * SCHED_SLOT;
-}
 
 namespace {
 
@@ -993,29 +924,6 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
 template <bool AFFINE, int BN, bool CONV, bool ROWAFF>
 constexpr bool split_dyn_tiles() { return AFFINE && !CONV && !ROWAFF; }
 
-// occupancy / CU count / the raised dynamic-LDS limit of one kernel instantiation, PER DEVICE (function attributes are per device; a
-// process may drive several): filled on the first launch on that device under a mutex
-struct SplitDevInfo { int occ = 0, cus = 256; };
-template <typename KernelT>
-int split_dev_info(KernelT kern, size_t smem, int fallback_occ, SplitDevInfo (&info)[SCHED_MAXDEV], std::mutex& mu, SplitDevInfo& out) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SCHED_MAXDEV) return MSS_ERR_UNSUPPORTED;
-  std::lock_guard<std::mutex> lock(mu);
-  if (info[dev].occ == 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) info[dev].cus = prop.multiProcessorCount;
-    if (smem > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return (int)e;
-    }
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, NT, smem) != hipSuccess || n < 1) n = fallback_occ;
-    info[dev].occ = n;
-  }
-  out = info[dev];
-  return MSS_OK;
-}
-
 template <bool AFFINE, int BN, bool CONV, bool ROWAFF, bool DYN, int MF>
 int launch_split_as(const MssConvArgs& p, hipStream_t stream, int* sched) {
   const int batch = p.batch > 1 ? p.batch : 1;
@@ -1023,24 +931,11 @@ int launch_split_as(const MssConvArgs& p, hipStream_t stream, int* sched) {
   const long long total = (long long)tiles_per_batch * batch;
   if (total <= 0) return MSS_OK;
   const size_t smem = (size_t)2 * (1 + BN / 128) * OPER + 16;          // + the two ticket words of the dynamic tile order
-  static SplitDevInfo info[SCHED_MAXDEV];
-  static std::mutex mu;
-  SplitDevInfo di;
-  const int rc = split_dev_info(gemm_nt_bf16x3_kernel<AFFINE, BN, CONV, ROWAFF, DYN, MF>, smem, BN == 256 ? 2 : 3, info, mu, di);
-  if (rc != MSS_OK) return rc;
-  int per_cu_max = di.occ;
-  // residency (per_cu_max or one less) whose last round of tiles is fuller, as launch_gemm (gemm.hip)
-  int grid = 0;
-  double best = -1.0;
-  // (round 6: only when that saves more than 15 % of the rounds' slots -- one workgroup per CU leaves a single wave on each SIMD, which
-  // keeps the matrix pipe 52-58 % busy against 72-79 % with two; 36 x 4096 x 512 -> 512, 2304 tiles: 192 -> 204 TFLOP/s at two per CU)
-  for (int per_cu = per_cu_max; per_cu >= (per_cu_max > 1 ? per_cu_max - 1 : 1); --per_cu) {
-    const long long slots = (long long)per_cu * di.cus;
-    const long long g = total < slots ? total : slots;
-    const long long rounds = (total + g - 1) / g;
-    const double eff = (double)total / (double)(rounds * g);
-    if (eff > best + (per_cu == per_cu_max ? 0.0 : 0.15)) { best = eff; grid = (int)g; }
-  }
+  MssKernelInfo di;
+  if (int rc = mss_kernel_info<gemm_nt_bf16x3_kernel<AFFINE, BN, CONV, ROWAFF, DYN, MF>>(NT, smem, BN == 256 ? 2 : 3, &di)) return rc;
+  // one workgroup less per CU only when that fills 15 % more of the rounds' slots (round 6): one per CU leaves a single wave on each SIMD, which
+  // keeps the matrix pipe 52-58 % busy against 72-79 % with two; 36 x 4096 x 512 -> 512, 2304 tiles: 192 -> 204 TFLOP/s at two per CU
+  const int grid = mss_gemm_grid(total, di.occ, di.cus, 0.15);
   const int group_m = MSS_ENV_INT("MSS_GEMM_GROUP_M", GEMM_GROUP_M_DEFAULT);
   const unsigned blk_bytes = (unsigned)(p.C / BK) * (CONV ? p.R * p.S : 1) * OPER;     // CONV: the taps are part of one long reduction
   hipLaunchKernelGGL((gemm_nt_bf16x3_kernel<AFFINE, BN, CONV, ROWAFF, DYN, MF>), dim3(grid), dim3(NT), smem, stream, p,
@@ -1141,20 +1036,10 @@ int mss_wgrad_tn_bf16x3_launch(const MssConvArgs& p, const float* dy, int lddy, 
   if (pl.splits > 1 && (!ws || ws_bytes < (long long)pl.splits * slab * 4)) return MSS_ERR_BAD_ARG;
   float* out = pl.splits > 1 ? ws : dwp;
   const size_t smem = (size_t)2 * 3 * OPER + 16;
-  static bool attr[SCHED_MAXDEV] = {false};                           // function attributes are per device
-  static std::mutex attr_mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SCHED_MAXDEV) return MSS_ERR_UNSUPPORTED;
-  std::lock_guard<std::mutex> attr_lock(attr_mu);
-  if (!attr[dev]) {
-    const void* ks[4] = {reinterpret_cast<const void*>(gemm_tn_bf16x3_kernel<false, false>), reinterpret_cast<const void*>(gemm_tn_bf16x3_kernel<false, true>),
-                         reinterpret_cast<const void*>(gemm_tn_bf16x3_kernel<true, false>), reinterpret_cast<const void*>(gemm_tn_bf16x3_kernel<true, true>)};
-    for (const void* kf : ks) {
-      hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return (int)e;
-    }
-    attr[dev] = true;
-  }
+  if (int rc = mss_kernel_info<gemm_tn_bf16x3_kernel<false, false>>(NT, smem)) return rc;      // all four before the first launch on a device
+  if (int rc = mss_kernel_info<gemm_tn_bf16x3_kernel<false, true>>(NT, smem)) return rc;
+  if (int rc = mss_kernel_info<gemm_tn_bf16x3_kernel<true, false>>(NT, smem)) return rc;
+  if (int rc = mss_kernel_info<gemm_tn_bf16x3_kernel<true, true>>(NT, smem)) return rc;
   const long long slots = 512;
   const int grid = (int)(pl.total < slots ? pl.total : slots);
   const long long a_bs = p.batch > 1 ? p.y_bs : 0, b_bs = p.batch > 1 ? p.x_bs : 0;

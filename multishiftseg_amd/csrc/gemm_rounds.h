@@ -71,15 +71,15 @@ static inline bool mss_gemm_wide_perimg(int mtiles, int K, int C) { return K % 2
 static inline bool mss_gemm_wide_split_conv(int mtiles, int K) { return K % 256 == 0 && (long long)mtiles * (K / 256) >= 2 * MSS_GEMM_WIDE_SLOTS; }
 
 // Workgroups of a launch of `total` tiles: every workgroup walks ceil(total / grid) tiles, so of the residencies per_cu_max and one
-// less the one whose last round is fuller, e.g. 4608 tiles = 6 full rounds of 768 but 4.5 rounds of 1024.
-static inline int mss_gemm_grid(long long total, int per_cu_max, int cus) {
+// less the one whose last round is fuller by more than `margin` (the caller's measurement), e.g. 4608 tiles = 6 full rounds of 768 but 4.5 of 1024.
+static inline int mss_gemm_grid(long long total, int per_cu_max, int cus, double margin) {
   int grid = 0;
   double best = -1.0;
   for (int per_cu = per_cu_max; per_cu >= (per_cu_max > 1 ? per_cu_max - 1 : 1); --per_cu) {
     const long long slots = (long long)per_cu * cus;
     const long long g = total < slots ? total : slots;
     const double eff = mss_gemm_round_fill(total, g);
-    if (eff > best + 0.02) { best = eff; grid = (int)g; }     // (r06: re-measured, 36 x 4096 x 512 -> 512 at one per CU 133.5 vs 125 TFLOP/s forced to two; the split kernel differs)
+    if (eff > best + margin) { best = eff; grid = (int)g; }
   }
   return grid;
 }

@@ -1067,9 +1067,8 @@ static int msda_backward_binned(const float* value, const int64_t* shapes, const
   hipLaunchKernelGGL(msda_bin_kernel<1>, dim3(chunks, (unsigned)N), dim3(MSDA_BIN_NT), hist_bytes, stream, g, loc, attn, M, Lq, P,
                      cursor, records, absmax + 1, gout, 0ll);       // + max|attn| over the filed samples
   const size_t win_bytes = (size_t)MSDA_BIN_WIN * 32 * sizeof(unsigned long long);
-  auto kern = msda_bwd_value_binned_kernel<8>;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_bytes);
-  if (e != hipSuccess) return (int)e;
+  constexpr auto kern = msda_bwd_value_binned_kernel<8>;
+  if ((rc = mss_kernel_info<kern>(MSDA_BIN_NT, win_bytes)) != MSS_OK) return rc;
   const long long nitems = (long long)g.ntiles * N * M;
   const unsigned nwg = (unsigned)(nitems < 512 ? nitems : 512);          // two 1024-thread workgroups per CU, 256 CUs
   hipLaunchKernelGGL(kern, dim3(nwg), dim3(MSDA_BIN_NT), win_bytes, stream, g, starts, gout, absmax, records, offsets, ticket, S, M,

@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "mss_gemm_dims.h"       // MSS_OK / MSS_ERR_*, shared with host-only code
+#include "mss_device.h"          // what a launcher asks about its device: mss_kernel_info
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

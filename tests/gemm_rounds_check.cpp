@@ -28,6 +28,10 @@
 int main(int argc, char** argv) {
   int line = 0;
   int mtiles, K, C, batch, tail_mode;
+  // the split-bf16 launcher's margin (gemm_bf16x3.hip) on its documented case: 2304 tiles at 2 workgroups per CU on 256 CUs are 4.5
+  // rounds of 512 or 9 whole rounds of 256 -- 10 % more of the slots filled, which 0.15 leaves at two per CU and gemm.hip's 0.02 does not
+  CHECK(mss_gemm_grid(2304, 2, 256, 0.15) == 512 && mss_gemm_grid(2304, 2, 256, 0.02) == 256, "grids %d %d",
+        mss_gemm_grid(2304, 2, 256, 0.15), mss_gemm_grid(2304, 2, 256, 0.02));
   if (argc == 2 && !std::strcmp(argv[1], "width")) {
     while (std::scanf("%d %d %d %d", &mtiles, &K, &C, &batch) == 4)
       std::printf("%d %d %d\n", (int)mss_gemm_wide(mtiles, K, C, batch), (int)mss_gemm_wide_perimg(mtiles, K, C), (int)mss_gemm_wide_split_conv(mtiles, K));
@@ -61,8 +65,8 @@ int main(int argc, char** argv) {
       first = wide_end;
     }
     for (long long t = 0; t < narrow; ++t) CHECK(hits[t] == 1, "narrow tile %lld covered %d times", t, hits[t]);
-    const int g1 = mss_gemm_grid(first, r.mode == MSS_GEMM_NARROW ? 3 : 2, 256);
-    const int g2 = second ? mss_gemm_grid(second, 3, 256) : 0;
+    const int g1 = mss_gemm_grid(first, r.mode == MSS_GEMM_NARROW ? 3 : 2, 256, 0.02);      // gemm.hip's margin
+    const int g2 = second ? mss_gemm_grid(second, 3, 256, 0.02) : 0;
     CHECK(g1 >= 1 && g1 <= first && g1 <= 768 && (second == 0 || (g2 >= 1 && g2 <= second && g2 <= 768)), "grids %d %d", g1, g2);
     std::printf("plan %d %lld %lld %lld %d %d\n", r.mode, r.tiles256, r.full, r.rem, g1, g2);
   }
