@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MSS_ABI_VERSION 25     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
+#define MSS_ABI_VERSION 26     /* 2: round-2 struct / workspace changes; 3: mss_msda_backward_binned_f32; 4: mss_add_layernorm_bwd_sum_f32, mss_stem_conv_pool_f32,
                                   mss_wino_input_transform_bnbwd_f32, mss_wino_input_transform_upcat_f32,
                                   mss_bn_fold_train_from_partials_f32; 5 (round 4): mss_adam_step_f32 takes double hyper-parameters, mss_env_reset,
                                   mss_wino_input_transform_aspp3_f32, mss_msda_prepare_backward_ld_f32, mss_rcl_pairs_device2_f32, mss_rcl_loss_device_f32, mss_m2f_fused_score_ws_f32, mss_oodm_compact_packed_f32,
@@ -64,7 +64,9 @@ extern "C" {
                                   backbone (csrc/stem7.hip), which it answered MSS_ERR_UNSUPPORTED before; mss_conv2d_forward_route labels it 5;
                                   25: no entry point or struct changes; mss_conv2d_forward_f32 takes MssConvArgs.stride == -2, the data gradient of a
                                   stride-2 convolution (csrc/conv_dgrad_s2.hip; no caller passed a negative stride before);
-                                  mss_conv2d_forward_route labels it 6 */
+                                  mss_conv2d_forward_route labels it 6;
+                                  26 (additive): mss_conv2d_wgrad_plan, MssWgradPlan and the MSS_WG_* kernel names (what a weight-gradient call
+                                  launches: kernel, splits, reducer), host-only */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -288,6 +290,10 @@ int mss_gemm_split_last_mfma(void);
 int mss_conv2d_pack_weights_f32(const float* w, float* packed, int K, int C, int R, int S, int Kpad, int Cp,
                                 int flip, const int* col, int n_img, int c0, void* stream);
 /* weight gradient: dwp[tap][k][c] = sum_m dy[m][k]*act(x[m@tap][c]); dwp [taps][Kpad][Cp] is fully overwritten.
+ * Kpad and Cp may pad K and C up to the end of the last output tile of the kernel that runs: at least to the next multiple of 32
+ * rows for K <= 32, of 64 for K <= 64, else of 128, and to the next multiple of 128 columns (so none where K or C is such a
+ * multiple already; rounding up to a multiple of 4 always fits). Padding beyond that tile no kernel would write:
+ * MSS_ERR_UNSUPPORTED (mss_conv2d_wgrad_plan answers the same without launching).
  * Deterministic (no atomics; pixel-range partials are summed in a fixed order: the reference pins
  * cudnn.deterministic, lib/utils/utils.py:10-13). ws: scratch of mss_conv2d_wgrad_workspace_bytes(args, Cp) bytes
  * (NULL allowed when that is 0). Replaces the autograd wgrad of nn.Conv2d for aspp/bot_aspp/bot_fine/ood_head
@@ -308,6 +314,41 @@ int mss_conv2d_unpack_wgrad_f32(const float* packed, float* grad, int K, int C, 
 /* 1 when mss_conv2d_wgrad_f32 runs these arguments on the split-bf16 TN kernel (args->route == 1, K % 128 == 0, C % 256 == 0, enough
  * tiles to fill half the chip), else 0 (native fp32 MFMA kernels). Profiling label only. */
 int mss_conv2d_wgrad_route(const MssConvArgs* args, int lddy);
+/* What a mss_conv2d_wgrad_f32 call with these arguments launches (csrc/wgrad_route.h): the launch's own decision, read
+ * through the same helper, so the two cannot disagree. Pure host arithmetic: no HIP call, and no pointer is dereferenced -- args->x,
+ * in_scale, in_shift, k_steps, dy and dwp are compared with NULL and their alignment is read, as the launch does. ws_bytes: the
+ * scratch the launch would be given; it decides one thing only, whether the split-bf16 kernel is skipped because the scratch is too
+ * small for it (a scratch too small for the kernel that then runs is the launch's MSS_ERR_BAD_ARG, not this query's: out->ws_bytes
+ * says what is needed). part: 0 = the product as given; for a MSS_WG_TWO_PART product 1 and 2 = its two parts (the first wide_K
+ * output channels, then the rest); MSS_ERR_BAD_ARG for part 1 or 2 of any other product and for any other value.
+ * Returns what mss_conv2d_wgrad_f32 returns from its argument checks; *out is written only on MSS_OK (0). A call without output
+ * pixels (N * OH * OW <= 0) launches nothing: MSS_OK with every field 0 except kernel = -1. */
+#define MSS_WG_CONV_32 0            /* conv_wgrad_kernel<32, 128, 16>: K <= 32                                             */
+#define MSS_WG_CONV_64 1            /* conv_wgrad_kernel<64, 128, 16>: K <= 64                                             */
+#define MSS_WG_CONV_128 2           /* conv_wgrad_kernel<128, 128, 16>                                                     */
+#define MSS_WG_NARROW 3             /* gemm_tn_narrow_kernel                                                               */
+#define MSS_WG_TN_LDS 4             /* gemm_tn_wgrad_kernel                                                                */
+#define MSS_WG_TN_WIDE 5            /* gemm_tn2_wgrad_kernel                                                               */
+#define MSS_WG_TN_DIRECT 6          /* gemm_tn_direct_kernel, whole tiles or row splits of every tile                      */
+#define MSS_WG_TN_DIRECT_TAIL 7     /* gemm_tn_direct_kernel with the tail plan + tn_tail_reduce_kernel                    */
+#define MSS_WG_TN_DIRECT_PERIMG 8   /* gemm_tn_direct_kernel, per-image form (MssConvArgs.k_steps)                         */
+#define MSS_WG_TN_BF16X3 9          /* the split-bf16 TN kernel (args->route == 1)                                         */
+#define MSS_WG_TWO_PART 10          /* K = 128 j + r: two launches, see `part`                                             */
+typedef struct MssWgradPlan {
+  int kernel;                /* MSS_WG_*                                                                                      */
+  int ktiles, ctiles;        /* output tiles along K and C                                                                    */
+  int positions;             /* independent products of the launch: filter taps, or the batch                                 */
+  int splits;                /* row ranges; > 1: partial slabs in the scratch, added in ascending order by a reduce launch    */
+  int rows_per_split;
+  long long total;           /* jobs (workgroups or waves) of the launch                                                      */
+  long long full;            /* MSS_WG_TN_DIRECT_TAIL: whole-tile jobs in front of the split ones; else -1                    */
+  long long ws_bytes;        /* scratch the launch needs                                                                      */
+  int wide_K;                /* MSS_WG_TWO_PART: output channels of the first part; else 0                                    */
+  int reduce_group;          /* threads that share an output element in the reduce launch: 1 = wgrad_reduce_kernel, 2..32 =   */
+                             /*   wgrad_reduce_par_kernel<G>; 0 = no such launch (one split, or a kernel with its own reducer) */
+} MssWgradPlan;
+int mss_conv2d_wgrad_plan(const MssConvArgs* args, const float* dy, int lddy, const float* dwp, int Cp, long long ws_bytes, int part,
+                          MssWgradPlan* out);
 
 /* Winograd F(m x m, 3x3) path, m = `tile` = 2 or 4, P = (m+2)^2 positions, for stride-1 3x3 convolutions with
  * many channels (csrc/winograd.hip): weights [K][C][3][3] -> U [P][Kpad][Cp]; x -> X' [P][T][C]

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so libmss_hip.
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSS_LIB", os.path.join(_HERE, "libmss_hip.so"))   # MSS_LIB: A/B experiments only
 
-MSS_ABI_VERSION = 25         # include/mss_hip.h
+MSS_ABI_VERSION = 26         # include/mss_hip.h
 MSS_WGRAD_PERIMG_TAIL_BYTES = 1024 * 128 * 128 * 4     # include/mss_hip.h: optional scratch of the per-image weight gradient
 MSS_ERR_BAD_ARG = 1001
 MSS_ERR_UNSUPPORTED = 1002
@@ -73,6 +73,16 @@ class MssConvArgs(Structure):
     ]
 
 
+# include/mss_hip.h MSS_WG_*: MssWgradPlan.kernel -> name
+MSS_WG_NAMES = ("conv32", "conv64", "conv128", "narrow", "tn_lds", "tn_wide", "tn_direct", "tn_direct_tail", "tn_direct_perimg", "tn_bf16x3", "two_part")
+
+
+class MssWgradPlan(Structure):
+    """include/mss_hip.h: what mss_conv2d_wgrad_plan answers -- the kernel, grid, splits, scratch and reducer of a weight-gradient call."""
+    _fields_ = [("kernel", c_int), ("ktiles", c_int), ("ctiles", c_int), ("positions", c_int), ("splits", c_int), ("rows_per_split", c_int),
+                ("total", c_longlong), ("full", c_longlong), ("ws_bytes", c_longlong), ("wide_K", c_int), ("reduce_group", c_int)]
+
+
 class MssRclArgs(Structure):
     _fields_ = [
         ("logit", c_void_p), ("score", c_void_p), ("target", c_void_p),
@@ -121,6 +131,7 @@ SIGNATURES = {
     "mss_conv2d_wgrad_workspace_bytes": [POINTER(MssConvArgs), I],
     "mss_conv2d_wgrad_f32": [POINTER(MssConvArgs), P, I, P, I, P, L, P],
     "mss_conv2d_wgrad_route": [POINTER(MssConvArgs), I],
+    "mss_conv2d_wgrad_plan": [POINTER(MssConvArgs), P, I, P, I, L, I, POINTER(MssWgradPlan)],
     "mss_conv2d_unpack_wgrad_f32": [P, P, I, I, I, I, I, I, I, P, P, I, I, P],
     "mss_nchw_to_nhwc_pad_f32": [P, P, I, I, I, I, I, P],
     "mss_im2col3x3_c3_f32": [P, P, I, I, I, P],
@@ -236,7 +247,7 @@ SIGNATURES = {
 # the entry points that return a plain value, and its C type; every other one returns an int status code
 VALUE_RESTYPE = {
     "mss_abi_version": c_int, "mss_env_reset": c_int, "mss_msda_backward_workspace_bytes": c_longlong, "mss_chan_compact_wanted": c_int, "mss_conv2d_kpad": c_int,
-    "mss_conv2d_forward_route": c_int, "mss_gemm_split_last_mfma": c_int, "mss_gemm_split_weights_bytes": c_longlong, "mss_conv2d_wgrad_workspace_bytes": c_longlong, "mss_conv2d_wgrad_route": c_int,
+    "mss_conv2d_forward_route": c_int, "mss_gemm_split_last_mfma": c_int, "mss_gemm_split_weights_bytes": c_longlong, "mss_conv2d_wgrad_workspace_bytes": c_longlong, "mss_conv2d_wgrad_route": c_int, "mss_conv2d_wgrad_plan": c_int,
     "mss_col_reduce_accum_doubles": c_longlong, "mss_colsum_workspace_floats": c_longlong, "mss_rcl_num_compact_blocks": c_int, "mss_rcl_workspace_bytes": c_longlong, "mss_adamw_chunk_elems": c_int,
     "mss_adamw_tensors_per_launch": c_int, "mss_adamw_blocks_per_launch": c_int, "mss_adamw_scratch_floats": c_longlong, "mss_adamw_plan": c_longlong, "mss_wino_num_tiles": c_longlong,
     "mss_wino_output_stats_parts": c_int, "mss_wino_aspp3_supported": c_int, "mss_m2f_attn_workspace_bytes": c_longlong, "mss_m2f_attn_bwd_workspace_bytes": c_longlong, "mss_m2f_match_workspace_bytes": c_longlong,

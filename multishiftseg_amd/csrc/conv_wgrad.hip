@@ -1,5 +1,5 @@
 // Weight gradient of the convolutions and Linears on the fp32 matrix cores of MI355X: the kernels, one launcher per kernel and the
-// three C entry points. Which kernel a product gets, its grid, splits and scratch are decided in wgrad_route.h (plain host C++,
+// four C entry points. Which kernel a product gets, its grid, splits and scratch are decided in wgrad_route.h (plain host C++,
 // checked alone by tests/wgrad_route_check.cpp); nothing here recomputes a plan.
 #include "mss_epilogue.h"
 #include "wgrad_route.h"
@@ -8,6 +8,7 @@ static_assert(MSS_WGRAD_PERIMG_TAIL_BYTES == (long long)TN_PERIMG_MAX_SLOTS * 12
 
 bool mss_wgrad_tn_bf16x3_eligible(const MssConvArgs& p, int lddy);   // gemm_bf16x3.hip
 long long mss_wgrad_tn_bf16x3_ws_bytes(const MssConvArgs& p, int Cp);
+void mss_wgrad_tn_bf16x3_plan(const MssConvArgs& p, WgradRoute& r);
 int mss_wgrad_tn_bf16x3_launch(const MssConvArgs& p, const float* dy, int lddy, float* dwp, int Cp, float* ws, long long ws_bytes, void* stream);
 
 namespace {
@@ -639,10 +640,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_par_kernel(const float* __re
   }
 }
 
-inline void launch_wgrad_reduce(const float* ws, float* dwp, long long slab4, int splits, hipStream_t stream) {
-  // threads wanted: ~64 k; G split-lanes per element while each lane still has >= 4 splits
-  int G = 1;
-  while (G < 32 && slab4 * G < 65536 && splits >= 8 * G) G *= 2;
+// G: wg_reduce_group(slab4, splits) (wgrad_route.h)
+inline void launch_wgrad_reduce(const float* ws, float* dwp, long long slab4, int splits, int G, hipStream_t stream) {
   if (G == 1) {
     long long blocks = (slab4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
@@ -957,7 +956,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(const float* __r
 
 // splits > 1: the kernel wrote every element of every partial slab of ws (see the kernels' epilogues), so whole slabs are swept
 inline int finish_splits(const WgradRoute& r, const MssConvArgs& p, int Cp, const float* ws, float* dwp, hipStream_t stream) {
-  if (r.splits > 1) launch_wgrad_reduce(ws, dwp, (long long)r.positions * p.Kpad * Cp / 4, r.splits, stream);
+  if (r.splits > 1) launch_wgrad_reduce(ws, dwp, (long long)r.positions * p.Kpad * Cp / 4, r.splits, r.reduce_group, stream);
   return mss_launch_status();
 }
 
@@ -1053,7 +1052,7 @@ int launch_wgrad_tn_lds(const WgradRoute& r, const MssConvArgs& p, const float* 
   return finish_splits(r, p, Cp, ws, dwp, stream);
 }
 
-const WgradSplitBf16 split_bf16 = {mss_wgrad_tn_bf16x3_eligible, mss_wgrad_tn_bf16x3_ws_bytes};
+const WgradSplitBf16 split_bf16 = {mss_wgrad_tn_bf16x3_eligible, mss_wgrad_tn_bf16x3_ws_bytes, mss_wgrad_tn_bf16x3_plan};
 
 // read per call through the cached lookup (mss_env_reset: tests switch routes inside one process)
 WgradSwitches wgrad_switches() {
@@ -1067,13 +1066,9 @@ WgradSwitches wgrad_switches() {
   return sw;
 }
 
-inline bool aligned_to(const void* q, uintptr_t n) { return (reinterpret_cast<uintptr_t>(q) & (n - 1)) == 0; }
-
-// One product on the kernel its route names.
-int launch_route(WgradRoute r, const MssConvArgs& p, const float* dy, int lddy, float* dwp, int Cp, float* ws, long long ws_bytes, WgradFacts f,
+// One product on the kernel its route names (wgrad_resolve's: already the native one where the scratch is too small for the split-bf16 kernel).
+int launch_route(const WgradRoute& r, const MssConvArgs& p, const float* dy, int lddy, float* dwp, int Cp, float* ws, long long ws_bytes,
                  const WgradSwitches& sw, hipStream_t s) {
-  // the split-bf16 kernel alone is skipped, not failed, on a scratch too small for it: the native route's needs then decide
-  if (r.kernel == WG_TN_BF16X3 && ws_bytes < r.ws_bytes) r = wgrad_route(p, lddy, Cp, f, sw);
   if (r.ws_bytes > 0 && (!ws || ws_bytes < r.ws_bytes)) return MSS_ERR_BAD_ARG;
   switch (r.kernel) {
     case WG_TN_BF16X3: return mss_wgrad_tn_bf16x3_launch(p, dy, lddy, dwp, Cp, ws, ws_bytes, s);
@@ -1094,7 +1089,7 @@ int launch_route(WgradRoute r, const MssConvArgs& p, const float* dy, int lddy, 
 }  // namespace
 
 void mss_wgrad_reduce_launch(const float* ws, float* dwp, long long slab4, int splits, hipStream_t stream) {
-  launch_wgrad_reduce(ws, dwp, slab4, splits, stream);
+  launch_wgrad_reduce(ws, dwp, slab4, splits, wg_reduce_group(slab4, splits), stream);
 }
 
 extern "C" {
@@ -1127,33 +1122,37 @@ long long mss_conv2d_wgrad_workspace_bytes(const MssConvArgs* args, int Cp) {
 // irrelevant on entry. Deterministic: no atomics, fixed summation order.
 int mss_conv2d_wgrad_f32(MssConvArgs* args, const float* dy, int lddy, float* dwp, int Cp, float* ws,
                          long long ws_bytes, void* stream) {
-  MssConvArgs p = *args;
-  if (!p.x || !dy || !dwp) return MSS_ERR_BAD_ARG;
-  if (p.C % 4 || p.ldx % 4 || lddy % 4 || p.R * p.S > 9 || Cp % 4) return MSS_ERR_UNSUPPORTED;
-  p.M = p.N * p.OH * p.OW;
-  if (p.M <= 0) return MSS_OK;
-  if (p.batch > 1 && (p.R * p.S != 1 || p.batch > 65535)) return MSS_ERR_BAD_ARG;
-  if (p.k_steps) {               // MssConvArgs.k_imgs: the LDS-free TN kernel is the only one that has the per-image form
-    if (p.k_imgs < 1 || p.batch < 2 || p.batch % p.k_imgs || p.k_base < 0 || p.k_base * 16 > p.C || p.R * p.S != 1 || p.N != 1 || p.H != 1 ||
-        p.K % 128 || p.C % 128 || p.K > 4096 || p.Kpad != p.K || Cp != p.C || p.ldx != p.C || lddy != p.K || p.x_bs % 4 || p.y_bs % 4 ||
-        p.in_scale || p.in_shift || p.in_relu || p.route)
-      return MSS_ERR_UNSUPPORTED;
-  }
-  WgradFacts f;
-  f.dense_dy = lddy == p.K;
-  f.dy8 = aligned_to(dy, 8);
-  f.x16 = aligned_to(p.x, 16);
-  f.affine16 = aligned_to(p.in_scale, 16) && aligned_to(p.in_shift, 16);      // (a null pointer counts as aligned)
   const WgradSwitches sw = wgrad_switches();
+  WgradCall c;
+  if (const int rc = wgrad_resolve(args, dy, lddy, dwp, Cp, ws_bytes, sw, split_bf16, c)) return rc;
+  if (c.empty) return MSS_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const WgradRoute r = wgrad_route(p, lddy, Cp, f, sw, split_bf16);
-  if (r.kernel != WG_TWO_PART) return launch_route(r, p, dy, lddy, dwp, Cp, ws, ws_bytes, f, sw, s);
+  if (c.route.kernel != WG_TWO_PART) return launch_route(c.route, c.p, dy, lddy, dwp, Cp, ws, ws_bytes, sw, s);
   // both parts one after the other on the same scratch, each writing its own rows of dwp
-  const MssConvArgs a = wgrad_part(p, r.wide_K, false), b = wgrad_part(p, r.wide_K, true);
-  f.dense_dy = false;
-  const int rc = launch_route(wgrad_route(a, lddy, Cp, f, sw, split_bf16), a, dy, lddy, dwp, Cp, ws, ws_bytes, f, sw, s);
+  const int wide = c.route.wide_K;
+  const int rc = launch_route(c.part_route[0], c.part[0], dy, lddy, dwp, Cp, ws, ws_bytes, sw, s);
   if (rc != MSS_OK) return rc;
-  return launch_route(wgrad_route(b, lddy, Cp, f, sw, split_bf16), b, dy + r.wide_K, lddy, dwp + (size_t)r.wide_K * Cp, Cp, ws, ws_bytes, f, sw, s);
+  return launch_route(c.part_route[1], c.part[1], dy + wide, lddy, dwp + (size_t)wide * Cp, Cp, ws, ws_bytes, sw, s);
+}
+
+// What that call launches: the same wgrad_resolve, nothing else (include/mss_hip.h).
+int mss_conv2d_wgrad_plan(const MssConvArgs* args, const float* dy, int lddy, const float* dwp, int Cp, long long ws_bytes, int part,
+                          MssWgradPlan* out) {
+  if (!args || !out || part < 0 || part > 2) return MSS_ERR_BAD_ARG;
+  WgradCall c;
+  if (const int rc = wgrad_resolve(args, dy, lddy, dwp, Cp, ws_bytes, wgrad_switches(), split_bf16, c)) return rc;
+  MssWgradPlan o = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (!c.empty) {
+    if (part != 0 && c.route.kernel != WG_TWO_PART) return MSS_ERR_BAD_ARG;
+    const WgradRoute& r = part == 0 ? c.route : c.part_route[part - 1];
+    o.kernel = r.kernel; o.ktiles = r.ktiles; o.ctiles = r.ctiles; o.positions = r.positions; o.splits = r.splits;
+    o.rows_per_split = r.rows_per_split; o.total = r.total; o.full = r.full; o.ws_bytes = r.ws_bytes; o.wide_K = r.wide_K;
+    o.reduce_group = r.reduce_group;
+  } else if (part != 0) {
+    return MSS_ERR_BAD_ARG;
+  }
+  *out = o;
+  return MSS_OK;
 }
 
 }  // extern "C"

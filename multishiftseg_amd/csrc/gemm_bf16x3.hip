@@ -1027,6 +1027,13 @@ long long mss_wgrad_tn_bf16x3_ws_bytes(const MssConvArgs& p, int Cp) {
   return pl.splits > 1 ? (long long)pl.splits * (p.batch > 1 ? p.batch : 1) * p.Kpad * Cp * 4 : 0;
 }
 
+// the plan's figures for mss_conv2d_wgrad_plan (wgrad_route.h: WgradSplitBf16.plan)
+void mss_wgrad_tn_bf16x3_plan(const MssConvArgs& p, WgradRoute& r) {
+  const TnSplitPlan pl = tn_split_plan(p);
+  r.ktiles = pl.ktiles; r.ctiles = pl.ctiles; r.positions = p.batch > 1 ? p.batch : 1;
+  r.splits = pl.splits; r.rows_per_split = pl.tps; r.total = pl.total;
+}
+
 int mss_wgrad_tn_bf16x3_launch(const MssConvArgs& p, const float* dy, int lddy, float* dwp, int Cp, float* ws, long long ws_bytes, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const TnSplitPlan pl = tn_split_plan(p);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/mss_hip.h"
+#include "mss_gemm_dims.h"
 #include "tn_perimg_plan.h"
 
 // The MSS_WGRAD_* switches (conv_wgrad.hip reads them with MSS_ENV_INT once per call; these are the defaults).
@@ -25,18 +26,19 @@ struct WgradSwitches {
   int tn_slots = TN_PERIMG_MAX_SLOTS;     // MSS_WGRAD_TN_SLOTS: wave slots of the packed per-image plan (tests reach its tail plan)
 };
 
+// (the values are include/mss_hip.h's MSS_WG_*: mss_conv2d_wgrad_plan publishes them)
 enum WgradKernel {
-  WG_CONV_32,             // conv_wgrad_kernel<32, 128, 16, 1>: the 19-channel heads
-  WG_CONV_64,             // conv_wgrad_kernel<64, 128, 16, 2>: bot_fine's 48
-  WG_CONV_128,            // conv_wgrad_kernel<128, 128, 16, 2>
-  WG_NARROW,              // gemm_tn_narrow_kernel (32 or 64 output rows; with or without prologue)
-  WG_TN_LDS,              // gemm_tn_wgrad_kernel
-  WG_TN_WIDE,             // gemm_tn2_wgrad_kernel
-  WG_TN_DIRECT,           // gemm_tn_direct_kernel, whole tiles or row splits of every tile
-  WG_TN_DIRECT_TAIL,      // gemm_tn_direct_kernel with the tail plan (full >= 0) + tn_tail_reduce_kernel
-  WG_TN_DIRECT_PERIMG,    // gemm_tn_direct_kernel<false, true>: MssConvArgs.k_steps
-  WG_TN_BF16X3,           // the split-bf16 TN kernel (gemm_bf16x3.hip): args->route == 1
-  WG_TWO_PART,            // K = 128 j + r: the first wide_K channels as one product, then the last r on WG_NARROW
+  WG_CONV_32 = MSS_WG_CONV_32,                        // conv_wgrad_kernel<32, 128, 16, 1>: the 19-channel heads
+  WG_CONV_64 = MSS_WG_CONV_64,                        // conv_wgrad_kernel<64, 128, 16, 2>: bot_fine's 48
+  WG_CONV_128 = MSS_WG_CONV_128,                      // conv_wgrad_kernel<128, 128, 16, 2>
+  WG_NARROW = MSS_WG_NARROW,                          // gemm_tn_narrow_kernel (32 or 64 output rows; with or without prologue)
+  WG_TN_LDS = MSS_WG_TN_LDS,                          // gemm_tn_wgrad_kernel
+  WG_TN_WIDE = MSS_WG_TN_WIDE,                        // gemm_tn2_wgrad_kernel
+  WG_TN_DIRECT = MSS_WG_TN_DIRECT,                    // gemm_tn_direct_kernel, whole tiles or row splits of every tile
+  WG_TN_DIRECT_TAIL = MSS_WG_TN_DIRECT_TAIL,          // gemm_tn_direct_kernel with the tail plan (full >= 0) + tn_tail_reduce_kernel
+  WG_TN_DIRECT_PERIMG = MSS_WG_TN_DIRECT_PERIMG,      // gemm_tn_direct_kernel<false, true>: MssConvArgs.k_steps
+  WG_TN_BF16X3 = MSS_WG_TN_BF16X3,                    // the split-bf16 TN kernel (gemm_bf16x3.hip): args->route == 1
+  WG_TWO_PART = MSS_WG_TWO_PART,                      // K = 128 j + r: the first wide_K channels as one product, then the last r on WG_NARROW
 };
 
 struct WgradRoute {
@@ -49,6 +51,7 @@ struct WgradRoute {
   long long full = -1;          // tail plan of gemm_tn_direct_kernel: whole-tile jobs in front of the split ones; -1: none
   long long ws_bytes = 0;       // scratch this launch needs
   int wide_K = 0;               // WG_TWO_PART: channels of the first product (the parts' routes: wgrad_route on wgrad_part)
+  int reduce_group = 0;         // wg_reduce_group of the launch that adds the partial slabs; 0: no such launch
 };
 
 // What the workspace query cannot know.
@@ -63,6 +66,8 @@ struct WgradFacts {
 struct WgradSplitBf16 {
   bool (*eligible)(const MssConvArgs& p, int lddy) = nullptr;
   long long (*ws_bytes)(const MssConvArgs& p, int Cp) = nullptr;
+  // optional: writes the tiles, positions, splits, rows per split and job count of its plan into r (for mss_conv2d_wgrad_plan)
+  void (*plan)(const MssConvArgs& p, WgradRoute& r) = nullptr;
 };
 
 static inline int wg_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
@@ -92,6 +97,19 @@ static inline void wg_cut_rows(WgradRoute& r, int M, int splits, int granule) {
 static inline long long wg_slab_bytes(const WgradRoute& r, const MssConvArgs& p, int Cp) {
   return r.splits > 1 ? (long long)r.splits * r.positions * p.Kpad * Cp * 4 : 0;
 }
+// The launch that adds `splits` partial slabs of slab4 float4s each (wgrad_reduce_kernel / wgrad_reduce_par_kernel<G>): how many
+// threads share one output float4. ~64 k threads are wanted, so G split-lanes per element while each lane still has >= 4 splits
+// (>= 8 G splits); 1 = the sequential kernel, one thread per float4 walking all the splits.
+static inline int wg_reduce_group(long long slab4, int splits) {
+  int G = 1;
+  while (G < 32 && slab4 * G < 65536 && splits >= 8 * G) G *= 2;
+  return G;
+}
+// scratch and reducer of a plan whose splits each write a whole [positions][Kpad][Cp] slab
+static inline void wg_plan_slabs(WgradRoute& r, const MssConvArgs& p, int Cp) {
+  r.ws_bytes = wg_slab_bytes(r, p, Cp);
+  r.reduce_group = r.splits > 1 ? wg_reduce_group((long long)r.positions * p.Kpad * Cp / 4, r.splits) : 0;
+}
 
 // conv_wgrad_kernel<BKO, 128, 16>: one workgroup per (k tile x c tile, tap or batch entry, split), 768 slots =
 // 3 workgroups per CU (34 KB LDS, 154 registers)
@@ -106,7 +124,7 @@ static inline WgradRoute wg_plan_conv(const MssConvArgs& p, int Cp) {
   if (max_splits < 1) max_splits = 1;
   wg_cut_rows(r, p.M, split_search(base, 768, max_splits), bp);
   r.total = (long long)base * r.splits;
-  r.ws_bytes = wg_slab_bytes(r, p, Cp);
+  wg_plan_slabs(r, p, Cp);
   return r;
 }
 
@@ -130,7 +148,7 @@ static inline WgradRoute wg_plan_narrow(const MssConvArgs& p, int Cp) {
   if (splits < 1) splits = 1;
   wg_cut_rows(r, p.M, splits, 2);
   r.total = (long long)r.ctiles * r.splits;
-  r.ws_bytes = wg_slab_bytes(r, p, Cp);
+  wg_plan_slabs(r, p, Cp);
   return r;
 }
 
@@ -148,7 +166,7 @@ static inline WgradRoute wg_plan_tn_lds(const MssConvArgs& p, int Cp, bool wide)
   if (max_splits < 1) max_splits = 1;
   wg_cut_rows(r, p.M, split_search(base, wide ? 512 : 768, max_splits), 16);
   r.total = base * r.splits;
-  r.ws_bytes = wg_slab_bytes(r, p, Cp);
+  wg_plan_slabs(r, p, Cp);
   return r;
 }
 static inline bool wg_tn_wide(const MssConvArgs& p, int Cp, const WgradSwitches& sw) {
@@ -188,7 +206,7 @@ static inline WgradRoute wg_plan_tn_direct(const MssConvArgs& p, int Cp, const W
   if (max_splits < 1) max_splits = 1;
   wg_cut_rows(r, p.M, split_search(base, slots, max_splits), 2);
   r.total = base * r.splits;
-  r.ws_bytes = wg_slab_bytes(r, p, Cp);
+  wg_plan_slabs(r, p, Cp);
   return r;
 }
 // Whether the LDS-free kernel takes the product; `plan` is then its plan.
@@ -262,6 +280,10 @@ static inline WgradRoute wgrad_route(const MssConvArgs& p, int lddy, int Cp, Wgr
     WgradRoute r;
     r.kernel = WG_TN_BF16X3;
     r.ws_bytes = bf.ws_bytes(p, Cp);
+    if (bf.plan) {
+      bf.plan(p, r);
+      r.reduce_group = r.splits > 1 ? wg_reduce_group((long long)r.positions * p.Kpad * Cp / 4, r.splits) : 0;
+    }
     return r;
   }
   WgradRoute d;
@@ -284,4 +306,75 @@ static inline long long wgrad_workspace_bytes(const MssConvArgs& p, int Cp, cons
     if (b > need) need = b;
   }
   return need;
+}
+
+// ---- One call of mss_conv2d_wgrad_f32, resolved: its argument checks, the facts read off its pointers and the route(s) it launches.
+// The launch and the plan query (mss_conv2d_wgrad_plan) both go through wgrad_resolve, so they cannot disagree. No pointer is
+// dereferenced.
+struct WgradCall {
+  bool empty = false;           // no output pixels: nothing is launched (MSS_OK)
+  MssConvArgs p;                // the arguments with M set
+  WgradFacts f;
+  WgradRoute route;             // the product as given; WG_TWO_PART: what is launched are the two parts below, with part_f
+  MssConvArgs part[2];          // part[1]: dy advanced by wide_K floats, dwp by wide_K * Cp (the launch does that)
+  WgradRoute part_route[2];
+  WgradFacts part_f;
+};
+
+static inline bool wg_aligned_to(const void* q, uintptr_t n) { return (reinterpret_cast<uintptr_t>(q) & (n - 1)) == 0; }
+
+// the route a launch given ws_bytes of scratch takes: the split-bf16 kernel alone is skipped, not failed, on a scratch too small
+// for it -- the native route's needs then decide
+static inline WgradRoute wgrad_route_given(const MssConvArgs& p, int lddy, int Cp, WgradFacts f, const WgradSwitches& sw, const WgradSplitBf16& bf,
+                                           long long ws_bytes) {
+  const WgradRoute r = wgrad_route(p, lddy, Cp, f, sw, bf);
+  return r.kernel == WG_TN_BF16X3 && ws_bytes < r.ws_bytes ? wgrad_route(p, lddy, Cp, f, sw) : r;
+}
+
+// Whether the tiles of a launch cover dwp [Kpad][Cp]: every kernel's epilogue writes rows < Kpad and columns < Cp INSIDE its own
+// ktiles x ctiles tiles only (the padding there holds exact zeros), so padding beyond the last tile would stay unwritten.
+// (The split-bf16 and per-image forms take an unpadded result only: checked where they are chosen.)
+static inline bool wg_covers_padding(const WgradRoute& r, const MssConvArgs& p, int Cp) {
+  if (r.kernel == WG_TN_BF16X3 || r.kernel == WG_TN_DIRECT_PERIMG) return true;
+  long long rows = 128, cols = 128;
+  switch (r.kernel) {
+    case WG_CONV_32: rows = 32; break;
+    case WG_CONV_64: rows = 64; break;
+    case WG_NARROW: rows = p.K <= 32 ? 32 : 64; break;
+    case WG_TN_WIDE: cols = 256; break;
+    default: break;
+  }
+  return p.Kpad <= rows * r.ktiles && Cp <= cols * r.ctiles;
+}
+
+static inline int wgrad_resolve(const MssConvArgs* args, const float* dy, int lddy, const float* dwp, int Cp, long long ws_bytes,
+                                const WgradSwitches& sw, const WgradSplitBf16& bf, WgradCall& c) {
+  MssConvArgs& p = c.p;
+  p = *args;
+  if (!p.x || !dy || !dwp) return MSS_ERR_BAD_ARG;
+  if (p.C % 4 || p.ldx % 4 || lddy % 4 || p.R * p.S > 9 || Cp % 4) return MSS_ERR_UNSUPPORTED;
+  p.M = p.N * p.OH * p.OW;
+  if (p.M <= 0) { c.empty = true; return MSS_OK; }
+  if (p.batch > 1 && (p.R * p.S != 1 || p.batch > 65535)) return MSS_ERR_BAD_ARG;
+  if (p.k_steps) {               // MssConvArgs.k_imgs: the LDS-free TN kernel is the only one that has the per-image form
+    if (p.k_imgs < 1 || p.batch < 2 || p.batch % p.k_imgs || p.k_base < 0 || p.k_base * 16 > p.C || p.R * p.S != 1 || p.N != 1 || p.H != 1 ||
+        p.K % 128 || p.C % 128 || p.K > 4096 || p.Kpad != p.K || Cp != p.C || p.ldx != p.C || lddy != p.K || p.x_bs % 4 || p.y_bs % 4 ||
+        p.in_scale || p.in_shift || p.in_relu || p.route)
+      return MSS_ERR_UNSUPPORTED;
+  }
+  c.f.dense_dy = lddy == p.K;
+  c.f.dy8 = wg_aligned_to(dy, 8);
+  c.f.x16 = wg_aligned_to(p.x, 16);
+  c.f.affine16 = wg_aligned_to(p.in_scale, 16) && wg_aligned_to(p.in_shift, 16);      // (a null pointer counts as aligned)
+  c.route = wgrad_route_given(p, lddy, Cp, c.f, sw, bf, ws_bytes);
+  if (c.route.kernel != WG_TWO_PART) return wg_covers_padding(c.route, p, Cp) ? MSS_OK : MSS_ERR_UNSUPPORTED;
+  // both parts one after the other on the same scratch, each writing its own rows of dwp
+  c.part_f = c.f;
+  c.part_f.dense_dy = false;
+  for (int i = 0; i < 2; ++i) {
+    c.part[i] = wgrad_part(p, c.route.wide_K, i == 1);
+    c.part_route[i] = wgrad_route_given(c.part[i], lddy, Cp, c.part_f, sw, bf, ws_bytes);
+    if (!wg_covers_padding(c.part_route[i], c.part[i], Cp)) return MSS_ERR_UNSUPPORTED;
+  }
+  return MSS_OK;
 }

@@ -85,7 +85,7 @@ def test_ctypes_table_matches_header(lib):
         assert base in scalars, f"a parameter type this test does not know: {param!r}"
         return scalars[base]
     decls = header_declarations()
-    assert len(decls) == len(lib.SIGNATURES) == 141 and {d[1] for d in decls} == set(lib.SIGNATURES)
+    assert len(decls) == len(lib.SIGNATURES) == 142 and {d[1] for d in decls} == set(lib.SIGNATURES)
     wrong = []
     for ret, name, params in decls:
         ret = " ".join(ret.split())
@@ -108,7 +108,7 @@ def test_struct_layout_matches_header(lib, tmp_path):
     """sizeof of every struct of the header, and offsetof of its last field, as the C compiler sees them."""
     import ctypes
     last = {"MssConvArgs": "w_img_stride", "MssRclArgs": "selection_ratio", "MssOodmBatch": "n", "MssM2fSteps": "step", "MssM2fGrads": "step",
-            "MssM2fMaps": "w", "MssM2fTargets": "W"}
+            "MssM2fMaps": "w", "MssM2fTargets": "W", "MssWgradPlan": "reduce_group"}
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mss_hip.h")).read(), flags=re.S)
     assert set(re.findall(r"typedef struct (Mss\w+)", header)) == set(last)
     for name, field in last.items():

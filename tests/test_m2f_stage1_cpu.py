@@ -1,5 +1,5 @@
 """CPU: the host side of Mask2Former stage 1 -- the chunk planner of kernels.m2f_semantic_inference, the exported names, and the
-promise that the feature adds no entry point: include/mss_hip.h still declares 141 functions at ABI version 25."""
+promise that the feature adds no entry point: include/mss_hip.h declared 141 functions at ABI version 25 with it (142 at version 26 since mss_conv2d_wgrad_plan)."""
 import inspect
 import os
 import re
@@ -68,6 +68,6 @@ def test_exported_names():
 def test_the_feature_adds_no_entry_point():
     from multishiftseg_amd import _lib
     src = open(os.path.join(ROOT, "include", "mss_hip.h")).read()
-    assert len(header_declarations()) == len(_lib.SIGNATURES) == 141
-    assert int(re.search(r"#define MSS_ABI_VERSION (\d+)", src).group(1)) == _lib.MSS_ABI_VERSION == 25
+    assert len(header_declarations()) == len(_lib.SIGNATURES) == 142          # (141 when the feature landed; mss_conv2d_wgrad_plan since)
+    assert int(re.search(r"#define MSS_ABI_VERSION (\d+)", src).group(1)) == _lib.MSS_ABI_VERSION == 26
     assert "lat == NULL" in src and "dmasks == NULL" in src                        # both variants are documented at their declarations

@@ -139,4 +139,4 @@ def test_what_is_new_is_exported():
     from multishiftseg_amd import _lib, kernels
     assert "conv2d_dgrad_s2" in pkg.__all__ and pkg.conv2d_dgrad_s2 is kernels.conv2d_dgrad_s2
     assert callable(pkg.ResNet.set_trainable) and callable(pkg.ResNet.freeze) and callable(pkg.MaskFormer.set_trainable)
-    assert _lib.MSS_ABI_VERSION == 25
+    assert _lib.MSS_ABI_VERSION == 26

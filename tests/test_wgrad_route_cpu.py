@@ -3,8 +3,8 @@
 tests/golden/wgrad_route_parent.json pins what mss_conv2d_wgrad_workspace_bytes and mss_conv2d_wgrad_route answered before the routing
 became one header (tools/gen_wgrad_route_golden.py): the route must be equal on every row and the scratch never larger. A stand-alone
 program (tests/wgrad_route_check.cpp, its own main, built with the host compiler's address and undefined-behaviour sanitizers) checks
-every row under every combination of the facts the query cannot know, prints the chosen kernel, and exposes split_search, which is
-compared with the rule written down again here."""
+every row under every combination of the facts the query cannot know, prints the chosen kernel, and exposes split_search and
+wg_reduce_group (which reducer adds the partial slabs), each compared with the rule written down again here."""
 import json
 import os
 import shutil
@@ -148,3 +148,27 @@ def test_split_search_is_the_rule(checker, cap):
     got = [int(v) for v in subprocess.run([checker, "split", str(cap)], capture_output=True, text=True, check=True).stdout.split()]
     want = [_split_search(base, slots, cap) for slots in (512, 768, 1024) for base in range(1, 5001)]
     assert got == want
+
+
+REDUCE_SLAB4 = [1, 304, 2047, 2048, 2049, 4095, 4096, 4097, 8191, 8192, 8193, 16383, 16384, 16385, 32767, 32768, 32769, 65535, 65536, 65537,
+                73728, 1048576, 1 << 33]
+
+
+def reduce_group(slab4, splits):
+    """The rule of wg_reduce_group: the largest power of two G <= 32 such that, for every doubling on the way to it, the threads so far
+    (one per output float4 and lane: slab4 * G / 2) are fewer than 65536 and every lane keeps at least 4 splits (splits >= 4 G)."""
+    g = 1
+    while g < 32 and slab4 * g < 65536 and splits >= 8 * g:
+        g *= 2
+    return g
+
+
+def test_reduce_group_is_the_rule(checker):
+    got = [int(v) for v in subprocess.run([checker, "reduce"], capture_output=True, text=True, check=True).stdout.split()]
+    want = [reduce_group(slab4, splits) for slab4 in REDUCE_SLAB4 for splits in range(1, 601)]
+    assert got == want
+    assert set(want) == {1, 2, 4, 8, 16, 32}
+    # the shapes the header's comments name: 1536 splits of the 19 x 256 head slab (20 KB) on 32 lanes, 256 splits of a 256 x 256
+    # Linear (256 KB) on 4, anything of 64 k float4s or more, or fewer than 8 splits, on the sequential kernel
+    assert reduce_group(20 * 256 // 4, 1536) == 32 and reduce_group(256 * 256 // 4, 256) == 4
+    assert reduce_group(65536, 1024) == 1 and reduce_group(16, 7) == 1

@@ -1,6 +1,7 @@
 // Stand-alone host check of csrc/wgrad_route.h (tests/test_wgrad_route_cpu.py compiles and runs it, with the host compiler's address
 // and undefined-behaviour sanitizers). `wgrad_route_check split CAP` prints split_search(base, slots, CAP) for base 1..5000 and slots
-// 512, 768, 1024. Otherwise one case per line of stdin (the columns of tests/golden/wgrad_route_parent.json with the switches written out):
+// 512, 768, 1024; `wgrad_route_check reduce` prints wg_reduce_group(slab4, splits) for every slab4 of REDUCE_SLAB4 (below) and splits
+// 1..600, slab4 outermost. Otherwise one case per line of stdin (the columns of tests/golden/wgrad_route_parent.json with the switches written out):
 //   M C K Kpad Cp lddy ldx R stride dil batch affine in_ss_stride route k_imgs  tn narrow tn_affine tn_tail
 // For every case and every combination of WgradFacts the chosen route (for the two-part route: both parts) is checked against the
 // kernels' preconditions as their comments state them, the job counts their decodes assume and the scratch formulas, and against the
@@ -27,6 +28,10 @@ static int line = 0;
   } while (0)
 
 static long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+
+// around every threshold of the rule (65536 / G float4s) and far from them; tests/test_wgrad_route_cpu.py has the same list
+static const long long REDUCE_SLAB4[] = {1, 304, 2047, 2048, 2049, 4095, 4096, 4097, 8191, 8192, 8193, 16383, 16384, 16385, 32767, 32768, 32769,
+                                         65535, 65536, 65537, 73728, 1048576, 1ll << 33};
 
 // one launched product: r is what wgrad_route chose for p
 static bool check_launch(const WgradRoute& r, const MssConvArgs& p, int lddy, int Cp, WgradFacts f, const WgradSwitches& sw, long long query) {
@@ -91,6 +96,8 @@ static bool check_launch(const WgradRoute& r, const MssConvArgs& p, int lddy, in
     CHECK(r.total == tiles * r.splits, "total %lld, %lld tiles", r.total, tiles);
     CHECK(r.ws_bytes == (r.splits > 1 ? (long long)r.splits * r.positions * p.Kpad * Cp * 4 : 0), "scratch %lld", r.ws_bytes);
   }
+  // the reduce launch: none for one split and for the tail plan (its own reducer), else the group of the slab's float4 count
+  CHECK(r.reduce_group == (r.splits > 1 && r.full < 0 ? wg_reduce_group((long long)r.positions * p.Kpad * Cp / 4, r.splits) : 0), "reduce group %d", r.reduce_group);
   return true;
 }
 
@@ -112,6 +119,11 @@ int main(int argc, char** argv) {
     const int slots[3] = {512, 768, 1024};
     for (int s = 0; s < 3; ++s)
       for (int base = 1; base <= 5000; ++base) std::printf("%d\n", split_search(base, slots[s], std::atoi(argv[2])));
+    return 0;
+  }
+  if (argc == 2 && !std::strcmp(argv[1], "reduce")) {
+    for (long long slab4 : REDUCE_SLAB4)
+      for (int splits = 1; splits <= 600; ++splits) std::printf("%d\n", wg_reduce_group(slab4, splits));
     return 0;
   }
   static float fake[64];                       // pointer fields are only compared with null
