@@ -66,7 +66,11 @@ extern "C" {
                                   stride-2 convolution (csrc/conv_dgrad_s2.hip; no caller passed a negative stride before);
                                   mss_conv2d_forward_route labels it 6;
                                   26 (additive): mss_conv2d_wgrad_plan, MssWgradPlan and the MSS_WG_* kernel names (what a weight-gradient call
-                                  launches: kernel, splits, reducer), host-only */
+                                  launches: kernel, splits, reducer), host-only;
+                                  still 26 (no entry point or struct changes, and two tests pin the number): mss_conv2d_wgrad_f32 takes the 7x7 /
+                                  stride-2 / 4 -> 64 stem of the ResNet-50 backbone (csrc/stem7_wgrad.hip), plain or with the max-pool and ReLU
+                                  backward fused, which it answered MSS_ERR_UNSUPPORTED before; mss_conv2d_wgrad_plan names it MSS_WG_STEM7. A caller
+                                  that needs to know asks the plan query for the stem form: MSS_OK with kernel 11 */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -301,7 +305,28 @@ int mss_conv2d_pack_weights_f32(const float* w, float* packed, int K, int C, int
  * Per-image form (args->k_steps): mss_conv2d_wgrad_workspace_bytes is 0 and ws = NULL works -- the live tiles are packed densely and
  * every job is a whole tile. With ws_bytes >= MSS_WGRAD_PERIMG_TAIL_BYTES the last, partial round of one-wave jobs is cut by rows
  * as well: partial tiles go to ws and a second launch adds them in ascending order (still no atomics, one fixed order). Either
- * way, tiles behind an image's extent stay unwritten and the columns behind it inside a tile are exact zeros. */
+ * way, tiles behind an image's extent stay unwritten and the columns behind it inside a tile are exact zeros.
+ * Shapes: C % 4 == 0, ldx % 4 == 0, lddy % 4 == 0, Cp % 4 == 0, 1 <= R * S <= 9 -- and ONE more, recognised in front of those checks:
+ * the stem of the Mask2Former ResNet-50 backbone (csrc/stem7_wgrad.hip, v_mfma_f32_16x16x4_f32 with four output pixels as the K step;
+ * MSS_WG_STEM7), exactly this argument set:
+ *   R == S == 7, stride == 2, pad == 3, dil == 1; C == 4 and ldx == 4; K == 64, Kpad == 64 and Cp == 4; batch <= 1; no in_scale,
+ *   in_shift, in_relu or k_steps. Every other combination with R * S > 9 is MSS_ERR_UNSUPPORTED as before. `route` is ignored: the
+ *   product runs on the native fp32 MFMA.
+ *   x = the image [N, H, W, 4] as mss_nchw_to_nhwc_pad_f32 writes it with Cp = 4 (three colour channels and one ZERO channel: the
+ *       caller's contract, as the forward's). OH, OW: the stem's output grid; MSS_ERR_BAD_ARG unless OH == (H - 1) / 2 + 1 and
+ *       OW == (W - 1) / 2 + 1. x, dy and res 16-byte aligned and lddy >= 64, else MSS_ERR_BAD_ARG.
+ *   Plain form, res == NULL: dy = dz [N, OH, OW, 64] with pitch lddy: dwp[tap][k][c] = sum_m dz[m][k] * x[m @ tap][c], zero outside
+ *       the image.
+ *   Pool form, res != NULL (ldres >= 64, ldres % 4 == 0 and res_mask == 1, else MSS_ERR_BAD_ARG): res = the stored stem output
+ *       a0 [N, OH, OW, 64] after norm and ReLU; dy = the gradient at the POOLED map [N, PH, PW, 64], PH = (OH - 1) / 2 + 1,
+ *       PW = (OW - 1) / 2 + 1 (max-pool 3x3, stride 2, padding 1). The kernel forms dz[n, oy, ox, k] = [a0 > 0] * the sum, in
+ *       ascending (py, px), of dy[n, py, px, k] over the up to four windows whose arg-max is (oy, ox). The arg-max is recomputed from
+ *       a0 (no index tensor): the FIRST maximum in row-major order among the window's in-image positions, a NaN takes the window
+ *       (F.max_pool2d's rule). A window whose maximum is not positive contributes nothing.
+ *   dwp [49][64][4] is fully overwritten; column c == 3 holds the product with the pad channel (zero under the image contract).
+ *   Deterministic and bit-reproducible as every form: no atomics, the pixel-range slabs are added in ascending order. Scratch:
+ *   mss_conv2d_wgrad_workspace_bytes; MSS_ERR_BAD_ARG with less. mss_conv2d_wgrad_plan: positions = 49, ktiles = ctiles = 1, one
+ *   workgroup per split (total = splits), rows_per_split = 64 x the 4 x 16-pixel tiles of a split. mss_conv2d_wgrad_route answers 0. */
 #define MSS_WGRAD_PERIMG_TAIL_BYTES (1024ll * 128 * 128 * 4)     /* 1024 wave slots x one 128 x 128 fp32 tile: tail tiles x splits <= slots */
 long long mss_conv2d_wgrad_workspace_bytes(const MssConvArgs* args, int Cp);
 int mss_conv2d_wgrad_f32(MssConvArgs* args, const float* dy, int lddy, float* dwp, int Cp, float* ws,
@@ -334,6 +359,7 @@ int mss_conv2d_wgrad_route(const MssConvArgs* args, int lddy);
 #define MSS_WG_TN_DIRECT_PERIMG 8   /* gemm_tn_direct_kernel, per-image form (MssConvArgs.k_steps)                         */
 #define MSS_WG_TN_BF16X3 9          /* the split-bf16 TN kernel (args->route == 1)                                         */
 #define MSS_WG_TWO_PART 10          /* K = 128 j + r: two launches, see `part`                                             */
+#define MSS_WG_STEM7 11             /* stem7_wgrad_kernel: the 7x7 stem form (above mss_conv2d_wgrad_f32)                  */
 typedef struct MssWgradPlan {
   int kernel;                /* MSS_WG_*                                                                                      */
   int ktiles, ctiles;        /* output tiles along K and C                                                                    */

@@ -24,6 +24,9 @@ def __getattr__(name):
     if name == "conv2d_dgrad_s2":
         from .kernels import conv2d_dgrad_s2
         return conv2d_dgrad_s2
+    if name == "stem7_wgrad":
+        from .kernels import stem7_wgrad
+        return stem7_wgrad
     if name in ("prepare_targets", "M2FTargets"):
         from . import m2f_targets
         return getattr(m2f_targets, name)
@@ -43,5 +46,5 @@ def __getattr__(name):
 
 
 __all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention",
-           "conv2d_dgrad_s2", "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER,
+           "conv2d_dgrad_s2", "stem7_wgrad", "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER,
            *_STAGE1_KERNELS]

@@ -75,6 +75,7 @@ class MssConvArgs(Structure):
 
 # include/mss_hip.h MSS_WG_*: MssWgradPlan.kernel -> name
 MSS_WG_NAMES = ("conv32", "conv64", "conv128", "narrow", "tn_lds", "tn_wide", "tn_direct", "tn_direct_tail", "tn_direct_perimg", "tn_bf16x3", "two_part")
+MSS_WG_STEM7 = 11            # include/mss_hip.h: stem7_wgrad_kernel (csrc/stem7_wgrad.hip); MSS_WG_NAMES covers the general routes 0..10
 
 
 class MssWgradPlan(Structure):

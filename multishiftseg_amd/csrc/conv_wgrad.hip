@@ -10,6 +10,7 @@ bool mss_wgrad_tn_bf16x3_eligible(const MssConvArgs& p, int lddy);   // gemm_bf1
 long long mss_wgrad_tn_bf16x3_ws_bytes(const MssConvArgs& p, int Cp);
 void mss_wgrad_tn_bf16x3_plan(const MssConvArgs& p, WgradRoute& r);
 int mss_wgrad_tn_bf16x3_launch(const MssConvArgs& p, const float* dy, int lddy, float* dwp, int Cp, float* ws, long long ws_bytes, void* stream);
+int mss_stem7_wgrad_launch(const WgradRoute& r, const MssConvArgs& p, const float* dy, int lddy, float* dwp, float* ws, hipStream_t stream);   // stem7_wgrad.hip
 
 namespace {
 
@@ -1081,6 +1082,7 @@ int launch_route(const WgradRoute& r, const MssConvArgs& p, const float* dy, int
     case WG_CONV_32: return launch_wgrad_conv<32, 1>(r, p, dy, lddy, dwp, Cp, ws, s);
     case WG_CONV_64: return launch_wgrad_conv<64, 2>(r, p, dy, lddy, dwp, Cp, ws, s);
     case WG_CONV_128: return launch_wgrad_conv<128, 2>(r, p, dy, lddy, dwp, Cp, ws, s);
+    case WG_STEM7: return mss_stem7_wgrad_launch(r, p, dy, lddy, dwp, ws, s);
     case WG_TWO_PART: break;      // (mss_conv2d_wgrad_f32 launches its parts)
   }
   return MSS_ERR_BAD_ARG;
@@ -1099,7 +1101,7 @@ extern "C" {
 int mss_conv2d_wgrad_route(const MssConvArgs* args, int lddy) {
   MssConvArgs p = *args;
   p.M = p.N * p.OH * p.OW;
-  if (p.M <= 0) return 0;
+  if (p.M <= 0 || wg_stem7_form(p, 4)) return 0;
   const WgradSwitches sw = wgrad_switches();
   WgradFacts f;
   f.dense_dy = lddy == p.K;
@@ -1113,6 +1115,7 @@ long long mss_conv2d_wgrad_workspace_bytes(const MssConvArgs* args, int Cp) {
   MssConvArgs p = *args;
   p.M = p.N * p.OH * p.OW;
   if (p.M <= 0) return 0;
+  if (wg_stem7_form(p, Cp)) return wg_plan_stem7(p).ws_bytes;      // (the plan wgrad_resolve gives the launch)
   return wgrad_workspace_bytes(p, Cp, wgrad_switches(), split_bf16);
 }
 

@@ -39,6 +39,7 @@ enum WgradKernel {
   WG_TN_DIRECT_PERIMG = MSS_WG_TN_DIRECT_PERIMG,      // gemm_tn_direct_kernel<false, true>: MssConvArgs.k_steps
   WG_TN_BF16X3 = MSS_WG_TN_BF16X3,                    // the split-bf16 TN kernel (gemm_bf16x3.hip): args->route == 1
   WG_TWO_PART = MSS_WG_TWO_PART,                      // K = 128 j + r: the first wide_K channels as one product, then the last r on WG_NARROW
+  WG_STEM7 = MSS_WG_STEM7,                            // stem7_wgrad_kernel (stem7_wgrad.hip): the 7x7 / stride-2 / 4 -> 64 stem, recognised in wgrad_resolve
 };
 
 struct WgradRoute {
@@ -308,6 +309,42 @@ static inline long long wgrad_workspace_bytes(const MssConvArgs& p, int Cp, cons
   return need;
 }
 
+// ---- The stem of the ResNet-50 backbone (stem7_wgrad.hip; the form is documented above mss_conv2d_wgrad_f32 in include/mss_hip.h).
+// It is recognised by wgrad_resolve in front of the general checks and never reaches wgrad_route.
+constexpr int WG_STEM7_TH = 4, WG_STEM7_TW = 16;      // output pixels of one tile of stem7_wgrad_kernel
+constexpr int WG_STEM7_MAX_SPLITS = 1024;             // four workgroups per CU (their LDS and registers allow it); every split writes a 50 KB slab
+static inline bool wg_stem7_form(const MssConvArgs& p, int Cp) {
+  return p.R == 7 && p.S == 7 && p.stride == 2 && p.pad == 3 && p.dil == 1 && p.C == 4 && p.ldx == 4 && p.K == 64 && p.Kpad == 64 && Cp == 4 &&
+         p.batch <= 1 && !p.in_scale && !p.in_shift && !p.in_relu && !p.k_steps;
+}
+static inline long long wg_stem7_tiles(const MssConvArgs& p) {
+  return (long long)p.N * wg_cdiv(p.OH, WG_STEM7_TH) * wg_cdiv(p.OW, WG_STEM7_TW);
+}
+// One workgroup per split: a run of consecutive tiles (image, tile row, tile column), at least two, accumulated in registers into ONE
+// [49][64][4] slab. rows_per_split counts the pixels of a split's tiles (tiles x 64, whatever part of them lies inside the map).
+static inline WgradRoute wg_plan_stem7(const MssConvArgs& p) {
+  WgradRoute r;
+  r.kernel = WG_STEM7;
+  r.ktiles = r.ctiles = 1; r.positions = 49;
+  const long long tiles = wg_stem7_tiles(p);
+  long long per = (tiles + WG_STEM7_MAX_SPLITS - 1) / WG_STEM7_MAX_SPLITS;
+  if (per < 2) per = 2;
+  r.splits = (int)((tiles + per - 1) / per);
+  r.rows_per_split = (int)(per * WG_STEM7_TH * WG_STEM7_TW);
+  r.total = r.splits;
+  wg_plan_slabs(r, p, 4);
+  return r;
+}
+// The stem form's own argument checks (p.M set, > 0). res: the stored stem output a0 of the pool form, or null.
+static inline int wg_stem7_check(const MssConvArgs& p, const float* dy, int lddy) {
+  if (p.H < 1 || p.W < 1 || p.OH != (p.H - 1) / 2 + 1 || p.OW != (p.W - 1) / 2 + 1) return MSS_ERR_BAD_ARG;
+  if (lddy < 64 || lddy % 4) return MSS_ERR_BAD_ARG;
+  if (p.res && (p.res_mask != 1 || p.ldres < 64 || p.ldres % 4)) return MSS_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(p.res)) & 15) return MSS_ERR_BAD_ARG;
+  if (wg_stem7_tiles(p) >= (1ll << 31) / (WG_STEM7_TH * WG_STEM7_TW)) return MSS_ERR_UNSUPPORTED;
+  return MSS_OK;
+}
+
 // ---- One call of mss_conv2d_wgrad_f32, resolved: its argument checks, the facts read off its pointers and the route(s) it launches.
 // The launch and the plan query (mss_conv2d_wgrad_plan) both go through wgrad_resolve, so they cannot disagree. No pointer is
 // dereferenced.
@@ -352,6 +389,13 @@ static inline int wgrad_resolve(const MssConvArgs* args, const float* dy, int ld
   MssConvArgs& p = c.p;
   p = *args;
   if (!p.x || !dy || !dwp) return MSS_ERR_BAD_ARG;
+  if (wg_stem7_form(p, Cp)) {      // the one form with R * S > 9; args->route is ignored (native fp32 MFMA)
+    p.M = p.N * p.OH * p.OW;
+    if (p.M <= 0) { c.empty = true; return MSS_OK; }
+    if (const int rc = wg_stem7_check(p, dy, lddy)) return rc;
+    c.route = wg_plan_stem7(p);
+    return MSS_OK;
+  }
   if (p.C % 4 || p.ldx % 4 || lddy % 4 || p.R * p.S > 9 || Cp % 4) return MSS_ERR_UNSUPPORTED;
   p.M = p.N * p.OH * p.OW;
   if (p.M <= 0) { c.empty = true; return MSS_OK; }

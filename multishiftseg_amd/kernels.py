@@ -1048,6 +1048,41 @@ def stem7_conv(img_nchw, weight, out_affine, relu=True):
     return out
 
 
+def stem7_wgrad(img_nchw, dy, a0=None):
+    """Weight gradient [64,3,7,7] of the 7x7 / stride-2 / padding-3 stem convolution (csrc/stem7_wgrad.hip, through
+    mss_conv2d_wgrad_f32) of the [N,3,H,W] NCHW image. a0 None: dy is the gradient dz at the convolution's output grid, Act
+    [N,(H-1)//2+1,(W-1)//2+1,64]. a0 (Act, the stored stem output after norm and ReLU): dy is the gradient at the max-pooled map
+    (3x3, stride 2, padding 1) and the kernel forms dz = [a0 > 0] * max-pool backward itself, the arg-max recomputed from a0 by
+    F.max_pool2d's rule (first maximum in row-major order). The image goes through image_to_nhwc(Cp=4), as stem7_conv's.
+    Native fp32 MFMA on either gemm route; deterministic."""
+    n, c, h, w = img_nchw.shape
+    if c != 3:
+        raise ValueError(f"the 7x7 stem expects a 3-channel image, got {tuple(img_nchw.shape)}")
+    if img_nchw.dtype != torch.float32 or not img_nchw.is_cuda:
+        raise TypeError("stem7_wgrad needs a float32 CUDA image")
+    OH, OW = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    grid = (n, OH, OW) if a0 is None else (n, (OH - 1) // 2 + 1, (OW - 1) // 2 + 1)
+    if (dy.N, dy.H, dy.W) != grid or dy.C != 64 or (a0 is not None and ((a0.N, a0.H, a0.W) != (n, OH, OW) or a0.C != 64)):
+        raise ValueError(f"stem7_wgrad: dy {(dy.N, dy.H, dy.W, dy.C)} / a0 {None if a0 is None else (a0.N, a0.H, a0.W, a0.C)} do not "
+                         f"belong to a {tuple(img_nchw.shape)} image")
+    x = image_to_nhwc(img_nchw, Cp=4)
+    dev = img_nchw.device
+    dwp = torch.empty((49, 64, 4), device=dev, dtype=torch.float32)                  # fully overwritten by the kernel
+    a = MssConvArgs()
+    a.x = x.ptr
+    a.N, a.H, a.W, a.C, a.ldx = n, h, w, 4, 4
+    a.OH, a.OW, a.K, a.Kpad = OH, OW, 64, 64
+    a.R, a.S, a.stride, a.dil, a.pad = 7, 7, 2, 1, 3
+    if a0 is not None:
+        a.res, a.ldres, a.res_mask = a0.ptr, a0.ld, 1
+    ws, ws_bytes = _wgrad_workspace(a, 4, dev)
+    with _Timed("conv_wgrad", 2.0 * n * OH * OW * 64 * 3 * 49, (n, h, w, 3, 64, 7, 2, 1)):
+        call("mss_conv2d_wgrad_f32", ctypes.byref(a), dy.ptr, dy.ld, ptr(dwp), 4, ptr(ws), ws_bytes)
+    grad = torch.empty((64, 3, 7, 7), device=dev, dtype=torch.float32)
+    call("mss_conv2d_unpack_wgrad_f32", ptr(dwp), ptr(grad), 64, 3, 7, 7, 64, 4, 0, None, None, 0, 0)
+    return grad
+
+
 class BNState:
     """Folded BatchNorm: y = x*scale + shift (+ what the backward needs in train mode)."""
     __slots__ = ("scale", "shift", "save_mean", "save_invstd", "M", "train")

@@ -50,12 +50,14 @@ class MaskFormer(nn.Module):
         self.size_divisibility = size_divisibility
         self._trainable = False
 
-    def set_trainable(self, flag=True):
+    def set_trainable(self, flag=True, stem=False):
         """Opt in to (or out of) the differentiable path of the backbone and the predictor (the pixel decoder has no switch: it follows
         its parameters' requires_grad). With it on and grad mode enabled forward() returns the predictor's training outputs for the
-        padded batch, so M2FTrainStep(head=model, ...) runs a whole-model step; off, or under torch.no_grad(), nothing changes."""
+        padded batch, so M2FTrainStep(head=model, ...) runs a whole-model step; off, or under torch.no_grad(), nothing changes.
+        stem: ResNet.set_trainable's second opt-in -- backbone.stem.conv1.weight is trained too (the reference's stage-2 set of 53
+        backbone weights with backbone.freeze(0, norms=True)); False (the default) refuses a trainable stem as before."""
         self._trainable = bool(flag)
-        self.backbone.set_trainable(flag)
+        self.backbone.set_trainable(flag, stem=stem)
         self.sem_seg_head.predictor.set_trainable(flag)
         return self
 

@@ -30,9 +30,14 @@ keeps ``a1``, ``a2`` and ``out`` of every block from the first trainable block o
   * data gradients: the forward kernels on flip-packed weights with s as the PROLOGUE scale (the flipped pack depends on the weight
     alone), gated by the stored activation through ``res_mask`` (a2 after conv3, a1 after conv2), summed at the block input through
     ``res=``; conv2 and shortcut of res3.0 / res4.0 / res5.0 run kernels.conv2d_dgrad_s2 (csrc/conv_dgrad_s2.hip);
-  * only what the ``requires_grad`` pattern asks for; nothing in front of the first trainable block.
-Not built: train-mode BatchNorm; a gradient for the image; a trainable stem (its weight gradient needs a 7x7 wgrad kernel and a
-max-pool backward). Without set_trainable() a backbone with trainable parameters raises under grad mode, as before.
+  * only what the ``requires_grad`` pattern asks for; nothing in front of the first trainable block;
+  * the stem weight, a second opt-in (``set_trainable(stem=True)``; a plain ``set_trainable()`` still refuses a trainable stem): the
+    stem output ``a0`` stays on the tape, the tape starts at res2.0, which is asked for its input gradient g at the pooled map, and the
+    walk ends with G = kernels.stem7_wgrad(image, g, a0) (csrc/stem7_wgrad.hip: the max-pool backward, its arg-max recomputed from a0,
+    and the ReLU gate run in the kernel's operand loader) and dW = s * G. The stem norm's weight and bias are never trained: the
+    reference's FrozenBatchNorm keeps them as buffers, and their dbeta would need dz materialised.
+Not built: train-mode BatchNorm; a gradient for the image; gradients of the stem norm's affine. Without set_trainable() a
+backbone with trainable parameters raises under grad mode, as before.
 """
 import torch
 from torch import nn
@@ -163,14 +168,16 @@ def _param_grads(conv, x, dz, stride, pad, grads):
 
 
 class _BackboneFn(torch.autograd.Function):
-    """image, the res2..res5 parameters that require a gradient -> the requested NCHW maps. The Acts between the blocks never become
-    tensors; the tape holds (block, x, a1, a2, out) from the first trainable block on."""
+    """image, the parameters that require a gradient (the stem weight first, where it is trained; then those of res2..res5) -> the
+    requested NCHW maps. The Acts between the blocks never become tensors; the tape holds (block, x, a1, a2, out) from the first
+    trainable block on -- from res2.0 on with a trainable stem, whose output a0 is kept beside it."""
 
     @staticmethod
     def forward(ctx, model, x, *params):
-        tape = []
-        out = model._run(x, tape, params)
+        tape, stem = [], {}
+        out = model._run(x, tape, params, stem)
         ctx.model, ctx.tape, ctx.params = model, tape, params
+        ctx.stem = (x.detach(), stem["a0"]) if stem else None
         ctx.ends = [id(getattr(model, n)[-1]) for n in out]          # the block whose `out` each returned map is
         return tuple(out.values())
 
@@ -192,8 +199,12 @@ class _BackboneFn(torch.autograd.Function):
                     K.nchw_into_rows(gin, g.ptr, g.ld, g.H * g.W * g.ld, accumulate=True)
             if g is None:
                 continue
-            g = blk.backward_act(g, x, a1, a2, out, i > 0, grads)
-        ctx.tape = None
+            g = blk.backward_act(g, x, a1, a2, out, i > 0 or ctx.stem is not None, grads)
+        if ctx.stem is not None and g is not None:                   # g: the gradient at the pooled map, res2.0's input
+            img, a0 = ctx.stem
+            conv1 = ctx.model.stem.conv1
+            grads[conv1.weight] = K.stem7_wgrad(img.float(), g, a0) * _folded(conv1)[0].view(-1, 1, 1, 1)
+        ctx.tape = ctx.stem = None
         return (None, None) + tuple(grads.get(p) for p in ctx.params)
 
 
@@ -225,14 +236,20 @@ class ResNet(nn.Module):
         if bad:
             raise NotImplementedError(f"ResNet (multishiftseg_amd): out_features among {self.stage_names}, got {bad}")
         self._out_features = list(out_features)
-        self._trainable = False
+        self._trainable = self._train_stem = False
         self.register_load_state_dict_pre_hook(_load_without_counters)
 
-    def set_trainable(self, flag=True):
+    def set_trainable(self, flag=True, stem=False):
         """Opt in to (or out of) the differentiable path: with the switch on, in eval mode and with grad mode enabled, forward() runs
         as one autograd node over the same kernels and the res2..res5 parameters that require a gradient receive one. Off (the
-        default) the backbone is forward-only, as before; under torch.no_grad() the switch makes no difference."""
+        default) the backbone is forward-only, as before; under torch.no_grad() the switch makes no difference.
+
+        stem=True (a second opt-in; without it a trainable stem raises as before): stem.conv1.weight receives a gradient too where
+        it requires one (kernels.stem7_wgrad). The stem norm's weight and bias still raise when they require a gradient: the
+        reference's FrozenBatchNorm never trains them, and their dbeta would need the stem's dz materialised, which the fused kernel
+        never does."""
         self._trainable = bool(flag)
+        self._train_stem = bool(flag) and bool(stem)
         return self
 
     def freeze(self, freeze_at=0, norms=False):
@@ -242,9 +259,10 @@ class ResNet(nn.Module):
 
         The reference config (anomaly_ft.yaml: FREEZE_AT 5, NORM "BN") turns every backbone norm into a FrozenBatchNorm2d, whose
         affine is a buffer, and stage 2's trainable_params_name_update ["."] then re-enables the convolution weights only. The
-        faithful stage-2 set-up here is therefore ``freeze(1, norms=True)``: all norm parameters frozen, stem.conv1.weight frozen
-        (the one deviation: a trainable stem is not built), the res2..res5 convolution weights trainable. Norm-parameter gradients
-        are built all the same, for users who keep the norms' affines as parameters."""
+        faithful stage-2 set-up here is therefore ``freeze(0, norms=True)`` with ``set_trainable(stem=True)``: all norm parameters
+        frozen, the 53 convolution weights (stem.conv1.weight and the 52 of res2..res5) trainable. ``freeze(1, norms=True)`` (the stem
+        weight frozen too, 52 weights) remains valid and needs no stem opt-in. Norm-parameter gradients are built all the same in
+        res2..res5, for users who keep the norms' affines as parameters; the stem norm's are not."""
         for idx, part in enumerate([self.stem] + [getattr(self, n) for n in self.stage_names], start=1):
             if freeze_at >= idx:
                 for p in part.parameters():
@@ -273,26 +291,38 @@ class ResNet(nn.Module):
             raise NotImplementedError("ResNet (multishiftseg_amd): no gradient for the image is built (the data gradient stops at the "
                                       "first trainable block); detach the image")
         stem = [n for n, p in self.stem.named_parameters() if p.requires_grad]
-        if stem:
-            raise NotImplementedError(f"ResNet (multishiftseg_amd): a trainable stem is not built (stem.{stem[0]} requires a gradient: "
-                                      "its weight gradient needs a 7x7 wgrad kernel and a max-pool backward); freeze(1) freezes it")
-        return tuple(p for name in self._run_stages() for p in getattr(self, name).parameters() if p.requires_grad)
+        norm = [n for n in stem if n != "conv1.weight"]
+        if norm and self._train_stem:
+            raise NotImplementedError(f"ResNet (multishiftseg_amd): a trainable stem norm is not built (stem.{norm[0]} requires a "
+                                      "gradient: the reference's FrozenBatchNorm never trains it, and its dbeta would need the stem's dz "
+                                      "materialised); freeze(0, norms=True) freezes the norms")
+        if stem and not self._train_stem:
+            raise NotImplementedError(f"ResNet (multishiftseg_amd): a trainable stem is not built (stem.{stem[0]} requires a gradient) "
+                                      "without its own opt-in: set_trainable(stem=True) trains stem.conv1.weight (never the stem "
+                                      "norm's affine); freeze(1) freezes the stem")
+        head = (self.stem.conv1.weight,) if stem else ()
+        return head + tuple(p for name in self._run_stages() for p in getattr(self, name).parameters() if p.requires_grad)
 
     def _run_stages(self):
         """The stages forward() runs: up to the last requested one."""
         last = max(self.stage_names.index(f) for f in self._out_features)
         return self.stage_names[:last + 1]
 
-    def _run(self, x, tape=None, params=()):
+    def _run(self, x, tape=None, params=(), stem=None):
         """stem -> stages -> {name: NCHW map}. tape (a list): from the first block that owns one of `params` on, every block leaves
-        (block, x, a1, a2, out) there -- the same kernel calls either way."""
+        (block, x, a1, a2, out) there -- the same kernel calls either way. stem (a dict): where the stem weight is among `params`
+        the stem output goes there as "a0" and the tape starts at res2.0."""
         conv1 = self.stem.conv1
-        y = K.maxpool3s2(K.stem7_conv(x.float(), conv1.weight, _folded(conv1), relu=True))
+        a0 = K.stem7_conv(x.float(), conv1.weight, _folded(conv1), relu=True)
+        y = K.maxpool3s2(a0)
         wanted = {id(p) for p in params}
+        from_start = stem is not None and id(conv1.weight) in wanted
+        if from_start:
+            stem["a0"] = a0
         out = {}
         for name in self._run_stages():
             for blk in getattr(self, name):
-                if tape is not None and (tape or any(id(p) in wanted for p in blk.parameters())):
+                if tape is not None and (tape or from_start or any(id(p) in wanted for p in blk.parameters())):
                     y = blk.forward_act_saving(y, tape)
                 else:
                     y = blk.forward_act(y)
