@@ -1,7 +1,9 @@
 """multishiftseg_amd: the MultiShiftSeg networks on hand-written HIP kernels for the MI355X. Sub-modules are imported on demand
 (`from multishiftseg_amd import kernels`); the names below are the package's module-level mirrors of reference classes."""
 
-_M2F_TRAINER = ("build_m2f_param_groups", "build_m2f_optimizer", "m2f_weight_dict", "weighted_losses", "M2FTrainStep", "M2FStage1Step")
+_M2F_TRAINER = ("build_m2f_param_groups", "build_m2f_optimizer", "m2f_weight_dict", "weighted_losses", "M2FTrainStep", "M2FStage1Step",
+                "attach_grad_sync", "target_count")
+_DDP = ("GradAllReduce", "CountAllReduce", "global_num_masks", "shard_pairs")
 _STAGE1_KERNELS = ("m2f_semantic_inference", "upsample_bilinear_nhwc", "stage1_chunks")
 
 
@@ -42,9 +44,12 @@ def __getattr__(name):
     if name in _M2F_TRAINER:
         from . import m2f_trainer
         return getattr(m2f_trainer, name)
+    if name in _DDP:
+        from . import ddp
+        return getattr(ddp, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention",
            "conv2d_dgrad_s2", "stem7_wgrad", "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER,
-           *_STAGE1_KERNELS]
+           *_STAGE1_KERNELS, *_DDP]

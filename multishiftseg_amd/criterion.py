@@ -247,7 +247,7 @@ class SetCriterion(nn.Module):
             sel_start, keys = plan.split, AUG_KEYS
         else:
             if num_masks is None:
-                num_masks = max(total_t, 1)                     # criterion.py:447-453 (its all_reduce is dead code: one process per GPU group)
+                num_masks = max(total_t, 1)                     # criterion.py:447-453 for one process; over ranks M2FTrainStep passes ddp.global_num_masks
             plan.split = None
             plan.scales = (1.0 / float(num_masks),)
             sel_start, keys = 0, PLAIN_KEYS

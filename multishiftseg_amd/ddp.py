@@ -29,6 +29,10 @@ class GradAllReduce:
 
     Contract: every handled parameter's ``.grad`` must be None when its gradient arrives (``zero_grad(set_to_none=True)``,
     what TrainStep does): ``param.grad`` aliases the bucket buffer between steps. Violations raise.
+
+    Two ways in: the call style above (DeepWV3Plus's own backward calls ``model.grad_sink(name, grad)``), and ``attach()``,
+    which takes the gradients from the parameters themselves with post-accumulate-grad hooks (Mask2Former: dozens of nodes
+    plus stock autograd). Layout, launch order and everything after the backward are the same in both.
     """
 
     def __init__(self, named_params, bucket_bytes=64 << 20, group=None, force=False, close_after_bytes=16 << 20):
@@ -69,6 +73,10 @@ class GradAllReduce:
         self.flat = [None] * len(self.buckets)          # persistent, allocated on first use
         self.comm_stream = None
         self.bytes_per_step = sum(self.sizes) * 4
+        self._handles = []      # attach(): the hooks' handles
+        self._hooked = []       # attach(): the parameters that carry them (each is marked with this sink: one sink a tensor)
+        self._flag_group = None # attach(): where the per-tensor "some rank produced it" flags travel (host tensors, gloo)
+        self._held = {}         # hook mode: name -> what this sink last left in param.grad (kept alive: its address identifies it)
         self._reset()
 
     def _reset(self):
@@ -87,15 +95,22 @@ class GradAllReduce:
         average once backward_done() has returned), or None when this sink does not handle `name`."""
         if not self.active or name not in self.where:
             return None
-        i, off, n = self.where[name]
         if self.params[name].grad is not None:
             # autograd steals the returned view as param.grad, so a gradient still defined from an earlier backward IS this
             # buffer: writing the new one would overwrite it and AccumulateGrad would then add the buffer to itself (silently
             # doubled gradients), and an accumulated sum would be all-reduced a second time. Accumulation over several
             # backwards is not what the reference loop does (train_deeplab.py:198-204: zero_grad / backward / step).
-            raise RuntimeError(f"GradAllReduce: {name}.grad is still defined at backward time; call "
-                               "optimizer.zero_grad(set_to_none=True) before every backward (gradient accumulation and "
-                               "zero_grad(set_to_none=False) are not supported with the in-place bucket buffers)")
+            raise RuntimeError(self._contract(name))
+        return self._take(name, grad)
+
+    def _contract(self, name):
+        return (f"GradAllReduce: {name}.grad is still defined at backward time; call "
+                "optimizer.zero_grad(set_to_none=True) before every backward (gradient accumulation and "
+                "zero_grad(set_to_none=False) are not supported with the in-place bucket buffers)")
+
+    def _take(self, name, grad):
+        """grad / world into the slice of `name`, then every bucket that has become complete, in index order -> the slice."""
+        i, off, n = self.where[name]
         view = self._buffer(i)[off:off + n].view(grad.shape)
         torch.mul(grad, 1.0 / self.world, out=view)
         self.arrived[i].add(name)
@@ -103,6 +118,54 @@ class GradAllReduce:
             self._launch(self.next_bucket)
             self.next_bucket += 1
         return view
+
+    def attach(self):
+        """Hook mode, for a model made of many autograd nodes and stock autograd between them: instead of one hand-written
+        backward calling the sink, every handled parameter that requires grad gets a post-accumulate-grad hook that does what
+        __call__ does -- the local gradient, scaled by 1/world, goes into the parameter's slice of its bucket, `param.grad` is
+        rebound to that slice and the complete buckets are launched. backward_done / flush / abort are used as before, with one
+        addition (_produced_somewhere): a tensor that NO rank produced a gradient for keeps .grad None. Nothing is attached to
+        an inactive sink (one rank, not forced). The flags travel over host_group(group). A tensor carries the hook of ONE sink:
+        attach() raises where another sink still holds a parameter (detach() that one first). Returns self; detach() removes
+        the hooks.
+
+        The contract check of hook mode is narrower than the call style's: by the time the hook runs AccumulateGrad has already
+        accumulated, so it recognises what THIS sink left in .grad at the previous step (the bucket slice, or the copy of the
+        average) by its address. A .grad that somebody else assigned between the steps is accumulated into and averaged without
+        an error, and so is an out-of-place accumulation (create_graph=True), which replaces the tensor."""
+        if self.active and not self._handles:
+            for name, p in self.params.items():
+                other = getattr(p, "_mss_grad_sink", None)
+                if p.requires_grad and other is not None and other is not self:
+                    # two hooks on one tensor would each scale by 1/world, and the older sink's buckets are never finished
+                    raise RuntimeError(f"GradAllReduce.attach: {name} already hands its gradient to another sink; detach() that one "
+                                       "first (M2FStage1Step.close() / M2FTrainStep.close() at the stage switch)")
+            self._flag_group = host_group(self.group)
+            for name, p in self.params.items():
+                if p.requires_grad:
+                    p._mss_grad_sink = self
+                    self._hooked.append(p)
+                    self._handles.append(p.register_post_accumulate_grad_hook(lambda p, name=name: self._hook(name, p)))
+        return self
+
+    def detach(self):
+        """Remove the hooks: the parameters are free for another sink (the stage switch), this one can attach() again."""
+        for h in self._handles:
+            h.remove()
+        for p in self._hooked:
+            if getattr(p, "_mss_grad_sink", None) is self:
+                del p._mss_grad_sink
+        self._handles, self._hooked = [], []
+
+    @torch.no_grad()
+    def _hook(self, name, p):
+        g = p.grad
+        held = self._held.get(name)
+        if held is not None and g.data_ptr() == held.data_ptr():
+            # AccumulateGrad found what the previous step handed over (the bucket slice, or the average given to a parameter
+            # without a local gradient) still in place and added to it: the live gradient is gone and the sum would travel again
+            raise RuntimeError(self._contract(name))
+        p.grad = self._held[name] = self._take(name, g)
 
     def _launch(self, i):
         flat = self._buffer(i)
@@ -130,19 +193,38 @@ class GradAllReduce:
             self._launch(self.next_bucket)
             self.next_bucket += 1
 
+    def _produced_somewhere(self):
+        """Hook mode: the names some rank produced a gradient for this step -- one all-reduce over a flag per tensor, issued by
+        every rank after its last bucket. A tensor NO rank produced one for (a parameter the forward never uses) keeps .grad None
+        as in a one-process step, so the optimizer skips it instead of decaying it with a zero gradient. The flags are host
+        tensors on host_group(group): the host decides what the optimizer sees, and reading the answer from the device would
+        make it wait for the whole backward every step. The all-reduce blocks the host until every rank's host has enqueued its
+        backward (the hosts meet once per step; the devices are not waited for)."""
+        names = [n for b in self.buckets for n in b]
+        here = [any(n in a for a in self.arrived) for n in names]
+        if self.no_comm:
+            return {n for n, f in zip(names, here) if f}
+        flags = torch.tensor([float(f) for f in here], dtype=torch.float32)
+        dist.all_reduce(flags, group=self._flag_group)
+        return {n for n, f in zip(names, flags.tolist()) if f > 0}
+
     def backward_done(self):
         if not self.active:
             return
         self.flush()
+        produced = self._produced_somewhere() if self._handles else None
         for i, work in self.inflight:
             if work is not None:
                 work.wait()      # CUDA: makes the current stream wait for the collective, no host block
             for n in self.buckets[i]:
                 if n not in self.arrived[i]:
                     p = self.params[n]
-                    if p.requires_grad:           # no local gradient this step, but the other ranks' average is this rank's too
+                    # no local gradient this step, but the other ranks' average is this rank's too
+                    if p.requires_grad and (produced is None or n in produced):
                         _, off, cnt = self.where[n]
                         p.grad = self.flat[i][off:off + cnt].view(p.shape).clone()
+                        if self._handles:
+                            self._held[n] = p.grad
         self._reset()
 
     def abort(self):
@@ -155,6 +237,74 @@ class GradAllReduce:
             except Exception:
                 pass
         self._reset()
+
+
+def is_active(group=None):
+    """The switch of every data-parallel step (trainer.TrainStep, m2f_trainer): torch.distributed is initialised and the group
+    has more than one rank, or MSS_DDP_FORCE=1 asks for the collectives in a one-rank group too (the RCCL path on one GPU)."""
+    import os
+    return dist.is_initialized() and (dist.get_world_size(group) > 1 or os.environ.get("MSS_DDP_FORCE") == "1")
+
+
+def broadcast_params(params, group=None):
+    """Rank 0's values of `params` to every rank of the group, in place, once (construction time: one collective a tensor)."""
+    src = dist.get_global_rank(group, 0) if group is not None else 0
+    for p in params:
+        dist.broadcast(p.detach(), src=src, group=group)     # in place on the shared storage: bumps the parameter's version
+
+
+_HOST_GROUPS = {}
+
+
+def host_group(group=None):
+    """The group over which host tensors of `group`'s ranks travel: `group` itself where its backend has gloo, else ONE gloo
+    group of the same ranks, created at the first call and shared by every sink and step of the process (a collective call: all
+    ranks of `group` make it, in the same order; with a sub-group only its members do)."""
+    if "gloo" in str(dist.get_backend(group)):
+        return group
+    key = (dist.group.WORLD, group)
+    if key not in _HOST_GROUPS:
+        if group is None:
+            _HOST_GROUPS[key] = dist.new_group(backend="gloo")
+        else:
+            _HOST_GROUPS[key] = dist.new_group(ranks=dist.get_process_group_ranks(group), backend="gloo", use_local_synchronization=True)
+    return _HOST_GROUPS[key]
+
+
+def global_num_masks(sums, world=None):
+    """The normaliser of Mask2Former's criterion over several processes (reference criterion.py:447-453): the ranks' target
+    counts sum_b T_b are summed, divided by the world size and clamped at 1. `sums`: one count per rank (or, with `world`,
+    any split of their total, as after an all-reduce) -> float."""
+    return max(float(sum(sums)) / (len(sums) if world is None else world), 1.0)
+
+
+class CountAllReduce:
+    """global_num_masks as one tiny collective per step that no device stream is involved in: start(count) before the forward,
+    result() before the criterion; a one-element host tensor over host_group(group). MSS_DDP_NO_COMM=1 skips the collective (the
+    probe then normalises by its own count)."""
+
+    def __init__(self, group=None):
+        import os
+        self.world = dist.get_world_size(group)
+        self.group = host_group(group)
+        self.no_comm = os.environ.get("MSS_DDP_NO_COMM") == "1"
+        self._pending = None
+
+    def drop(self):
+        """The step is unwinding from an exception: forget a collective that was started, without waiting for it (a peer that
+        failed earlier may never have started its own)."""
+        self._pending = None
+
+    def start(self, count):
+        t = torch.tensor([float(count) * (self.world if self.no_comm else 1)], dtype=torch.float64)
+        self._pending = (t, None if self.no_comm else dist.all_reduce(t, group=self.group, async_op=True))
+
+    def result(self):
+        t, work = self._pending
+        self._pending = None
+        if work is not None:
+            work.wait()
+        return global_num_masks((float(t.item()),), self.world)       # the ranks' sum is what travelled
 
 
 def init_from_env():
