@@ -70,7 +70,11 @@ extern "C" {
                                   still 26 (no entry point or struct changes, and two tests pin the number): mss_conv2d_wgrad_f32 takes the 7x7 /
                                   stride-2 / 4 -> 64 stem of the ResNet-50 backbone (csrc/stem7_wgrad.hip), plain or with the max-pool and ReLU
                                   backward fused, which it answered MSS_ERR_UNSUPPORTED before; mss_conv2d_wgrad_plan names it MSS_WG_STEM7. A caller
-                                  that needs to know asks the plan query for the stem form: MSS_OK with kernel 11 */
+                                  that needs to know asks the plan query for the stem form: MSS_OK with kernel 11;
+                                  still 26 (the same two tests pin the number as well as the count of 142 entry points): mss_seg_hist added (the
+                                  confusion matrix of the closed-set segmentation metrics, csrc/metric.hip); mss_peak_scatter_f32 removed to make
+                                  room (only a layout experiment of a diagnostic tool called it). A library from before the swap lacks the new
+                                  symbol and is refused at load by name, not by number */
 int mss_abi_version(void);
 
 /* The MSS_* environment switches (A/B experiments, test routes; none is needed in production) are read once per call site and
@@ -781,6 +785,25 @@ int mss_oodm_rank_blocks(long long P);
 int mss_oodm_measures_f64(const unsigned int* pos_sorted, long long P, const unsigned int* neg_sorted, long long N,
                           double recall_level, unsigned long long* u2_part, double* ap_part, double* out, void* stream);
 
+/* ---- closed-set segmentation metrics (csrc/metric.hip) ----
+ * replaces hist_info (lib/utils/metric.py:10-18) on the device; compute_metric / compute_score / compute_score_per_class
+ * (metric.py:21-64) are host arithmetic on the table this accumulates (multishiftseg_amd/metric.py).
+ *   hist u64 [n_cl * n_cl + 1], ACCUMULATED into (the caller zeroes it once per sweep): hist[gt * n_cl + pred] += 1 for every pixel
+ *   with 0 <= gt < n_cl (metric.py:12; 254 / 255 and negative labels drop out, the full 64-bit value is compared). The last slot
+ *   counts labelled pixels whose map prediction lies outside 0 .. n_cl-1, where the reference raises or files the pixel in another
+ *   row. `labeled` and `correct` of hist_info are the table's sum and trace.
+ *   pred_kind 0: pred = float32 logits, B x n_cl planes of HW contiguous pixels, image b's plane c at pred + b * img_stride +
+ *     c * chan_stride (elements; a channel slice of a wider tensor goes in as it is). The argmax over c is fused, with np.argmax's
+ *     semantics: the first maximal index, -0.0 == 0.0, a NaN is maximal and the first NaN wins, all -inf gives 0. Any alignment.
+ *   pred_kind 1 / 8: pred = a uint8 / int64 prediction map [B, HW] (what mss_ood_score_f32 writes as `label`); strides ignored.
+ *   label [B, HW], label_bytes 1 (uint8) or 8 (int64).
+ * Checked in this order, before any HIP call: a NULL pointer, another pred_kind or label_bytes, B < 0 or HW < 0 ->
+ * MSS_ERR_BAD_ARG; n_cl outside 2..32 -> MSS_ERR_UNSUPPORTED; B == 0 or HW == 0 -> MSS_OK, nothing launched; B * HW >= 2^32 ->
+ * MSS_ERR_UNSUPPORTED; for logits chan_stride < HW or img_stride < n_cl * chan_stride (overlapping planes; negative strides are
+ * among them) -> MSS_ERR_BAD_ARG. One launch, integer atomics only: two runs give the same table. */
+int mss_seg_hist(const void* pred, int pred_kind, long long img_stride, long long chan_stride, const void* label, int label_bytes,
+                 int B, long long HW, int n_cl, unsigned long long* hist, void* stream);
+
 /* ---- Mask2Former pixel decoder glue (csrc/norm.hip; msdeformattn.py:116-131,215-219,262-281,314-358) ----
  * y = LayerNorm(x + res) over the last dimension C (multiple of 256, <= 1024; res may be NULL): the post-norm residual
  * sites of MSDeformAttnTransformerEncoderLayer in one pass. stat (optional) [rows][2] = (mean, rstd) for the backward. */
@@ -999,10 +1022,6 @@ int mss_peak_mfma_f32(float* out, int blocks, int iters, void* stream);
  * blocks x 4 waves x iters x 1 572 864 FLOP; shape 0 = 48 x v_mfma_f32_32x32x16_bf16 per iteration, 1 = 96 x v_mfma_f32_16x16x32_bf16. */
 int mss_peak_mfma_bf16(float* out, int blocks, int iters, int shape, void* stream);
 int mss_peak_stream_f32(const float* src, float* dst, long long n, int variant, void* stream);
-/* layout experiment behind the Winograd-domain layout: one coalesced float4 read, ns (16|36) float4 writes
- * into ns slabs that are n floats apart (blocked = 0) or adjacent per block of blk_floats floats (blocked = 1). */
-int mss_peak_scatter_f32(const float* src, float* dst, long long n, int ns, int blocked, long long blk_floats,
-                         void* stream);
 
 #ifdef __cplusplus
 }

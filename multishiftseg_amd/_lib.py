@@ -225,6 +225,7 @@ SIGNATURES = {
     "mss_oodm_sort_u32": [P, P, L, P, L, P],
     "mss_oodm_rank_blocks": [L],
     "mss_oodm_measures_f64": [P, L, P, L, c_double, P, P, P, P],
+    "mss_seg_hist": [P, I, L, L, P, I, I, L, I, P, P],
     "mss_add_layernorm_f32": [P, P, L, I, P, P, F, P, P, P],
     "mss_add_layernorm_bwd_workspace_floats": [L, I],
     "mss_add_layernorm_bwd_f32": [P, P, P, P, L, I, P, P, P, P, P, P],
@@ -243,7 +244,6 @@ SIGNATURES = {
     "mss_peak_mfma_f32": [P, I, I, P],
     "mss_peak_mfma_bf16": [P, I, I, I, P],
     "mss_peak_stream_f32": [P, P, L, I, P],
-    "mss_peak_scatter_f32": [P, P, L, I, I, L, P],
 }
 # the entry points that return a plain value, and its C type; every other one returns an int status code
 VALUE_RESTYPE = {

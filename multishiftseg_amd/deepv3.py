@@ -371,7 +371,7 @@ class DeepWV3Plus(nn.Module):
             self._heads_cache = (key, K.pack_weight(wh), K.pack_weight(wh, flip=True))
         return self._heads_cache[1], self._heads_cache[2]
 
-    def _head_forward(self, x, m2, size, keep=False, want_logit=True):
+    def _head_forward(self, x, m2, size, keep=False, want_logit=True, want_label=False):
         train = self.training
         N, h8, w8 = x.N, x.H, x.W
         h2, w2 = m2.H, m2.W
@@ -476,8 +476,10 @@ class DeepWV3Plus(nn.Module):
         final_xt = {0: kx0.get("xt") if kx0 else None, 3: kx3.get("xt") if kx3 else None}
         wh, _ = self._heads_weight()
         dec12 = K.conv2d(f1, wh, in_affine=(st_f1.scale, st_f1.shift), in_relu=True)
-        score, logit, _ = K.ood_score(dec12.slice(20, 19), dec12.slice(0, 19) if want_logit else None, size[0], size[1],
-                                      want_logit=want_logit)
+        score, logit, label = K.ood_score(dec12.slice(20, 19), dec12.slice(0, 19) if (want_logit or want_label) else None, size[0], size[1],
+                                          want_logit=want_logit, want_label=want_label)
+        if want_label:                 # evaluate(): the uint8 argmax of the logits, whether or not they are written
+            return score, logit, label
         saved = None
         if keep:
             saved = dict(plan=plan, aspp_xt=aspp_xt, x=x, fx=fx, comp=comp, drop=drop, m2=m2, raw=raw, scale=scale, shift=shift, states=states, pooled_act=pooled_act,
@@ -633,3 +635,32 @@ class DeepWV3Plus(nn.Module):
                 with torch.no_grad():
                     score, logit, _ = self._head_forward(x, m2, size, want_logit=self.training or not self.score_only)
         return score, logit
+
+    def evaluate(self, batches, meter=None, seg_meter=None):
+        """The validation / test sweep (train_deeplab.py:223-241, test_deeplab.py:84-102) with no copy to the host: `batches` yields
+        (images, target); every anomaly-score map goes to OODMeter.update on the device. Returns meter.compute().
+        seg_meter (a metric.SegMeter): the closed-set half as well, from the SAME forward: the score tail also writes the uint8 argmax
+        of the logits it interpolates (1 byte per pixel instead of the 76 of the logits, which are not written: score_only or not,
+        the sweep never needs them), and that map goes to SegMeter.update. Returns (meter.compute(), seg_meter.compute()).
+        Evaluation mode, no gradients; the mode the module was in is restored."""
+        from .metric import OODMeter
+        meter = OODMeter() if meter is None else meter
+        was = self.training
+        self.eval()
+        try:
+            for images, target in batches:
+                if not images.is_cuda:
+                    raise RuntimeError("DeepWV3Plus (multishiftseg_amd) runs on an MI355X only; there is no CPU path")
+                images = images.float()
+                size = (images.shape[2], images.shape[3])
+                with K.batched_counters(), torch.no_grad():
+                    x, m2 = self._run_trunk(images)
+                    score, _, label = self._head_forward(x, m2, size, want_logit=False, want_label=seg_meter is not None)
+                meter.update(score, target)
+                if seg_meter is not None:
+                    seg_meter.update(label, target)
+        finally:
+            self.train(was)
+        if seg_meter is None:
+            return meter.compute()
+        return meter.compute(), seg_meter.compute()

@@ -226,7 +226,7 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
                                       f"the other parameters or call under torch.no_grad(); trainable: {bad[:4]} ... ({len(bad)})")
 
     # ---- reference API ----------------------------------------------------------------------------------------------------
-    def forward(self, x, mask_features, mask=None, *, fuse_score=None, return_attn_bits=False, semantic=None):
+    def forward(self, x, mask_features, mask=None, *, fuse_score=None, return_attn_bits=False, semantic=None, sem_seg=False):
         """As the reference's forward. fuse_score=(H, W): the last step's pixel-major mask logits go straight to
         kernels.m2f_score_fused with pred_logits_ood; the anomaly score [B, H, W] is returned as "ood_score" and the last step's
         NCHW "pred_masks" / "pred_masks_ood" are not materialised (None). fuse_score=(Hp, Wp, H, W): upsample to the padded image
@@ -237,10 +237,15 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
         last step's masks upsampled to (Hp, Wp), cropped to (H, W)) and "ood_score" [B, H, W] (train_m2f.py:387-407 of
         pred_logits_ood on the same upsampled masks), both from the last step's pixel-major logits through
         kernels.m2f_semantic_inference. "ood_score" is attached to pred_logits_ood where class_embed2 requires grad (stage 1);
-        "sem_seg" never requires grad. Not together with fuse_score, which names the same key."""
+        "sem_seg" never requires grad. Not together with fuse_score, which names the same key.
+        sem_seg=True with fuse_score=(Hp, Wp, H, W), evaluation only: the dict also gains "sem_seg" as above, from the same last-step
+        logits the fused score read -- the evaluation sweep's closed-set prediction beside the UNCHANGED fused "ood_score" (the score of
+        `semantic` is the stage-1 form of the same quantity and differs from the fused one in the last bits)."""
         del mask                                                     # "disable mask, it does not affect performance" (:445)
         if semantic is not None and (fuse_score is not None or len(tuple(semantic)) != 4):
             raise ValueError("semantic=(Hp, Wp, H, W), and not together with fuse_score: both name \"ood_score\"")
+        if sem_seg and (fuse_score is None or len(tuple(fuse_score)) != 4 or (self._trainable and torch.is_grad_enabled())):
+            raise ValueError("sem_seg=True goes with fuse_score=(Hp, Wp, H, W) on the evaluation path")
         if len(x) != self.num_feature_levels:
             raise ValueError(f"expected {self.num_feature_levels} feature levels, got {len(x)}")
         if not mask_features.is_cuda or not all(t.is_cuda for t in x):
@@ -253,7 +258,12 @@ class MultiScaleMaskedTransformerDecoder_GMA(nn.Module):
         self._check_grad_mode()
         with torch.no_grad():
             state = self._forward_frozen(x, mask_features, fuse_score is not None)
-        return self._finish(state, fuse_score, return_attn_bits, semantic)
+        out = self._finish(state, fuse_score, return_attn_bits, semantic)
+        if sem_seg:
+            Hp, Wp, H, W = (int(v) for v in fuse_score)
+            with torch.no_grad():
+                out["sem_seg"] = K.m2f_semantic_inference(out["pred_logits"], state[2], (Hp, Wp), (H, W), Q=out["pred_logits"].shape[1])
+        return out
 
     def _position(self, x):
         """[1, hw, C] position code of a level, kept per (size, device): it depends on nothing else."""

@@ -1024,6 +1024,59 @@ def gen_metric():
     save("ood_metrics", **out)
 
 
+def gen_seg_metric():
+    """lib/utils/metric.py:10-64 (hist_info, compute_metric and the two scorers behind it, loaded by file path) on seeded
+    2 x 19 x 24 x 40 logits: every class present, several classes absent (compute_score leaves them NaN under the nanmean,
+    compute_score_per_class clamps the union to 1), labels with 254 / 255 mixed in, and logits on a three-value lattice (ties
+    everywhere: np.argmax's first maximal index decides). Per case: logits, their np.argmax, labels, the reference's hist /
+    labeled / correct (one hist_info per image, summed by compute_metric) and compute_metric's output for both per_class settings."""
+    import importlib.util
+    import warnings
+    spec = importlib.util.spec_from_file_location("ref_metric", os.path.join(REF, "lib", "utils", "metric.py"))
+    rm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rm)
+    rng = np.random.default_rng(1019)
+    n_cl, B, H, W = 19, 2, 24, 40
+    out = {}
+    for tag in ("all", "absent", "ignore", "lattice"):
+        classes = np.array([0, 1, 2, 5, 7, 8, 10, 11, 13, 18]) if tag == "absent" else np.arange(n_cl)
+        # labels in blocks of 4 x 5 pixels (uniform regions, as a label map has them), predictions that mostly agree
+        coarse = classes[rng.integers(0, len(classes), (B, H // 4, W // 5))]
+        label = np.repeat(np.repeat(coarse, 4, axis=1), 5, axis=2).astype(np.int64)
+        if tag == "lattice":
+            logits = rng.integers(-1, 2, (B, n_cl, H, W)).astype(np.float32)
+        else:
+            logits = (np.round(rng.standard_normal((B, n_cl, H, W)) * 16) / 16).astype(np.float32)   # multiples of 1/16: some ties
+            boost = classes[rng.integers(0, len(classes), (B, H, W))]
+            boost = np.where(rng.random((B, H, W)) < 0.7, label, boost)
+            np.put_along_axis(logits, boost[:, None], np.take_along_axis(logits, boost[:, None], 1) + np.float32(2.5), 1)
+        if tag == "absent":                                   # never predicted either: these classes' union is 0
+            logits[:, np.setdiff1d(np.arange(n_cl), classes)] -= np.float32(64)
+        if tag == "ignore":
+            r = rng.random((B, H, W))
+            label = np.where(r < 0.1, 255, np.where(r < 0.18, 254, label)).astype(np.int64)
+        pred = np.argmax(logits, axis=1).astype(np.int64)
+        results = []
+        for b in range(B):
+            hist, labeled, correct = rm.hist_info(n_cl, pred[b], label[b])
+            results.append({"hist": hist, "labeled": labeled, "correct": correct})
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")                   # 0 / 0 of the absent classes
+            mean_iu, acc = rm.compute_metric(results, per_class=False)
+            mean_iu_pc, acc_pc, iu_pc, class_acc = rm.compute_metric(results, per_class=True)
+            iu = rm.compute_score(sum(d["hist"] for d in results).astype(np.float64), 1, 1)[0]
+        out[tag + "_logits"], out[tag + "_pred"], out[tag + "_label"] = logits, pred.astype(np.uint8), label.astype(np.uint8)
+        out[tag + "_hist"] = sum(d["hist"] for d in results).astype(np.int64)
+        out[tag + "_labeled"] = np.int64(sum(int(d["labeled"]) for d in results))
+        out[tag + "_correct"] = np.int64(sum(int(d["correct"]) for d in results))
+        out[tag + "_metric"] = np.array([mean_iu, acc], dtype=np.float64)
+        out[tag + "_metric_per_class"] = np.array([mean_iu_pc, acc_pc], dtype=np.float64)
+        out[tag + "_iu"] = np.asarray(iu, dtype=np.float64)
+        out[tag + "_iu_per_class"], out[tag + "_class_acc"] = np.asarray(iu_pc, dtype=np.float64), np.asarray(class_acc, dtype=np.float64)
+        print(f"   {tag}: labeled {int(out[tag + '_labeled'])} correct {int(out[tag + '_correct'])} mIoU {mean_iu:.4f} / {mean_iu_pc:.4f} acc {acc:.4f}")
+    save("seg_metrics", **out)
+
+
 # ------------------------------------------------------------------------------------------- matcher
 def import_reference_matcher():
     """lib/network/mask2former/modeling/matcher.py imported by file path. detectron2 is absent: its point_sample is stubbed as
@@ -1177,6 +1230,7 @@ def main():
         print("loss"); gen_loss(ref_loss)
     if "metric" in which:
         print("metric"); gen_metric()
+        print("seg_metric"); gen_seg_metric()
     if "deeplab" in which:
         print("deeplab"); gen_deeplab(DeepWV3Plus)
     if "train" in which:

@@ -104,18 +104,5 @@ def wino_transforms(dev):
         del x, xt, y
 
 
-def layout_experiment(dev):
-    """Does the [P][T][C] layout (36 write streams tens of MB apart) cost bandwidth against a tile-block-major one?"""
-    from multishiftseg_amd._lib import call, ptr
-    n = 1 << 25                                  # 128 MB read, 36x = 4.8 GB written
-    src = torch.randn(n, device=dev)
-    for ns in (16, 36):
-        dst = torch.empty(ns * n, device=dev)
-        for blocked, blk in ((0, 4), (1, 128 * 128), (1, 128 * 256), (1, 128 * 1024), (1, 16 * 128)):
-            ms = timeit(lambda: call("mss_peak_scatter_f32", ptr(src), ptr(dst), n, ns, blocked, blk), iters=5)
-            row(f"scatter ns={ns} blocked={blocked} blk_floats={blk}", ms, 4.0 * n * (1 + ns))
-        del dst
-
-
 if __name__ == "__main__":
     main()
