@@ -3,7 +3,7 @@
 
 _M2F_TRAINER = ("build_m2f_param_groups", "build_m2f_optimizer", "m2f_weight_dict", "weighted_losses", "M2FTrainStep", "M2FStage1Step",
                 "attach_grad_sync", "target_count")
-_DDP = ("GradAllReduce", "CountAllReduce", "global_num_masks", "shard_pairs")
+_DDP = ("GradAllReduce", "CountAllReduce", "global_num_masks", "shard_pairs", "shard_batches")
 _STAGE1_KERNELS = ("m2f_semantic_inference", "upsample_bilinear_nhwc", "stage1_chunks")
 
 

@@ -342,3 +342,31 @@ def init_from_env():
 def shard_pairs(num_pairs, rank, world):
     """Pairs owned by `rank`: {k : k mod world == rank}."""
     return list(range(rank, num_pairs, world))
+
+
+def shard_batches(batches, rank=None, world=None, group=None):
+    """A rank's share of a validation sweep: the items k of any iterable with k mod world == rank (shard_pairs' rule), as a
+    generator -- the iterable is walked once and never asked for its length. `rank` / `world` default to the group's, and to 0 / 1
+    without an initialised process group. A rank beyond the item count gets nothing and still takes part in the collectives of
+    evaluate(group=)."""
+    up = dist.is_available() and dist.is_initialized()
+    if world is None:
+        world = dist.get_world_size(group) if up else 1
+    if rank is None:
+        rank = dist.get_rank(group) if up else 0
+    for k, item in enumerate(batches):
+        if k % world == rank:
+            yield item
+
+
+def gather_meters(group, meter, seg_meter=None):
+    """The end of a sharded sweep (DeepWV3Plus.evaluate / MaskFormer.evaluate with group=): every rank of the group calls this
+    once, a rank whose shard was empty too. `group` True stands for the default group. The OOD keys are gathered
+    (OODMeter.all_gather), the confusion matrix is summed (SegMeter.all_reduce). A rank that raised inside its sweep never gets
+    here: its peers wait in the collective until the process group's timeout ends them. There is no protocol for that."""
+    group = None if group is True else group
+    meter.all_gather(group)
+    if seg_meter is not None:
+        if seg_meter._table is None and torch.cuda.is_available() and is_active(group):
+            seg_meter._counters(torch.device("cuda", torch.cuda.current_device()))      # an empty shard: a table where the peers' are
+        seg_meter.all_reduce(group)

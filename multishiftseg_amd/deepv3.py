@@ -636,13 +636,18 @@ class DeepWV3Plus(nn.Module):
                     score, logit, _ = self._head_forward(x, m2, size, want_logit=self.training or not self.score_only)
         return score, logit
 
-    def evaluate(self, batches, meter=None, seg_meter=None):
+    def evaluate(self, batches, meter=None, seg_meter=None, group=None):
         """The validation / test sweep (train_deeplab.py:223-241, test_deeplab.py:84-102) with no copy to the host: `batches` yields
         (images, target); every anomaly-score map goes to OODMeter.update on the device. Returns meter.compute().
         seg_meter (a metric.SegMeter): the closed-set half as well, from the SAME forward: the score tail also writes the uint8 argmax
         of the logits it interpolates (1 byte per pixel instead of the 76 of the logits, which are not written: score_only or not,
         the sweep never needs them), and that map goes to SegMeter.update. Returns (meter.compute(), seg_meter.compute()).
-        Evaluation mode, no gradients; the mode the module was in is restored."""
+        Evaluation mode, no gradients; the mode the module was in is restored.
+        group (a process group, or True for the default one): the sweep is split over the ranks. Each rank consumes the `batches` it
+        is given -- the caller shards them, e.g. ddp.shard_batches(loader) -- and after the loop every rank, one with an empty shard
+        too, gathers the OOD keys and sums the confusion matrix (ddp.gather_meters), so every rank returns what one process
+        returns over all batches, bit for bit. A rank that raises inside its sweep raises before the collective: its
+        peers wait there until the process group's timeout. None: no collective, the sweep of one process."""
         from .metric import OODMeter
         meter = OODMeter() if meter is None else meter
         was = self.training
@@ -661,6 +666,9 @@ class DeepWV3Plus(nn.Module):
                     seg_meter.update(label, target)
         finally:
             self.train(was)
+        if group is not None:
+            from . import ddp
+            ddp.gather_meters(group, meter, seg_meter)
         if seg_meter is None:
             return meter.compute()
         return meter.compute(), seg_meter.compute()

@@ -117,29 +117,39 @@ class MaskFormer(nn.Module):
         out = self._semantic(images)
         return out["sem_seg"], out["ood_score"]
 
-    def evaluate(self, batches, meter=None, seg_meter=None):
+    def evaluate(self, batches, meter=None, seg_meter=None, group=None):
         """valid_batch / test (train_m2f.py:469-509, test_m2f.py:109-158) with no copy to the host: `batches` yields (images, target);
         every score map goes to OODMeter.update on the device. Returns meter.compute().
         seg_meter (a metric.SegMeter): the closed-set half of the sweep as well -- ONE forward per batch feeds both meters, its
         "ood_score" the OODMeter and its "sem_seg" logits the SegMeter (the argmax is fused into the count). The score is the fused
         one of the sweep without a seg_meter, so the OOD measures are the same numbers; sem_seg is semantic_inference's map, built
-        from the same last-step mask logits. Returns (meter.compute(), seg_meter.compute())."""
+        from the same last-step mask logits. Returns (meter.compute(), seg_meter.compute()).
+        group (a process group, or True for the default one): the sweep is split over the ranks. Each rank consumes the `batches` it
+        is given -- the caller shards them, e.g. ddp.shard_batches(loader) -- and after the loop every rank, one with an empty shard
+        too, gathers the OOD keys and sums the confusion matrix (ddp.gather_meters), so every rank returns what one process
+        returns over all batches, bit for bit. A rank that raises inside its sweep raises before the collective: its
+        peers wait there until the process group's timeout. None: no collective, the sweep of one process."""
         meter = OODMeter() if meter is None else meter
         if seg_meter is None:
             for images, target in batches:
                 meter.update(self.ood_score(images), target)
+        else:
+            if self._trainable:
+                raise RuntimeError("MaskFormer: sem_seg runs on the evaluation path of the backbone and the predictor: set_trainable(False) first")
+            for images, target in batches:
+                if images.dim() != 4 or images.shape[1] != 3:
+                    raise ValueError(f"MaskFormer takes [B, 3, H, W] image batches, got {tuple(images.shape)}")
+                H, W = images.shape[-2:]
+                with torch.no_grad():
+                    x = self.pad(images.float())
+                    features = self.backbone(x)
+                    mask_features, _, multi_scale = self.sem_seg_head.pixel_decoder.forward_features(features)
+                    out = self.sem_seg_head.predictor(multi_scale, mask_features, None, fuse_score=(x.shape[-2], x.shape[-1], H, W), sem_seg=True)
+                meter.update(out["ood_score"], target)
+                seg_meter.update(out["sem_seg"], target)
+        if group is not None:
+            from . import ddp
+            ddp.gather_meters(group, meter, seg_meter)
+        if seg_meter is None:
             return meter.compute()
-        if self._trainable:
-            raise RuntimeError("MaskFormer: sem_seg runs on the evaluation path of the backbone and the predictor: set_trainable(False) first")
-        for images, target in batches:
-            if images.dim() != 4 or images.shape[1] != 3:
-                raise ValueError(f"MaskFormer takes [B, 3, H, W] image batches, got {tuple(images.shape)}")
-            H, W = images.shape[-2:]
-            with torch.no_grad():
-                x = self.pad(images.float())
-                features = self.backbone(x)
-                mask_features, _, multi_scale = self.sem_seg_head.pixel_decoder.forward_features(features)
-                out = self.sem_seg_head.predictor(multi_scale, mask_features, None, fuse_score=(x.shape[-2], x.shape[-1], H, W), sem_seg=True)
-            meter.update(out["ood_score"], target)
-            seg_meter.update(out["sem_seg"], target)
         return meter.compute(), seg_meter.compute()

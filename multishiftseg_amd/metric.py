@@ -35,7 +35,12 @@ def _flat(score, label):
 
 
 class OODMeter:
-    """update(anomaly_score, target) per batch, compute() at the end of the sweep."""
+    """update(anomaly_score, target) per batch, compute() at the end of the sweep.
+
+    The state is a multiset of 32-bit order-preserving keys per class, and compute() sorts before it measures: the union of two
+    meters' keys therefore measures exactly what one meter fed both meters' maps does, whatever the order. merge() forms that
+    union in one process, all_gather() over the ranks of a process group; keys() / extend_keys() are the dense form
+    in which keys leave and enter a meter."""
 
     def __init__(self, train_id_in=0, train_id_out=1, recall_level=0.95):
         if train_id_in == train_id_out:
@@ -49,6 +54,8 @@ class OODMeter:
 
     def reset(self):
         self._chunks = []          # (key buffer, first slot, cap, pool, row): 8 cap u32 slots from `first slot`, per lane inliers at the front, OOD at the back of its segment
+        self._dense = []           # (id_in keys, id_out keys): dense int32 arrays taken in whole (extend_keys, all_gather)
+        self._gathered = False     # all_gather() ran: a second one would count the peers twice
         self._pool, self._pool_ptr, self._used = None, 0, 0
 
     def _counters(self, device):
@@ -116,10 +123,14 @@ class OODMeter:
         call("mss_oodm_sort_u32", ptr(keys), ptr(out), n, ptr(temp), temp.numel())
         return out
 
-    def compute(self):
-        """(auroc, aupr, fpr) as Python floats, or None if there is no in- or no out-of-distribution pixel."""
-        if not self._chunks:
-            return None
+    def _device(self):
+        """Where the keys live, None for a meter that holds none."""
+        if self._chunks:
+            return self._chunks[0][0].device
+        return self._dense[0][0].device if self._dense else None
+
+    def _totals(self):
+        """(#id_in, #id_out) of every lane chunk -- one D2H copy per counter pool -- and of the whole meter, dense chunks included."""
         pools = {}
         for _, _, _, pool, _ in self._chunks:
             pools.setdefault(id(pool), pool)
@@ -128,16 +139,33 @@ class OODMeter:
         for _, _, _, pool, row in self._chunks:
             lanes = host[id(pool)][row]
             totals.append((sum(v & 0xFFFFFFFF for v in lanes), sum((v & 0xFFFFFFFFFFFFFFFF) >> 32 for v in lanes)))
-        N, P = sum(t[0] for t in totals), sum(t[1] for t in totals)
-        if not N or not P:
-            return None
-        dev = self._chunks[0][0].device
-        neg_in, pos_in = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev)
-        np_, pp_, no, po = neg_in.data_ptr(), pos_in.data_ptr(), 0, 0
+        N = sum(t[0] for t in totals) + sum(n.numel() for n, _ in self._dense)
+        P = sum(t[1] for t in totals) + sum(p.numel() for _, p in self._dense)
+        return totals, N, P
+
+    def _gather(self, totals, neg_out, pos_out):
+        """Every chunk's keys -> its slice of the caller's two arrays (at least one element each, N and P of _totals used): a map's
+        lane segments with one kernel, a dense chunk with one copy. Every used element is written."""
+        np_, pp_, no, po = neg_out.data_ptr(), pos_out.data_ptr(), 0, 0
         for (keys, first, cap, pool, row), (a, b) in zip(self._chunks, totals):   # every map's lane segments -> its slice of the two arrays
             call("mss_oodm_gather_lanes_u32", ctypes.c_void_p(keys.data_ptr() + 4 * first), cap, ctypes.c_void_p(pool.data_ptr() + 8 * self._LANES * row),
                  ctypes.c_void_p(np_ + 4 * no), ctypes.c_void_p(pp_ + 4 * po))
             no, po = no + a, po + b
+        for neg, pos in self._dense:
+            neg_out[no:no + neg.numel()].copy_(neg)
+            pos_out[po:po + pos.numel()].copy_(pos)
+            no, po = no + neg.numel(), po + pos.numel()
+
+    def compute(self):
+        """(auroc, aupr, fpr) as Python floats, or None if there is no in- or no out-of-distribution pixel."""
+        if not self._chunks and not self._dense:
+            return None
+        totals, N, P = self._totals()
+        if not N or not P:
+            return None
+        dev = self._device()
+        neg_in, pos_in = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev)
+        self._gather(totals, neg_in, pos_in)
         pos, neg = self._sorted(pos_in), self._sorted(neg_in)
         P, N = pos.numel(), neg.numel()
         nb = _lib.value("mss_oodm_rank_blocks", P)
@@ -147,6 +175,88 @@ class OODMeter:
         call("mss_oodm_measures_f64", ptr(pos), P, ptr(neg), N, ctypes.c_double(self.recall_level), ptr(u2), ptr(ap), ptr(out))
         auroc, aupr, fpr = out.tolist()
         return auroc, aupr, fpr
+
+    # ---- combining meters ------------------------------------------------------------------------------------------------------
+    def keys(self):
+        """(id_in keys, id_out keys) seen so far: two dense, unsorted int32 device tensors -- the gather step of compute(). Two empty
+        tensors for an empty meter."""
+        totals, N, P = self._totals()
+        dev = self._device()
+        if dev is None:
+            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        # one spare element: the gather kernel is handed a valid address for a class without a pixel too (it writes nothing there)
+        neg, pos = torch.zeros(N + 1, dtype=torch.int32, device=dev), torch.zeros(P + 1, dtype=torch.int32, device=dev)
+        self._gather(totals, neg, pos)
+        return neg[:N], pos[:P]
+
+    def extend_keys(self, neg, pos):
+        """Take dense key arrays (what keys() returns) in as if their pixels had been streamed. The tensors are kept by reference
+        and never written."""
+        for t in (neg, pos):
+            if t.dtype != torch.int32 or t.dim() != 1:
+                raise ValueError(f"OODMeter.extend_keys: keys are one-dimensional int32 tensors, got {t.dtype} {tuple(t.shape)}")
+        if neg.numel() or pos.numel():
+            if not (neg.is_cuda and pos.is_cuda):
+                raise RuntimeError("OOD metrics (multishiftseg_amd) run on an MI355X only; there is no CPU path")
+            dev = self._device()
+            if neg.device != pos.device or (dev is not None and dev != neg.device):
+                raise ValueError(f"OODMeter.extend_keys: keys on {neg.device} / {pos.device}, the meter's on {dev}")
+            self._dense.append((neg.detach().contiguous(), pos.detach().contiguous()))
+        return self
+
+    def merge(self, other):
+        """Afterwards this meter measures the union of both meters' pixels; `other` stays valid and unchanged (its key buffers are
+        shared by reference: nothing writes them after the update that filled them)."""
+        if (other.id_in, other.id_out, other.recall_level) != (self.id_in, self.id_out, self.recall_level):
+            raise ValueError(f"OODMeter.merge: (train_id_in, train_id_out, recall_level) = {(other.id_in, other.id_out, other.recall_level)} "
+                             f"into {(self.id_in, self.id_out, self.recall_level)}")
+        a, b = self._device(), other._device()
+        if a is not None and b is not None and a != b:
+            raise ValueError(f"OODMeter.merge: keys on {b} into keys on {a}")
+        self._chunks += other._chunks
+        self._dense += other._dense
+        return self
+
+    def all_gather(self, group=None):
+        """A collective: afterwards every rank's meter holds the keys of all ranks of `group`, so compute() returns on every rank
+        what one meter fed every rank's maps returns (the same tuple, or None). Without an initialised group, or with one rank,
+        nothing happens (ddp.is_active: MSS_DDP_FORCE=1 runs the collectives in a one-rank group too). Two collectives: the 2 x
+        world key counts, then the keys padded to the largest count of each class -- device to device where the group's backend
+        is nccl (RCCL), staged through host tensors over ddp.host_group(group) otherwise. The padding is sliced off here: no
+        padding element is ever read. A second call before reset() raises: it would count the peers twice."""
+        from . import ddp
+        import torch.distributed as dist
+        if self._gathered:
+            raise RuntimeError("OODMeter.all_gather: the peers' keys are already here; reset() before the next sweep")
+        if not (dist.is_available() and ddp.is_active(group)):
+            return self
+        world = dist.get_world_size(group)
+        neg, pos = self.keys()
+        on_device = "nccl" in str(dist.get_backend(group))
+        dev = neg.device if neg.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        if on_device:
+            where, g = dev, group
+        else:
+            where, g = torch.device("cpu"), ddp.host_group(group)
+        counts = torch.zeros(2 * world, dtype=torch.int64, device=where)
+        dist.all_gather_into_tensor(counts, torch.tensor([neg.numel(), pos.numel()], dtype=torch.int64, device=where), group=g)
+        counts = counts.tolist()
+        ns, ps = counts[0::2], counts[1::2]
+        mn, mp = max(ns), max(ps)
+        self._chunks, self._dense, self._gathered = [], [], True
+        if mn + mp == 0:                                     # every rank knows: no rank enters the key exchange
+            return self
+        send = torch.zeros(mn + mp, dtype=torch.int32, device=where)          # [id_in keys, padding | id_out keys, padding]
+        send[:neg.numel()].copy_(neg)
+        send[mn:mn + pos.numel()].copy_(pos)
+        recv = torch.zeros(world * (mn + mp), dtype=torch.int32, device=where)
+        dist.all_gather_into_tensor(recv, send, group=g)
+        recv = recv.to(dev)
+        for r in range(world):
+            at = r * (mn + mp)
+            if ns[r] or ps[r]:
+                self._dense.append((recv[at:at + ns[r]], recv[at + mn:at + mn + ps[r]]))
+        return self
 
 
 def eval_ood_measure(conf, seg_label, train_id_in=0, train_id_out=1):
