@@ -540,12 +540,32 @@ int mss_upsample_ac_nhwc_bwd_f32(const float* dy, int lddy, float* dx, int lddx,
 /* The OOD-score tail (deepv3.py:251-253,279-283):
  *   score[n,oy,ox] = bilinear_ac( -logsumexp_c dec2[n,:,:,c] )    dec2 NHWC [N,IH,IW,C] (ld)
  *   logit[n,c,oy,ox] = bilinear_ac( dec1[n,:,:,c] )               written NCHW
- *   label[n,oy,ox]  = argmax_c logit (first max wins, as torch.argmax), optional (uint8)
- * Any of score/logit/label may be NULL. */
+ *   label[n,oy,ox]  = argmax_c logit (first max wins, as torch.argmax; a NaN is maximal and the first NaN wins), optional (uint8)
+ * Any of score/logit/label may be NULL. The logsumexp is max-shifted, computed once per source pixel, classes summed in ascending
+ * order; the blend is l0y (l0x v00 + l1x v01) + l1y (l0x v10 + l1x v11).
+ * Class count: 1 <= C <= 100 (class indices above 99 mean "OOD" to RelContrastiveLoss and label_threshold, and label is uint8);
+ * anything else -> MSS_ERR_UNSUPPORTED, checked first. Then: score without dec2, or logit / label without dec1 ->
+ * MSS_ERR_BAD_ARG; N * OH * OW == 0 -> MSS_OK, nothing launched. C == 19 runs kernels specialised for the Cityscapes classes,
+ * every other count a class-generic route that walks the classes in chunks of 24 (registers and LDS do not grow with C; at most
+ * 64 KB of LDS per workgroup). Both routes pick one of three launch regimes:
+ *   vector    OW % 4 == 0, up-sampling, and both heads in ONE pixel-contiguous buffer: ld1 == ld2, ld % 4 == 0, dec1 and dec2 each
+ *             at a multiple of 4 floats from the lower of the two, each with 4 * ceil(C/4) readable floats inside the row (the
+ *             columns past C are read and ignored), every operand 16-byte aligned, N * C * OH * OW * 4 < 2^32;
+ *   tiled     up-sampling with any alignment and any OW;
+ *   per-pixel everything else (down-sampling, identity, large ratios).
+ * MSS_OOD_TAIL_GENERIC=1 (default 0; read through the cached switches, see mss_env_reset) sends C == 19 through the class-generic
+ * route too: an A/B switch to measure and cross-check the two routes. */
 int mss_ood_score_f32(const float* dec2, int ld2, const float* dec1, int ld1, int N, int IH, int IW, int C,
                       int OH, int OW, float* score, float* logit_nchw, uint8_t* label, void* stream);
 /* backward: given dscore [N,OH,OW] and dlogit NCHW [N,C,OH,OW] (either may be NULL) produce
- * ddec2 / ddec1 (NHWC, assigned). */
+ * ddec2 = -softmax(dec2) * gathered dscore / ddec1[c] = gathered dlogit[c] (NHWC, assigned; either may be NULL). Gather form, no
+ * atomics: every source pixel sums the output pixels whose taps contain it in a fixed order. Same class range, check order
+ * (C, then ddec2 without dec2 -> MSS_ERR_BAD_ARG, then N * IH * IW == 0 -> MSS_OK) and switch as the forward.
+ * Where both gradients go into ONE pixel-contiguous buffer (ldd1 == ldd2, the two heads not overlapping inside a row of ldd
+ * floats) the tiled regime (up-sampling by at most ~x4, OW % 4 == 0, ldd % 4 == 0, ld2 % 4 == 0, heads at multiples of 4 floats
+ * with 4 * ceil(C/4) floats each, 16-byte aligned operands) writes the WHOLE row: the columns outside the two heads, the padding
+ * up to the channel quad and the head of an absent gradient as zeros, so the buffer needs no memset. The class-generic route's
+ * per-pixel fallback does the same for such a buffer; the <19> fallback writes the C columns of each head only. */
 int mss_ood_score_bwd_f32(const float* dec2, int ld2, const float* dscore, const float* dlogit_nchw, int N,
                           int IH, int IW, int C, int OH, int OW, float* ddec2, int ldd2, float* ddec1, int ldd1,
                           void* stream);

@@ -1078,6 +1078,472 @@ __global__ __launch_bounds__(256) void ood_score_bwd_tiled_kernel(
     if ((c < c1 || c >= c1 + 4 * CQ) && (c < c2 || c >= c2 + 4 * CQ)) st4(o + c, f32x4{0.f, 0.f, 0.f, 0.f});
 }
 
+// ---------------------------------------------------------------- OOD-score tail, any class count
+// The class-generic route of the tail (every C != 19, and C == 19 under MSS_OOD_TAIL_GENERIC=1): the class count is a run-time
+// argument and the classes are walked in chunks of OOD_CH, so registers and LDS do not grow with C. The three launch regimes
+// mirror the <19> kernels above (per-pixel fallback, tiled, vector); the arithmetic per value is theirs, written out once.
+constexpr int OOD_CH = 24;   // classes per chunk of the class-generic tail (6 channel quads: 19 and 21 classes are one chunk)
+
+// -logsumexp of one source pixel's C-vector, max-shifted, classes summed in ascending order (two passes over the row)
+__device__ __forceinline__ float ood_energy(const float* __restrict__ q, int C) {
+  float m = -__builtin_huge_valf();
+  for (int c = 0; c < C; ++c) m = fmaxf(m, q[c]);
+  float s = 0.f;
+  for (int c = 0; c < C; ++c) s += expf(q[c] - m);
+  return -(m + logf(s));
+}
+// the same from 16-byte loads (q 16-byte aligned, 4 * ceil(C/4) floats readable); the padding lanes of the last quad drop out.
+// Up to OOD_RQ quads (32 classes) are loaded once, all loads in flight together, and both passes run from registers; longer rows
+// take two passes over memory, OOD_RQ loads in flight per step (one load per loop trip would cost a memory round trip per quad).
+constexpr int OOD_RQ = 8;
+__device__ __forceinline__ void ood_load_quads(const float* __restrict__ q, int k0, int CQ, f32x4 (&t)[OOD_RQ]) {
+#pragma unroll
+  for (int k = 0; k < OOD_RQ; ++k) t[k] = k0 + k < CQ ? ld4(q + 4 * (k0 + k)) : f32x4{0.f, 0.f, 0.f, 0.f};   // past the row: masked by the caller
+}
+__device__ __forceinline__ void ood_max_sum4(const float* __restrict__ q, int C, float& m, float& s) {
+  const int CQ = (C + 3) >> 2;
+  f32x4 t[OOD_RQ];
+  m = -__builtin_huge_valf();
+  s = 0.f;
+  ood_load_quads(q, 0, CQ, t);
+#pragma unroll
+  for (int k = 0; k < OOD_RQ; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (4 * k + j < C) m = fmaxf(m, t[k][j]);
+  if (CQ <= OOD_RQ) {
+#pragma unroll
+    for (int k = 0; k < OOD_RQ; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) if (4 * k + j < C) s += expf(t[k][j] - m);
+    return;
+  }
+  for (int k0 = OOD_RQ; k0 < CQ; k0 += OOD_RQ) {
+    ood_load_quads(q, k0, CQ, t);
+#pragma unroll
+    for (int k = 0; k < OOD_RQ; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) if (4 * (k0 + k) + j < C) m = fmaxf(m, t[k][j]);
+  }
+  for (int k0 = 0; k0 < CQ; k0 += OOD_RQ) {
+    ood_load_quads(q, k0, CQ, t);
+#pragma unroll
+    for (int k = 0; k < OOD_RQ; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) if (4 * (k0 + k) + j < C) s += expf(t[k][j] - m);
+  }
+}
+
+// Per-pixel fallback (down-sampling, identity, large ratios, unaligned operands): one thread per output pixel.
+__global__ __launch_bounds__(256) void ood_score_gen_kernel(const float* __restrict__ dec2, int ld2,
+                                                            const float* __restrict__ dec1, int ld1, int N, int IH,
+                                                            int IW, int C, int OH, int OW, float sh, float sw,
+                                                            float* __restrict__ score, float* __restrict__ logit,
+                                                            uint8_t* __restrict__ label) {
+  const long long total = (long long)N * OH * OW;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    long long p = i;
+    const int ox = (int)(p % OW); p /= OW;
+    const int oy = (int)(p % OH);
+    const int n = (int)(p / OH);
+    const Tap ty = ac_tap(oy, sh, IH), tx = ac_tap(ox, sw, IW);
+    const long long nb = (long long)n * IH * IW;
+    const long long o00 = nb + (long long)ty.i0 * IW + tx.i0, o01 = nb + (long long)ty.i0 * IW + tx.i1;
+    const long long o10 = nb + (long long)ty.i1 * IW + tx.i0, o11 = nb + (long long)ty.i1 * IW + tx.i1;
+    if (score) {
+      const float e0 = ood_energy(dec2 + o00 * ld2, C), e1 = ood_energy(dec2 + o01 * ld2, C);
+      const float e2 = ood_energy(dec2 + o10 * ld2, C), e3 = ood_energy(dec2 + o11 * ld2, C);
+      score[i] = ty.l0 * (tx.l0 * e0 + tx.l1 * e1) + ty.l1 * (tx.l0 * e2 + tx.l1 * e3);
+    }
+    if (logit || label) {
+      const float* q00 = dec1 + o00 * ld1; const float* q01 = dec1 + o01 * ld1;
+      const float* q10 = dec1 + o10 * ld1; const float* q11 = dec1 + o11 * ld1;
+      float best = -__builtin_huge_valf();
+      int arg = 0;
+      const long long plane = (long long)OH * OW;
+      float* lo = logit ? logit + (long long)n * C * plane + (long long)oy * OW + ox : nullptr;
+      for (int c = 0; c < C; ++c) {
+        const float val = ty.l0 * (tx.l0 * q00[c] + tx.l1 * q01[c]) + ty.l1 * (tx.l0 * q10[c] + tx.l1 * q11[c]);
+        if (lo) lo[c * plane] = val;
+        if (val > best || (val != val && best == best)) { best = val; arg = c; }  // first max; NaN wins like torch
+      }
+      if (label) label[i] = (uint8_t)arg;
+    }
+  }
+}
+
+// Tiled regime: the geometry of ood_score_tiled_kernel. The energies of the tile's source footprint are computed straight
+// from global memory (one source pixel per thread); dec1 is staged OOD_CH classes at a time, padded to an odd pixel stride,
+// and the running (best, arg) of the argmax stays in registers across the chunks.
+template <int TH, int TW>
+__global__ __launch_bounds__(256) void ood_score_gen_tiled_kernel(const float* __restrict__ dec2, int ld2,
+                                                                  const float* __restrict__ dec1, int ld1, int C,
+                                                                  int IH, int IW, int OH, int OW, float sh, float sw,
+                                                                  int SRmax, int SCmax, float* __restrict__ score,
+                                                                  float* __restrict__ logit, uint8_t* __restrict__ label) {
+  constexpr int PS = OOD_CH + 1;         // LDS floats per staged pixel (odd: neighbouring pixels on different banks)
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* en = lds;                       // [SRmax*SCmax] energies
+  float* dv = lds + SRmax * SCmax;       // [SRmax*SCmax][PS] one chunk of staged channel vectors
+  const int n = blockIdx.z;
+  const int oy0 = blockIdx.y * TH, ox0 = blockIdx.x * TW;
+  const int oy1 = min(oy0 + TH, OH) - 1, ox1 = min(ox0 + TW, OW) - 1;
+  const int r0 = ac_tap(oy0, sh, IH).i0, r1 = ac_tap(oy1, sh, IH).i1;
+  const int c0 = ac_tap(ox0, sw, IW).i0, c1 = ac_tap(ox1, sw, IW).i1;
+  const int SR = r1 - r0 + 1, SC = c1 - c0 + 1;   // <= SRmax, SCmax by construction
+  const int npix = SR * SC;
+  const long long nb = (long long)n * IH * IW;
+  if (score) {
+    for (int pix = threadIdx.x; pix < npix; pix += 256) {
+      const int rr = pix / SC, cc = pix - rr * SC;
+      en[pix] = ood_energy(dec2 + (nb + (long long)(r0 + rr) * IW + (c0 + cc)) * ld2, C);
+    }
+  }
+  __syncthreads();
+  const int tx = threadIdx.x % TW;
+  const int ox = ox0 + tx;
+  const bool col_live = ox <= ox1;
+  const Tap tapx = ac_tap(col_live ? ox : ox1, sw, IW);
+  const int x0 = tapx.i0 - c0, x1 = tapx.i1 - c0;
+  const long long plane = (long long)OH * OW;
+  constexpr int ROWS = TH / (256 / TW);   // output rows per thread
+  if (score && col_live) {
+    for (int ty = threadIdx.x / TW; ty < TH; ty += 256 / TW) {
+      const int oy = oy0 + ty;
+      if (oy > oy1) break;
+      const Tap tapy = ac_tap(oy, sh, IH);
+      const int p00 = (tapy.i0 - r0) * SC + x0, p01 = (tapy.i0 - r0) * SC + x1;
+      const int p10 = (tapy.i1 - r0) * SC + x0, p11 = (tapy.i1 - r0) * SC + x1;
+      score[(long long)n * plane + (long long)oy * OW + ox] =
+          tapy.l0 * (tapx.l0 * en[p00] + tapx.l1 * en[p01]) + tapy.l1 * (tapx.l0 * en[p10] + tapx.l1 * en[p11]);
+    }
+  }
+  if (!(logit || label)) return;
+  float best[ROWS];
+  int arg[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) { best[r] = -__builtin_huge_valf(); arg[r] = 0; }
+  for (int cb = 0; cb < C; cb += OOD_CH) {
+    const int nc = min(OOD_CH, C - cb);
+    if (cb) __syncthreads();             // the previous chunk has been read
+    for (int idx = threadIdx.x; idx < npix * nc; idx += 256) {
+      const int pix = idx / nc, c = idx - pix * nc;
+      const int rr = pix / SC, cc = pix - rr * SC;
+      dv[pix * PS + c] = dec1[(nb + (long long)(r0 + rr) * IW + (c0 + cc)) * ld1 + cb + c];
+    }
+    __syncthreads();
+    if (col_live) {
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        const int oy = oy0 + (int)threadIdx.x / TW + r * (256 / TW);
+        if (oy > oy1) break;
+        const Tap tapy = ac_tap(oy, sh, IH);
+        const float* v00 = dv + ((tapy.i0 - r0) * SC + x0) * PS; const float* v01 = dv + ((tapy.i0 - r0) * SC + x1) * PS;
+        const float* v10 = dv + ((tapy.i1 - r0) * SC + x0) * PS; const float* v11 = dv + ((tapy.i1 - r0) * SC + x1) * PS;
+        float* lo = logit ? logit + ((long long)n * C + cb) * plane + (long long)oy * OW + ox : nullptr;
+        for (int c = 0; c < nc; ++c) {
+          const float val = tapy.l0 * (tapx.l0 * v00[c] + tapx.l1 * v01[c]) + tapy.l1 * (tapx.l0 * v10[c] + tapx.l1 * v11[c]);
+          if (lo) lo[c * plane] = val;
+          if (val > best[r] || (val != val && best[r] == best[r])) { best[r] = val; arg[r] = cb + c; }
+        }
+      }
+    }
+  }
+  if (label && col_live) {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      const int oy = oy0 + (int)threadIdx.x / TW + r * (256 / TW);
+      if (oy > oy1) break;
+      label[(long long)n * plane + (long long)oy * OW + ox] = (uint8_t)arg[r];
+    }
+  }
+}
+
+// Vector regime: the geometry, LDS layout and swizzle of ood_score_v4_kernel with the class count at run time. Both heads
+// live in one pixel-contiguous buffer (dec1 at column c1, dec2 at column c2, each 4 * ceil(C/4) floats wide). The dec2 part
+// is reduced to -logsumexp straight from 16-byte loads; the dec1 part passes through LDS OOD_CH / 4 channel quads at a time.
+template <int TH, int TW>
+__global__ __launch_bounds__(256) void ood_score_gen_v4_kernel(const float* __restrict__ dec, int ld, int c1, int c2, int C,
+                                                               int IH, int IW, int OH, int OW, float sh, float sw,
+                                                               int SRmax, int SCmax, float* __restrict__ score,
+                                                               float* __restrict__ logit, uint8_t* __restrict__ label) {
+  constexpr int CHQ = OOD_CH / 4;          // channel quads per chunk
+  const int CQ = (C + 3) >> 2;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int NP = SRmax * SCmax + 16;       // slots per quad plane (swizzle stays inside: p ^ 1 < NP)
+  float* en = lds;                         // [NP] energies
+  f32x4* sv = reinterpret_cast<f32x4*>(lds + ((NP + 3) & ~3));   // [CHQ][NP] float4
+  const int n = blockIdx.z;
+  const int oy0 = blockIdx.y * TH, ox0 = blockIdx.x * TW;
+  const int oy1 = min(oy0 + TH, OH) - 1, ox1 = min(ox0 + TW, OW) - 1;
+  const int r0 = ac_tap(oy0, sh, IH).i0, r1 = ac_tap(oy1, sh, IH).i1;
+  const int cc0 = ac_tap(ox0, sw, IW).i0, cc1 = ac_tap(ox1, sw, IW).i1;
+  const int SR = r1 - r0 + 1, SC = cc1 - cc0 + 1;
+  const int npix = SR * SC;
+  const long long nb = (long long)n * IH * IW;
+  auto slot = [](int p) { return p ^ ((p >> 3) & 1); };
+  if (score) {
+    for (int pix = threadIdx.x; pix < npix; pix += 256) {
+      const int rr = pix / SC, cc = pix - rr * SC;
+      float m, sum;
+      ood_max_sum4(dec + (nb + (long long)(r0 + rr) * IW + (cc0 + cc)) * ld + c2, C, m, sum);
+      en[pix] = -(m + logf(sum));          // energy_func: -logsumexp (deepv3.py:251-253)
+    }
+  }
+  __syncthreads();
+  const int ty = threadIdx.x / (TW / 4), xq = threadIdx.x % (TW / 4);
+  const int oy = oy0 + ty, ox = ox0 + 4 * xq;
+  const bool live = oy <= oy1 && ox <= ox1;   // OW % 4 == 0: a quad is inside or outside as a whole
+  const Tap tapy = ac_tap(live ? oy : oy1, sh, IH);
+  const int rowa = (tapy.i0 - r0) * SC - cc0, rowb = (tapy.i1 - r0) * SC - cc0;
+  int pa0[4], pa1[4], pb0[4], pb1[4];
+  float l0[4], l1[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const Tap t = ac_tap(live ? ox + e : ox1, sw, IW);
+    pa0[e] = rowa + t.i0; pa1[e] = rowa + t.i1; pb0[e] = rowb + t.i0; pb1[e] = rowb + t.i1;
+    l0[e] = t.l0; l1[e] = t.l1;
+  }
+  const long long plane = (long long)OH * OW;
+  const long long opix = (long long)oy * OW + ox;
+  if (score && live) {
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      o[e] = tapy.l0 * (l0[e] * en[pa0[e]] + l1[e] * en[pa1[e]]) + tapy.l1 * (l0[e] * en[pb0[e]] + l1[e] * en[pb1[e]]);
+    st4(score + (long long)n * plane + opix, o);
+  }
+  if (!(logit || label)) return;
+  float best[4] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+  int arg[4] = {0, 0, 0, 0};
+  const unsigned voff = live ? (unsigned)(((long long)n * C * plane + opix) * 4) : 0u;   // launcher: N*C*OH*OW*4 < 2^32
+  char* lbase = reinterpret_cast<char*>(logit);
+  for (int k0 = 0; k0 < CQ; k0 += CHQ) {
+    const int nq = min(CHQ, CQ - k0);
+    if (k0) __syncthreads();               // the previous chunk has been read
+    for (int pix = threadIdx.x; pix < npix; pix += 256) {
+      const int rr = pix / SC, cc = pix - rr * SC;
+      const float* q = dec + (nb + (long long)(r0 + rr) * IW + (cc0 + cc)) * ld + c1 + 4 * k0;
+#pragma unroll
+      for (int k = 0; k < CHQ; ++k)
+        if (k < nq) sv[k * NP + slot(pix)] = ld4(q + 4 * k);
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll 1
+      for (int k = 0; k < nq; ++k) {       // not unrolled: six quads of taps in flight cost 190 VGPRs and half the waves
+        f32x4 val[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const f32x4 a0 = sv[k * NP + slot(pa0[e])], a1 = sv[k * NP + slot(pa1[e])];
+          const f32x4 b0 = sv[k * NP + slot(pb0[e])], b1 = sv[k * NP + slot(pb1[e])];
+          val[e] = tapy.l0 * (l0[e] * a0 + l1[e] * a1) + tapy.l1 * (l0[e] * b0 + l1[e] * b1);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = 4 * (k0 + k) + j;
+          if (c >= C) break;
+          const f32x4 o = {val[0][j], val[1][j], val[2][j], val[3][j]};
+          if (logit) *reinterpret_cast<f32x4*>(lbase + (size_t)c * plane * 4 + voff) = o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (o[e] > best[e] || (o[e] != o[e] && best[e] == best[e])) { best[e] = o[e]; arg[e] = c; }   // first max; NaN wins like torch
+        }
+      }
+    }
+  }
+  if (label && live)
+    *reinterpret_cast<uint32_t*>(label + (long long)n * plane + opix) =
+        (uint32_t)arg[0] | ((uint32_t)arg[1] << 8) | ((uint32_t)arg[2] << 16) | ((uint32_t)arg[3] << 24);
+}
+
+// Backward, per-pixel fallback: one thread per half-resolution pixel gathers its outputs OOD_CH class planes at a time.
+// With row_ld > 0 both gradients lie in one pixel-contiguous buffer of that width (ddec1 / ddec2 point at their columns of
+// the row that starts at rowbase) and the columns outside the two heads are written as zeros.
+__global__ __launch_bounds__(256) void ood_score_gen_bwd_kernel(const float* __restrict__ dec2, int ld2,
+                                                                const float* __restrict__ dscore,
+                                                                const float* __restrict__ dlogit, int N, int IH,
+                                                                int IW, int C, int OH, int OW, float sh, float sw,
+                                                                float* __restrict__ ddec2, int ldd2,
+                                                                float* __restrict__ ddec1, int ldd1,
+                                                                float* __restrict__ rowbase, int row_ld, int rc1, int rc2) {
+  const long long total = (long long)N * IH * IW;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    long long p = i;
+    const int ix = (int)(p % IW); p /= IW;
+    const int iy = (int)(p % IH);
+    const int n = (int)(p / IH);
+    int ylo, yhi, xlo, xhi;
+    ac_range(iy, sh, OH, ylo, yhi);
+    ac_range(ix, sw, OW, xlo, xhi);
+    const long long plane = (long long)OH * OW;
+    if (ddec1) {
+      float* o = ddec1 + i * ldd1;
+      for (int cb = 0; cb < C; cb += OOD_CH) {
+        const int nc = min(OOD_CH, C - cb);
+        float gl[OOD_CH];
+#pragma unroll
+        for (int c = 0; c < OOD_CH; ++c) gl[c] = 0.f;
+        if (dlogit) {
+          for (int oy = ylo; oy <= yhi; ++oy) {
+            const float wy = ac_weight(oy, iy, sh, IH);
+            if (wy == 0.f) continue;
+            for (int ox = xlo; ox <= xhi; ++ox) {
+              const float w = wy * ac_weight(ox, ix, sw, IW);
+              if (w == 0.f) continue;
+              const float* q = dlogit + ((long long)n * C + cb) * plane + (long long)oy * OW + ox;
+#pragma unroll
+              for (int c = 0; c < OOD_CH; ++c) if (c < nc) gl[c] += w * q[c * plane];
+            }
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < OOD_CH; ++c) if (c < nc) o[cb + c] = gl[c];
+      }
+    }
+    if (ddec2) {
+      float gs = 0.f;
+      if (dscore) {
+        for (int oy = ylo; oy <= yhi; ++oy) {
+          const float wy = ac_weight(oy, iy, sh, IH);
+          if (wy == 0.f) continue;
+          for (int ox = xlo; ox <= xhi; ++ox) {
+            const float w = wy * ac_weight(ox, ix, sw, IW);
+            if (w == 0.f) continue;
+            gs += w * dscore[(long long)n * plane + (long long)oy * OW + ox];
+          }
+        }
+      }
+      const float* q = dec2 + i * ld2;
+      float* o = ddec2 + i * ldd2;
+      float m = -__builtin_huge_valf();
+      for (int c = 0; c < C; ++c) m = fmaxf(m, q[c]);
+      float s = 0.f;
+      for (int c = 0; c < C; ++c) s += expf(q[c] - m);
+      const float k = -gs / s;  // d(-lse)/dx_c = -softmax_c
+      for (int c = 0; c < C; ++c) o[c] = dscore ? k * expf(q[c] - m) : 0.f;
+    }
+    if (row_ld > 0) {
+      float* o = rowbase + i * row_ld;
+      for (int c = 0; c < row_ld; ++c)
+        if ((c < rc1 || c >= rc1 + C) && (c < rc2 || c >= rc2 + C)) o[c] = 0.f;
+    }
+  }
+}
+
+// Tiled backward: the geometry and staging of ood_score_bwd_tiled_kernel. The class planes of dlogit and, as plane C, dscore
+// pass through LDS G = 4 at a time and every pass ends in one 16-byte store of its channel quad, so no per-class accumulator
+// outlives a pass. The softmax of dec2 comes from global memory (max and sum from registers up to 32 classes, then the products).
+template <int MAXW>
+__global__ __launch_bounds__(256) void ood_score_gen_bwd_tiled_kernel(
+    const float* __restrict__ dec2, int ld2, const float* __restrict__ dscore, const float* __restrict__ dlogit, int C,
+    int IH, int IW, int OH, int OW, float sh, float sw, float* __restrict__ dd, int ldd, int c1, int c2, int RR, int RC) {
+  constexpr int TSY = 4, TSX = 64, G = 4;
+  extern __shared__ __attribute__((aligned(16))) float lds[];     // [G][RR][RC]
+  const int CQ = (C + 3) >> 2;
+  const int n = blockIdx.z, iy0 = blockIdx.y * TSY, ix0 = blockIdx.x * TSX;
+  const int tx = threadIdx.x % TSX, tyl = threadIdx.x / TSX;
+  const int iy = iy0 + tyl, ix = ix0 + tx;
+  const bool live = iy < IH && ix < IW;
+  int ylo, yhi, xlo, xhi, t0, t1;
+  ac_range(iy0, sh, OH, ylo, t1);
+  ac_range(min(iy0 + TSY, IH) - 1, sh, OH, t0, yhi);
+  ac_range(ix0, sw, OW, xlo, t1);
+  ac_range(min(ix0 + TSX, IW) - 1, sw, OW, t0, xhi);
+  xlo &= ~3;                                          // 16-byte aligned rows
+  const int nrow = yhi - ylo + 1, ncol4 = (xhi - xlo + 4) >> 2;   // <= RR, <= RC / 4 by construction
+  int oy_a = 0, ox_a = 0, ny = 0, nx = 0;
+  float wy[MAXW], wx[MAXW];
+#pragma unroll
+  for (int k = 0; k < MAXW; ++k) { wy[k] = 0.f; wx[k] = 0.f; }
+  if (live) {
+    int a, b;
+    ac_range(iy, sh, OH, a, b);
+    while (a < b && ac_weight(a, iy, sh, IH) == 0.f) ++a;
+    while (b > a && ac_weight(b, iy, sh, IH) == 0.f) --b;
+    oy_a = a; ny = b - a + 1;
+#pragma unroll
+    for (int k = 0; k < MAXW; ++k) if (k < ny) wy[k] = ac_weight(a + k, iy, sh, IH);
+    ac_range(ix, sw, OW, a, b);
+    while (a < b && ac_weight(a, ix, sw, IW) == 0.f) ++a;
+    while (b > a && ac_weight(b, ix, sw, IW) == 0.f) --b;
+    ox_a = a; nx = b - a + 1;
+#pragma unroll
+    for (int k = 0; k < MAXW; ++k) if (k < nx) wx[k] = ac_weight(a + k, ix, sw, IW);
+  }
+  const int ro = oy_a - ylo, co = ox_a - xlo;
+  const long long plane = (long long)OH * OW;
+  const long long spix = ((long long)n * IH + iy) * IW + ix;
+  float* o = dd + spix * ldd;                         // dereferenced by live threads only
+  const int per_plane = nrow * ncol4;
+  // ddec1: channels c1 .. c1+C-1 (+ padding up to the next multiple of 4). Planes 0..C-1 = dlogit, plane C = dscore, as in the
+  // <19> kernel: pass p stages planes 4p .. 4p+3, gathers this thread's value of each and ends in the 16-byte store of quad p
+  float gs = 0.f;
+  for (int p = 0; 4 * p <= C; ++p) {
+    const int np = min(G, C + 1 - 4 * p);
+    __syncthreads();
+    for (int i = threadIdx.x; i < np * per_plane; i += 256) {
+      const int g = i / per_plane, rem = i - g * per_plane;
+      const int rr = rem / ncol4, c4 = rem - rr * ncol4;
+      const int pl = 4 * p + g;
+      const int ox = xlo + 4 * c4;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (ox < OW) {
+        const float* src = pl < C ? (dlogit ? dlogit + ((long long)n * C + pl) * plane : nullptr)
+                                  : (dscore ? dscore + (long long)n * plane : nullptr);
+        if (src) v = ld4(src + (long long)(ylo + rr) * OW + ox);
+      }
+      *reinterpret_cast<f32x4*>(&lds[(g * RR + rr) * RC + 4 * c4]) = v;
+    }
+    __syncthreads();
+    if (live) {
+      f32x4 out = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if (g >= np) break;
+        float acc = 0.f;
+#pragma unroll
+        for (int a = 0; a < MAXW; ++a) {
+          if (a >= ny) break;
+          const float* row = &lds[(g * RR + ro + a) * RC + co];
+          float racc = 0.f;
+#pragma unroll
+          for (int b = 0; b < MAXW; ++b) if (b < nx) racc += wx[b] * row[b];
+          acc += wy[a] * racc;
+        }
+        if (4 * p + g == C) gs = acc; else out[g] = acc;
+      }
+      if (p < CQ) st4(o + c1 + 4 * p, out);
+    }
+  }
+  if (!live) return;
+  // ddec2 = -gs * softmax(dec2)   (d(-lse)/dx_c = -softmax_c)
+  if (dscore) {
+    const float* q = dec2 + spix * ld2;
+    float m, sum;
+    ood_max_sum4(q, C, m, sum);
+    const float kk = -gs / sum;
+    f32x4 t[OOD_RQ];
+    for (int k0 = 0; k0 < CQ; k0 += OOD_RQ) {
+      ood_load_quads(q, k0, CQ, t);
+#pragma unroll
+      for (int k = 0; k < OOD_RQ; ++k) {
+        if (k0 + k >= CQ) break;
+        f32x4 w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = 4 * (k0 + k) + j < C ? kk * expf(t[k][j] - m) : 0.f;
+        st4(o + c2 + 4 * (k0 + k), w);
+      }
+    }
+  } else {
+    for (int k = 0; k < CQ; ++k) st4(o + c2 + 4 * k, f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+  // channels outside the two heads (the GEMM's padding rows): zeros
+  for (int c = 0; c < ldd; c += 4)
+    if ((c < c1 || c >= c1 + 4 * CQ) && (c < c2 || c >= c2 + 4 * CQ)) st4(o + c, f32x4{0.f, 0.f, 0.f, 0.f});
+}
+
 // ---------------------------------------------------------------- Mask2Former anomaly score
 // block = one row segment of 256 pixels of one image; class probabilities of the image's Q
 // queries live in LDS as [Q][CP] (CP = C rounded up to 4) and are read as broadcast b128.
@@ -1364,78 +1830,115 @@ int mss_upsample_ac_nhwc_bwd_f32(const float* dy, int lddy, float* dx, int lddx,
   return mss_launch_status();
 }
 
+// MSS_OOD_TAIL_GENERIC=1 sends C == 19 through the class-generic kernels too (A/B measurement and cross-check)
+static inline bool ood_tail_generic(int C) { return C != 19 || MSS_ENV_INT("MSS_OOD_TAIL_GENERIC", 0) != 0; }
+
 int mss_ood_score_f32(const float* dec2, int ld2, const float* dec1, int ld1, int N, int IH, int IW, int C,
                       int OH, int OW, float* score, float* logit_nchw, uint8_t* label, void* stream) {
-  if (C != 19) return MSS_ERR_UNSUPPORTED;  // Cityscapes, the only class count on the path
+  if (C < 1 || C > 100) return MSS_ERR_UNSUPPORTED;  // label is uint8 and class indices above 99 mean "OOD" downstream
   if (score && !dec2) return MSS_ERR_BAD_ARG;
   if ((logit_nchw || label) && !dec1) return MSS_ERR_BAD_ARG;
   if ((long long)N * OH * OW == 0) return MSS_OK;
+  const bool generic = ood_tail_generic(C);
+  const int q4 = 4 * ((C + 3) / 4);                  // a head's width in the fused buffer: C rounded up to a channel quad
   {
     constexpr int TH = 8, TW = 128;
     const float sh = ac_scale(IH, OH), sw = ac_scale(IW, OW);
     const int SRmax = (int)((TH - 1) * sh) + 3, SCmax = (int)((TW - 1) * sw) + 3;
-    // both heads in one pixel-contiguous buffer (the K = 48 fused heads GEMM output), 16-byte aligned everywhere
+    // both heads in one pixel-contiguous buffer (the fused heads GEMM output), 16-byte aligned everywhere
     const float* base = dec1 ? (dec2 ? (dec1 < dec2 ? dec1 : dec2) : dec1) : dec2;
     const long long off1 = dec1 ? dec1 - base : 0, off2 = dec2 ? dec2 - base : 0;
     const int ld = dec1 ? ld1 : ld2;
     const int NP = SRmax * SCmax + 16;
-    const size_t smem4 = ((size_t)((NP + 3) & ~3) + (size_t)5 * NP * 4) * sizeof(float);
+    const int quads = generic ? OOD_CH / 4 : 5;      // channel quads resident in LDS
+    const size_t smem4 = ((size_t)((NP + 3) & ~3) + (size_t)quads * NP * 4) * sizeof(float);
     const bool v4 = OW % 4 == 0 && (!dec1 || !dec2 || ld1 == ld2) && ld % 4 == 0 && off1 % 4 == 0 && off2 % 4 == 0 &&
-                    off1 + 20 <= ld && off2 + 20 <= ld && smem4 <= 64 * 1024 && N <= 65535 &&
-                    (long long)N * 19 * OH * OW * 4 < (1ll << 32) &&
+                    off1 + q4 <= ld && off2 + q4 <= ld && smem4 <= 64 * 1024 && N <= 65535 &&
+                    (long long)N * C * OH * OW * 4 < (1ll << 32) &&
                     ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(score) |
                       reinterpret_cast<uintptr_t>(logit_nchw) | reinterpret_cast<uintptr_t>(label)) & 15) == 0;
     if (v4) {
-      hipLaunchKernelGGL((ood_score_v4_kernel<19, TH, TW>), dim3((OW + TW - 1) / TW, (OH + TH - 1) / TH, N), dim3(256),
-                         smem4, S_(stream), base, ld, (int)off1, (int)off2, IH, IW, OH, OW, sh, sw, SRmax, SCmax, score,
-                         logit_nchw, label);
+      const dim3 grid((OW + TW - 1) / TW, (OH + TH - 1) / TH, N);
+      if (generic)
+        hipLaunchKernelGGL((ood_score_gen_v4_kernel<TH, TW>), grid, dim3(256), smem4, S_(stream), base, ld, (int)off1,
+                           (int)off2, C, IH, IW, OH, OW, sh, sw, SRmax, SCmax, score, logit_nchw, label);
+      else
+        hipLaunchKernelGGL((ood_score_v4_kernel<19, TH, TW>), grid, dim3(256), smem4, S_(stream), base, ld, (int)off1,
+                           (int)off2, IH, IW, OH, OW, sh, sw, SRmax, SCmax, score, logit_nchw, label);
       return mss_launch_status();
     }
-    const size_t smem = (size_t)SRmax * SCmax * (19 + 1) * sizeof(float);
+    const size_t smem = (size_t)SRmax * SCmax * ((generic ? OOD_CH + 1 : 19) + 1) * sizeof(float);
     if (smem <= 48 * 1024 && N <= 65535) {   // up-sampling: the source footprint of a tile is small
-      hipLaunchKernelGGL((ood_score_tiled_kernel<19, TH, TW>), dim3((OW + TW - 1) / TW, (OH + TH - 1) / TH, N),
-                         dim3(256), smem, S_(stream), dec2, ld2, dec1, ld1, IH, IW, OH, OW, sh, sw, SRmax, SCmax, score,
-                         logit_nchw, label);
+      const dim3 grid((OW + TW - 1) / TW, (OH + TH - 1) / TH, N);
+      if (generic)
+        hipLaunchKernelGGL((ood_score_gen_tiled_kernel<TH, TW>), grid, dim3(256), smem, S_(stream), dec2, ld2, dec1, ld1, C,
+                           IH, IW, OH, OW, sh, sw, SRmax, SCmax, score, logit_nchw, label);
+      else
+        hipLaunchKernelGGL((ood_score_tiled_kernel<19, TH, TW>), grid, dim3(256), smem, S_(stream), dec2, ld2, dec1, ld1,
+                           IH, IW, OH, OW, sh, sw, SRmax, SCmax, score, logit_nchw, label);
       return mss_launch_status();
     }
   }
-  hipLaunchKernelGGL(ood_score_kernel<19>, dim3(grid_for((long long)N * OH * OW, 256, 1 << 20)), dim3(256), 0,
-                     S_(stream), dec2, ld2, dec1, ld1, N, IH, IW, OH, OW, ac_scale(IH, OH), ac_scale(IW, OW), score,
-                     logit_nchw, label);
+  if (generic)
+    hipLaunchKernelGGL(ood_score_gen_kernel, dim3(grid_for((long long)N * OH * OW, 256, 1 << 20)), dim3(256), 0,
+                       S_(stream), dec2, ld2, dec1, ld1, N, IH, IW, C, OH, OW, ac_scale(IH, OH), ac_scale(IW, OW), score,
+                       logit_nchw, label);
+  else
+    hipLaunchKernelGGL(ood_score_kernel<19>, dim3(grid_for((long long)N * OH * OW, 256, 1 << 20)), dim3(256), 0,
+                       S_(stream), dec2, ld2, dec1, ld1, N, IH, IW, OH, OW, ac_scale(IH, OH), ac_scale(IW, OW), score,
+                       logit_nchw, label);
   return mss_launch_status();
 }
 
 int mss_ood_score_bwd_f32(const float* dec2, int ld2, const float* dscore, const float* dlogit_nchw, int N,
                           int IH, int IW, int C, int OH, int OW, float* ddec2, int ldd2, float* ddec1, int ldd1,
                           void* stream) {
-  if (C != 19) return MSS_ERR_UNSUPPORTED;
+  if (C < 1 || C > 100) return MSS_ERR_UNSUPPORTED;
   if (ddec2 && !dec2) return MSS_ERR_BAD_ARG;
   if ((long long)N * IH * IW == 0) return MSS_OK;
+  const bool generic = ood_tail_generic(C);
+  const int q4 = 4 * ((C + 3) / 4);
+  // both heads' gradients in one pixel-contiguous buffer (the input of the fused-heads dgrad): the whole row is written
+  float* base = nullptr;
+  long long c1 = 0, c2 = 0;
+  if (ddec1 && ddec2 && ldd1 == ldd2) {
+    base = ddec1 < ddec2 ? ddec1 : ddec2;
+    c1 = ddec1 - base; c2 = ddec2 - base;
+  }
   {
-    // tiled path: both heads' gradients go into one pixel-contiguous buffer (the 48-wide input of the fused-heads dgrad)
     constexpr int MAXW = 6, TSY = 4, TSX = 64;
     const float sh = ac_scale(IH, OH), sw = ac_scale(IW, OW);
     const bool up = sh > 0.f && sw > 0.f && (int)(2.f / sh) + 2 <= MAXW && (int)(2.f / sw) + 2 <= MAXW;
-    if (up && ddec1 && ddec2 && ldd1 == ldd2 && OW % 4 == 0 && ldd1 % 4 == 0 && ld2 % 4 == 0 && N <= 65535) {
-      float* base = ddec1 < ddec2 ? ddec1 : ddec2;
-      const long long c1 = ddec1 - base, c2 = ddec2 - base;
+    if (up && base && OW % 4 == 0 && ldd1 % 4 == 0 && ld2 % 4 == 0 && N <= 65535) {
       const int RR = (int)((TSY + 1) / sh) + 6, RC = ((int)((TSX + 1) / sw) + 10 + 3) & ~3;
       const size_t smem = (size_t)4 * RR * RC * sizeof(float);
-      const bool ok = c1 % 4 == 0 && c2 % 4 == 0 && c1 + 20 <= ldd1 && c2 + 20 <= ldd1 && (c1 + 20 <= c2 || c2 + 20 <= c1) &&
+      const bool ok = c1 % 4 == 0 && c2 % 4 == 0 && c1 + q4 <= ldd1 && c2 + q4 <= ldd1 && (c1 + q4 <= c2 || c2 + q4 <= c1) &&
                       smem <= 64 * 1024 &&
                       ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(dec2) | reinterpret_cast<uintptr_t>(dscore) |
                         reinterpret_cast<uintptr_t>(dlogit_nchw)) & 15) == 0;
       if (ok) {
-        hipLaunchKernelGGL((ood_score_bwd_tiled_kernel<19, MAXW>), dim3((IW + TSX - 1) / TSX, (IH + TSY - 1) / TSY, N),
-                           dim3(256), smem, S_(stream), dec2, ld2, dscore, dlogit_nchw, IH, IW, OH, OW, sh, sw, base, ldd1,
-                           (int)c1, (int)c2, RR, RC);
+        const dim3 grid((IW + TSX - 1) / TSX, (IH + TSY - 1) / TSY, N);
+        if (generic)
+          hipLaunchKernelGGL((ood_score_gen_bwd_tiled_kernel<MAXW>), grid, dim3(256), smem, S_(stream), dec2, ld2, dscore,
+                             dlogit_nchw, C, IH, IW, OH, OW, sh, sw, base, ldd1, (int)c1, (int)c2, RR, RC);
+        else
+          hipLaunchKernelGGL((ood_score_bwd_tiled_kernel<19, MAXW>), grid, dim3(256), smem, S_(stream), dec2, ld2, dscore,
+                             dlogit_nchw, IH, IW, OH, OW, sh, sw, base, ldd1, (int)c1, (int)c2, RR, RC);
         return mss_launch_status();
       }
     }
   }
-  hipLaunchKernelGGL(ood_score_bwd_kernel<19>, dim3(grid_for((long long)N * IH * IW, 256, 1 << 20)), dim3(256), 0,
-                     S_(stream), dec2, ld2, ddec2 ? dscore : nullptr, ddec1 ? dlogit_nchw : nullptr, N, IH, IW, OH,
-                     OW, ac_scale(IH, OH), ac_scale(IW, OW), ddec2, ldd2, ddec1, ldd1);
+  if (generic) {
+    // the fallback writes the whole row too where the two heads share one buffer and do not overlap
+    const bool row = base && c1 + C <= ldd1 && c2 + C <= ldd1 && (c1 + C <= c2 || c2 + C <= c1);
+    hipLaunchKernelGGL(ood_score_gen_bwd_kernel, dim3(grid_for((long long)N * IH * IW, 256, 1 << 20)), dim3(256), 0,
+                       S_(stream), dec2, ld2, ddec2 ? dscore : nullptr, ddec1 ? dlogit_nchw : nullptr, N, IH, IW, C, OH, OW,
+                       ac_scale(IH, OH), ac_scale(IW, OW), ddec2, ldd2, ddec1, ldd1, base, row ? ldd1 : 0, (int)c1, (int)c2);
+  } else {
+    hipLaunchKernelGGL(ood_score_bwd_kernel<19>, dim3(grid_for((long long)N * IH * IW, 256, 1 << 20)), dim3(256), 0,
+                       S_(stream), dec2, ld2, ddec2 ? dscore : nullptr, ddec1 ? dlogit_nchw : nullptr, N, IH, IW, OH,
+                       OW, ac_scale(IH, OH), ac_scale(IW, OW), ddec2, ldd2, ddec1, ldd1);
+  }
   return mss_launch_status();
 }
 

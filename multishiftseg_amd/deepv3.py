@@ -2,7 +2,7 @@
 
 Host-side mirror of lib/network/deepv3/deepv3.py:203-285 (DeepWV3Plus, ASPP) and
 lib/network/deepv3/wider_resnet.py:64-182,267-364 (WiderResNetA2 trunk): same constructor, same
-``forward(inp) -> (anomaly_score [B,H,W], logit [B,19,H,W])``, same parameter / buffer names (the
+``forward(inp) -> (anomaly_score [B,H,W], logit [B,num_classes,H,W])`` for 2..100 classes, same parameter / buffer names (the
 269 state-dict entries load unchanged), same train()/eval() behaviour of BatchNorm and Dropout2d,
 same ``uncertainty_func_init``. The nn.Conv2d / nn.BatchNorm2d children are parameter containers
 only -- their forward is never called. What runs instead (all in libmss_hip.so):
@@ -141,13 +141,28 @@ class _HeadFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
+MIN_CLASSES, MAX_CLASSES = 2, 100      # class indices above 99 mean "OOD" to RelContrastiveLoss and label_threshold; labels are uint8
+
+
+def heads_layout(num_classes):
+    """Layout of the fused heads GEMM (final.6 and ood_head share their input) -> (q, Kh): final.6 lives in rows [0, C) and
+    ood_head in rows [q, q + C) of Kh, q = C rounded up to a channel quad (the 16-byte unit of the OOD-score tail), Kh = 2q
+    rounded up to 16; every other row is zero. (20, 48) for the 19 Cityscapes classes."""
+    C = int(num_classes)
+    if C < 1:
+        raise ValueError(f"num_classes must be positive, got {num_classes}")
+    q = 4 * ((C + 3) // 4)
+    return q, 16 * ((2 * q + 15) // 16)
+
+
 class DeepWV3Plus(nn.Module):
     """Wide-ResNet-38 DeepLabV3+ with the extra OOD head (deepv3.py:203-285)."""
 
     def __init__(self, num_classes, criterion=None, trunk="WideResnet38"):
         super().__init__()
-        if num_classes != 19:
-            raise NotImplementedError("the HIP OOD-score tail is built for the 19 Cityscapes classes")
+        if not MIN_CLASSES <= num_classes <= MAX_CLASSES:
+            raise ValueError(f"num_classes must be in {MIN_CLASSES}..{MAX_CLASSES} (the range of the HIP OOD-score tail), "
+                             f"got {num_classes}")
         self.mod1 = nn.Sequential(OrderedDict([("conv1", nn.Conv2d(3, 64, 3, stride=1, padding=1, bias=False))]))
         cin = 64
         for mod_id, num in enumerate(_STRUCTURE):
@@ -361,13 +376,15 @@ class DeepWV3Plus(nn.Module):
 
     # ---- decoder + heads -------------------------------------------------------------------------
     def _heads_weight(self):
-        """final.6 and ood_head share their input: one GEMM with K = 48 (rows 0-18 / 20-38)."""
+        """final.6 and ood_head share their input: one GEMM over the rows of heads_layout (K = 48, rows 0-18 / 20-38, at 19 classes)."""
         w1, w2 = self.final[6].weight, self.ood_head.weight
         key = (w1._version, w1.data_ptr(), w2._version, w2.data_ptr())
         if self._heads_cache is None or self._heads_cache[0] != key:
-            wh = torch.zeros((48, 256, 1, 1), device=w1.device, dtype=torch.float32)
-            wh[0:19] = w1.detach()
-            wh[20:39] = w2.detach()
+            C = self.num_classes
+            q, Kh = heads_layout(C)
+            wh = torch.zeros((Kh, 256, 1, 1), device=w1.device, dtype=torch.float32)
+            wh[0:C] = w1.detach()
+            wh[q:q + C] = w2.detach()
             self._heads_cache = (key, K.pack_weight(wh), K.pack_weight(wh, flip=True))
         return self._heads_cache[1], self._heads_cache[2]
 
@@ -476,7 +493,9 @@ class DeepWV3Plus(nn.Module):
         final_xt = {0: kx0.get("xt") if kx0 else None, 3: kx3.get("xt") if kx3 else None}
         wh, _ = self._heads_weight()
         dec12 = K.conv2d(f1, wh, in_affine=(st_f1.scale, st_f1.shift), in_relu=True)
-        score, logit, label = K.ood_score(dec12.slice(20, 19), dec12.slice(0, 19) if (want_logit or want_label) else None, size[0], size[1],
+        C = self.num_classes
+        q, _ = heads_layout(C)
+        score, logit, label = K.ood_score(dec12.slice(q, C), dec12.slice(0, C) if (want_logit or want_label) else None, size[0], size[1],
                                           want_logit=want_logit, want_label=want_label)
         if want_label:                 # evaluate(): the uint8 argmax of the logits, whether or not they are written
             return score, logit, label
@@ -516,15 +535,17 @@ class DeepWV3Plus(nn.Module):
         dev = x.buf.device
         dscore = dscore.contiguous() if dscore is not None else None
         dlogit = dlogit.contiguous() if dlogit is not None else None
-        ddec12 = Act.zeros(N, h2, w2, 48, dev)
-        # both slices always: the tiled kernel writes the whole 48-channel row (zeros where a gradient is absent)
-        K.ood_score_bwd(dec12.slice(20, 19), dscore, dlogit, ddec12.slice(20, 19), ddec12.slice(0, 19), OH, OW)
+        C = self.num_classes
+        q, Kh = heads_layout(C)
+        ddec12 = Act.zeros(N, h2, w2, Kh, dev)
+        # both slices always: the tiled kernel writes the whole Kh-channel row (zeros where a gradient is absent)
+        K.ood_score_bwd(dec12.slice(q, C), dscore, dlogit, ddec12.slice(q, C), ddec12.slice(0, C), OH, OW)
         aff_f1 = (s["st_f1"].scale, s["st_f1"].shift)
         if need["ood_head.weight"]:
-            grads["ood_head.weight"] = K.conv2d_wgrad(f1, ddec12.slice(20, 19), 19, 256, 1, 1, in_affine=aff_f1,
+            grads["ood_head.weight"] = K.conv2d_wgrad(f1, ddec12.slice(q, C), C, 256, 1, 1, in_affine=aff_f1,
                                                       in_relu=True)
         if need["final.6.weight"]:
-            grads["final.6.weight"] = K.conv2d_wgrad(f1, ddec12.slice(0, 19), 19, 256, 1, 1, in_affine=aff_f1,
+            grads["final.6.weight"] = K.conv2d_wgrad(f1, ddec12.slice(0, C), C, 256, 1, 1, in_affine=aff_f1,
                                                      in_relu=True)
         upstream = [n for n in names if need[n] and not n.startswith(("ood_head", "final.6"))]
         if not upstream:
@@ -650,6 +671,8 @@ class DeepWV3Plus(nn.Module):
         peers wait there until the process group's timeout. None: no collective, the sweep of one process."""
         from .metric import OODMeter
         meter = OODMeter() if meter is None else meter
+        if seg_meter is not None and seg_meter.n_cl != self.num_classes:
+            raise ValueError(f"seg_meter counts {seg_meter.n_cl} classes, the model predicts {self.num_classes}")
         was = self.training
         self.eval()
         try:

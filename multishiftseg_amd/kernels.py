@@ -1318,21 +1318,24 @@ def upsample_ac_bwd(dy, IH, IW):
 
 
 def ood_score(dec2, dec1, OH, OW, want_score=True, want_logit=True, want_label=False):
-    """The OOD-score tail (deepv3.py:279-283). dec2/dec1: Acts with 19 channels at half res."""
+    """The OOD-score tail (deepv3.py:279-283). dec2/dec1: Acts at half res, one channel per class (1..100; both the same)."""
     ref = dec2 if dec2 is not None else dec1
+    C = ref.C
+    if dec2 is not None and dec1 is not None and dec1.C != dec2.C:
+        raise ValueError(f"ood_score: dec2 has {dec2.C} classes, dec1 has {dec1.C}")
     dev = ref.buf.device
     N = ref.N
     score = torch.empty((N, OH, OW), device=dev, dtype=torch.float32) if want_score else None
-    logit = torch.empty((N, 19, OH, OW), device=dev, dtype=torch.float32) if want_logit else None
+    logit = torch.empty((N, C, OH, OW), device=dev, dtype=torch.float32) if want_logit else None
     label = torch.empty((N, OH, OW), device=dev, dtype=torch.uint8) if want_label else None
     call("mss_ood_score_f32", dec2.ptr if dec2 is not None else None, dec2.ld if dec2 is not None else 0,
-         dec1.ptr if dec1 is not None else None, dec1.ld if dec1 is not None else 0, N, ref.H, ref.W, 19, OH, OW,
+         dec1.ptr if dec1 is not None else None, dec1.ld if dec1 is not None else 0, N, ref.H, ref.W, C, OH, OW,
          ptr(score), ptr(logit), ptr(label))
     return score, logit, label
 
 
 def ood_score_bwd(dec2, dscore, dlogit, ddec2, ddec1, OH, OW):
-    call("mss_ood_score_bwd_f32", dec2.ptr, dec2.ld, ptr(dscore), ptr(dlogit), dec2.N, dec2.H, dec2.W, 19, OH, OW,
+    call("mss_ood_score_bwd_f32", dec2.ptr, dec2.ld, ptr(dscore), ptr(dlogit), dec2.N, dec2.H, dec2.W, dec2.C, OH, OW,
          ddec2.ptr if ddec2 is not None else None, ddec2.ld if ddec2 is not None else 0,
          ddec1.ptr if ddec1 is not None else None, ddec1.ld if ddec1 is not None else 0)
 
