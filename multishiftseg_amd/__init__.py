@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "class_mix_upsample":
         from .criterion import class_mix_upsample
         return class_mix_upsample
+    if name == "class_mix_ood_loss":
+        from .ood_loss import class_mix_ood_loss
+        return class_mix_ood_loss
     if name == "masked_attention":
         from .kernels import masked_attention
         return masked_attention
@@ -50,6 +53,6 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "masked_attention",
+__all__ = ["MultiScaleMaskedTransformerDecoder_GMA", "HungarianMatcher", "SetCriterion", "class_mix_upsample", "class_mix_ood_loss", "masked_attention",
            "conv2d_dgrad_s2", "stem7_wgrad", "prepare_targets", "M2FTargets", "ResNet", "build_resnet_backbone", "MaskFormer", *_M2F_TRAINER,
            *_STAGE1_KERNELS, *_DDP]

@@ -7,11 +7,15 @@ loss and the sampled mask losses of ALL S steps (the last output and its aux_out
 launches (three forward, two backward) after the matcher's two, with no device-to-host copy, and two runs give the same bits.
 There is no CPU path.
 
-`loss_ood` (criterion.py:128-187) is here in its RCL branch, the one the entry scripts select. Per step it is two autograd nodes of
-`class_mix_upsample` -- the class mix of (pred_logits, pred_masks) upsampled and cropped to the 19 logit maps, and that of
-(pred_logits_ood, pred_masks_ood) reduced to -max over the classes at full size -- followed by `extra_loss(logits, score, target)`.
-The mix and the sigmoids stay at the low resolution, the backward gathers (no float atomics) and stores no argmax map: it
-recomputes it. The `margin` and `bce` branches, which no entry script selects, raise NotImplementedError.
+`loss_ood` (criterion.py:128-187) is here in all three branches. `RCL` (what exps/M2F.yaml selects through
+replace_official_odd_loss_with_RCL): per step two autograd nodes of `class_mix_upsample` -- the class mix of (pred_logits, pred_masks)
+upsampled and cropped to the 19 logit maps, and that of (pred_logits_ood, pred_masks_ood) reduced to -max over the classes at full
+size -- followed by `extra_loss(logits, score, target)`. `margin` (the reference's default: mask2former/config.py:118-119,
+train_m2f.py:157-158 with lib/configs/config.py:44) and `bce`: per step one node `ood_loss.class_mix_ood_loss` over (pred_logits,
+pred_masks) and the stacked ood_mask -- -max over the classes at the LOW resolution, the one-channel score interpolated with
+align_corners=True to the size of ood_mask, two masked means. In every branch the mix and the sigmoids stay at the low resolution,
+the backward gathers (no float atomics) and stores no argmax map: it recomputes it. `margin` and `bce` have no CPU path: with
+tensors that are not on the device they raise NotImplementedError before any other check.
 
 Deviations from the reference, all deliberate:
   * the random numbers have the reference's distribution, not its draw order (one torch.rand per kind for all rows of all steps);
@@ -34,6 +38,7 @@ from torch import nn
 
 from . import kernels as K
 from .matcher import _steps_of
+from .ood_loss import class_mix_ood_loss
 
 CLEAN_OVERSAMPLE_RATIO = 1 / 0.8            # criterion.py:374-376: hard-coded in get_clean_point_coords_with_randomness
 CLEAN_IMPORTANCE_SAMPLE_RATIO = 0.95
@@ -162,11 +167,14 @@ class SetCriterion(nn.Module):
         if self.ood_loss == "RCL":
             if self.extra_loss is None:                         # the reference asserts (criterion.py:163)
                 raise NotImplementedError("loss_ood with ood_loss 'RCL' needs an extra_loss: call set_extra_loss(RelContrastiveLoss(...)) first")
-        elif self.ood_loss in ("margin", "bce"):
-            raise NotImplementedError(f"SetCriterion on HIP has loss_ood for ood_loss 'RCL' only (criterion.py:162-183); {self.ood_loss!r} "
-                                      "(:140-161) is selected by no entry script")
-        else:
+        elif self.ood_loss not in ("margin", "bce"):        # those two: _refuse_host, with the call's tensors
             raise ValueError("define_ood_loss")
+
+    def _refuse_host(self, outputs):
+        """ood_loss 'margin' / 'bce' (criterion.py:140-161) with tensors that are not on the device: before any other check."""
+        if self.ood_loss in ("margin", "bce") and not all(v.is_cuda for v in outputs.values() if isinstance(v, torch.Tensor)):
+            raise NotImplementedError(f"SetCriterion.loss_ood with ood_loss {self.ood_loss!r} runs on an MI355X only (CUDA tensors); "
+                                      "there is no CPU path")
 
     def _check_losses(self):
         for loss in self.losses:
@@ -176,12 +184,15 @@ class SetCriterion(nn.Module):
             assert loss in ("labels", "masks"), f"do you really want to compute {loss} loss?"
 
     def loss_ood(self, outputs, targets):
-        """criterion.py:128-138, 162-187 for one prediction step: outputs holds pred_logits, pred_masks (or pred_masks_pixel_major),
+        """criterion.py:128-187 for one prediction step. ood_loss "margin" / "bce": see _loss_ood_pixel. "RCL": outputs holds pred_logits, pred_masks (or pred_masks_pixel_major),
         pred_logits_ood and pred_masks_ood; targets per image "ood_mask" (only its shape (H, W) is used) and "sem_seg" [Ht,Wt]
         (numpy array or tensor). extra_loss gets a fresh int64 copy of the stacked sem_seg, as the reference's torch.tensor(target):
         RelContrastiveLoss changes it in place. -> {"loss_ood": 0-d tensor}."""
+        self._refuse_host(outputs)
         self._check_ood()
         pixel_major = "pred_masks" not in outputs
+        if self.ood_loss in ("margin", "bce"):
+            return {"loss_ood": self._loss_ood_pixel(outputs, targets, pixel_major)}
         cls, cls_ood = outputs["pred_logits"], outputs["pred_logits_ood"]
         if pixel_major:
             masks = outputs["pred_masks_pixel_major"]
@@ -204,15 +215,29 @@ class SetCriterion(nn.Module):
         score = class_mix_upsample(cls_ood, masks_ood, size, crop, "neg_max", pixel_major=pixel_major, Q=Q)
         return {"loss_ood": self.extra_loss(logits, score, target)}
 
+    def _loss_ood_pixel(self, outputs, targets, pixel_major):
+        """criterion.py:130-161 for one prediction step: pred_logits with pred_masks (or pred_masks_pixel_major), not the _ood heads;
+        targets per image "ood_mask" [H,W], stacked: a uint8 or bool stack as it is, another dtype through == 1 / == 0. sem_seg and
+        extra_loss are not read."""
+        cls = outputs["pred_logits"]
+        masks = outputs["pred_masks_pixel_major" if pixel_major else "pred_masks"]
+        ood = torch.stack([t["ood_mask"] if isinstance(t["ood_mask"], torch.Tensor) else torch.as_tensor(t["ood_mask"]) for t in targets])
+        if ood.dim() == 4 and ood.shape[1] == 1:                # [B,1,H,W]: the reference squeezes that axis (:144-145)
+            ood = ood[:, 0]
+        return class_mix_ood_loss(cls, masks, ood.to(cls.device), self.ood_loss, self.margin, pixel_major=pixel_major, Q=cls.shape[1])
+
     def forward(self, outputs, targets, *, num_masks=None, point_candidates=None, random_points=None, matcher_points=None):
         """The loss computation (criterion.py:432-469). outputs: {"pred_logits" [B,Q,C+1], "pred_masks" [B,Q,h,w] (or
         "pred_masks_pixel_major" [B,h,w,ldq]), "aux_outputs": [the same per earlier step]}; targets: per image {"labels" [T_b],
         "masks" [T_b,H,W]}. Returns {loss_ce, loss_mask, loss_dice} (or the four keys of loss_masks_aug), then `<key>_<i>` for
         aux_outputs[i] when deep_supervision is set: 0-d float32 device tensors attached to autograd, weight_dict NOT applied.
         With "ood" in losses every step also needs "pred_logits_ood" / "pred_masks_ood" and every target "ood_mask" / "sem_seg"
-        (see loss_ood), and "loss_ood" / "loss_ood_<i>" take their place in the order of `losses`.
+        (ood_loss "RCL"; "margin" and "bce" need "ood_mask" alone: see loss_ood), and "loss_ood" / "loss_ood_<i>" take their place in
+        the order of `losses`.
         num_masks: overrides max(sum T_b, 1). point_candidates [S, rows that select, K, 2], random_points [S * sum T, Pr, 2],
         matcher_points [S,B,P,2]: inject the random numbers (see kernels.m2f_point_select / HungarianMatcher.match_steps)."""
+        if "ood" in self.losses:
+            self._refuse_host(outputs)
         self._check_losses()
         steps = _steps_of(outputs) if self.deep_supervision else _steps_of({k: v for k, v in outputs.items() if k != "aux_outputs"})
         S = len(steps)
