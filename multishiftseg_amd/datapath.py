@@ -17,8 +17,11 @@ mixing weights, crop corners, objects, scales and paste corners:
     object scale      random.choice                         img_utils.py:346
     paste corner      random.randint x 2                    img_utils.py:412-415
 
-File decoding and the cv2 rescale of the COCO object are out of scope (no image codecs / cv2 in the image): objects are
-handed over already rescaled. There is no CPU path: a CPU tensor raises.
+The rescale of the COCO object (cv2.resize, img_utils.py:345-352) and its bounding-box cut run on the device too when the
+objects come from an object_bank.ObjectBank: the decoded objects stay resident as uint8, draw_sample_params takes the box from
+the bank's table and hands on pick=(index, scale), and make_pair_batch(..., bank=bank) fills the object buffers of the whole
+batch with one launch. Host objects with a scaled_object callback keep working, bit for bit. File decoding is
+out of scope (no image codecs in the image). There is no CPU path: a CPU tensor raises.
 """
 import random as _random
 
@@ -45,25 +48,49 @@ def mask_bbox(mask):
 def draw_sample_params(H, W, crop_size, mixup, objects=None, scaled_object=None, rng=_random, scales=OOD_SCALES):
     """Random decisions of ONE sample in the reference's order. objects: list of candidates for the anomaly mix;
     scaled_object(obj, scale) -> (image float32 [oh, ow, 3], mask uint8 [oh, ow]) performs the rescale (the reference uses
-    cv2.resize, img_utils.py:349-350). Returns a dict with p, top, left and, with objects, obj_img / obj_mask / geom."""
+    cv2.resize, img_utils.py:349-350). Returns a dict with p, top, left and, with objects, obj_img / obj_mask / geom.
+    objects with a `bbox` method (an object_bank.ObjectBank, or anything with __len__ and bbox(index, scale)) is a BANK: the same
+    draws, the box from objects.bbox, and pick=(index, scale) / geom=(0, 0, bh, bw, h0, w0) in place of the two arrays;
+    scaled_object is not called."""
     out = {"p": min(rng.random(), 0.3) if mixup else None}                   # cityscapes.py:161-162
     out["top"] = rng.randint(0, H - crop_size[0])                            # img_utils.py:256
     out["left"] = rng.randint(0, W - crop_size[1])                           # img_utils.py:257
     if objects:
-        obj = objects[rng.randint(0, len(objects) - 1)]                      # img_utils.py:369
+        index = rng.randint(0, len(objects) - 1)                             # img_utils.py:369
         scale = rng.choice(scales)                                           # img_utils.py:346
-        o_img, o_mask = scaled_object(obj, scale)
-        y1, x1, y2, x2 = mask_bbox(o_mask)
+        bank = hasattr(objects, "bbox")
+        if bank:
+            y1, x1, y2, x2 = objects.bbox(index, scale)
+        else:
+            o_img, o_mask = scaled_object(objects[index], scale)
+            y1, x1, y2, x2 = mask_bbox(o_mask)
         bh, bw = y2 - y1, x2 - x1
         h0 = rng.randint(0, crop_size[0] - bh)                               # img_utils.py:412
         w0 = rng.randint(0, crop_size[1] - bw)                               # img_utils.py:414
-        out.update(obj_img=o_img, obj_mask=o_mask, geom=(y1, x1, bh, bw, h0, w0))
+        if bank:                    # the bank writes the box to the origin of the sample's slot
+            out.update(pick=(index, scale), geom=(0, 0, bh, bw, h0, w0))
+        else:
+            out.update(obj_img=o_img, obj_mask=o_mask, geom=(y1, x1, bh, bw, h0, w0))
     return out
 
 
-def make_pair_batch(img, gen, tgt, gen_tgt, crop_size, params, flip=None, mean=MEAN, std=STD):
+def bank_objects(params, bank):
+    """The object tensors of a batch whose parameter sets carry `pick`: one bank.rescale launch. None when no set carries one;
+    ValueError for picks without a bank and for a batch that mixes picks with host objects."""
+    picked = ["pick" in p for p in params]
+    if not any(picked):
+        return None
+    if not all(picked):
+        raise ValueError("a batch either picks every object from the bank or carries every object itself")
+    if bank is None:
+        raise ValueError("the parameter sets pick objects from a bank: pass it as bank=")
+    return bank.rescale([p["pick"] for p in params])
+
+
+def make_pair_batch(img, gen, tgt, gen_tgt, crop_size, params, flip=None, mean=MEAN, std=STD, bank=None):
     """img / gen: uint8 [B,H,W,3] device tensors, tgt / gen_tgt: uint8 [B,H,W]; params: one dict per sample as returned by
-    draw_sample_params. Returns (images float32 [2B,3,h,w], targets int64 [2B,h,w]), originals first."""
+    draw_sample_params; bank: the object_bank.ObjectBank the sets were drawn from, when they carry `pick`. Returns
+    (images float32 [2B,3,h,w], targets int64 [2B,h,w]), originals first."""
     for t in (img, gen, tgt, gen_tgt):
         if not t.is_cuda:
             raise RuntimeError("multishiftseg_amd.datapath runs on an MI355X only; there is no CPU path")
@@ -81,7 +108,12 @@ def make_pair_batch(img, gen, tgt, gen_tgt, crop_size, params, flip=None, mean=M
     flip_t = torch.tensor([int(f) for f in flip], dtype=torch.int32).to(dev) if flip is not None else None
     obj_img = obj_mask = geom = None
     ohm = owm = 0
-    if "geom" in params[0]:
+    picked = bank_objects(params, bank)
+    if picked is not None:
+        obj_img, obj_mask = picked
+        ohm, owm = obj_mask.shape[1:]
+        geom = torch.tensor([list(p["geom"]) for p in params], dtype=torch.int32).to(dev)
+    elif "geom" in params[0]:
         ohm = max(p["obj_mask"].shape[0] for p in params)
         owm = max(p["obj_mask"].shape[1] for p in params)
         oi = np.zeros((B, ohm, owm, 3), dtype=np.float32)

@@ -13,7 +13,11 @@ sample's two slots of the batch. Every stage is also callable alone (the functio
 
 QUIRK kept on purpose: the reference rotates without a `fill`, so rotated-in corners are black and CLASS 0 in the label map.
 
-There is no CPU path: a CPU tensor raises. File decoding and the cv2 rescale of the COCO object stay the caller's.
+The pasted COCO object comes either from the caller, already rescaled (scaled_object), or from a resident
+object_bank.ObjectBank: draw_m2f_sample_params then hands on pick=(index, scale) and make_m2f_pair_batch(..., bank=bank) rescales
+and cuts the objects of the whole batch with one launch; a sample takes its slot.
+
+There is no CPU path: a CPU tensor raises. File decoding stays the caller's.
 """
 import ctypes
 import math
@@ -23,7 +27,7 @@ import torch
 
 from . import _lib_aug as A
 from ._lib_aug import call, ptr
-from .datapath import MEAN, STD, draw_sample_params
+from .datapath import MEAN, STD, bank_objects, draw_sample_params
 
 # train_m2f.py:48-61
 M2F_CHAIN = (("ToTensor", 1.0), ("ColorJitter", 0.5), ("GaussianBlur", 0.5), ("RandSharpness", 0.5), ("AutoContrast", 0.5),
@@ -52,7 +56,7 @@ class _ReplayCrop:
 
 def draw_m2f_sample_params(H, W, crop_size, mixup=True, objects=None, scaled_object=None, rng=_random, chain=M2F_CHAIN):
     """Random decisions of ONE sample in the reference's order. Returns {"p", "entries", "size", "top", "left"} and, with
-    objects, obj_img / obj_mask / geom as datapath.draw_sample_params. "entries" lists the APPLIED chain entries in order,
+    objects, obj_img / obj_mask / geom (pick / geom when objects is a bank) as datapath.draw_sample_params. "entries" lists the APPLIED chain entries in order,
     each a dict with "name" and its own draws. ColorJitter and GaussianBlur read torch's default CPU generator, as
     torchvision does; everything else reads `rng`."""
     p = min(rng.random(), 0.3) if mixup else None                              # cityscapes.py:161
@@ -92,7 +96,10 @@ def draw_m2f_sample_params(H, W, crop_size, mixup=True, objects=None, scaled_obj
         if top is None:
             raise ValueError("the paste needs the crop: the chain applied no RandCrop")
         paste = draw_sample_params(Hs, Ws, crop_size, False, objects, scaled_object, _ReplayCrop(rng, top, left))
-        out.update(obj_img=paste["obj_img"], obj_mask=paste["obj_mask"], geom=paste["geom"])
+        if "pick" in paste:         # objects is a bank: the object tensors come from bank.rescale in make_m2f_pair_batch
+            out.update(pick=paste["pick"], geom=paste["geom"])
+        else:
+            out.update(obj_img=paste["obj_img"], obj_mask=paste["obj_mask"], geom=paste["geom"])
     return out
 
 
@@ -252,7 +259,7 @@ def finish(x, m, out_img, out_tgt, b, hflip=False, vflip=False, top=0, left=0, s
 
 # ---- the chain ---------------------------------------------------------------------------------------------------------------
 
-def _sample(img, gen, tgt, gen_tgt, crop_size, prm, b, out_img, out_tgt, mean, std, trace):
+def _sample(img, gen, tgt, gen_tgt, crop_size, prm, b, out_img, out_tgt, mean, std, trace, picked=None):
     x, m = load_pair(img, gen, tgt, gen_tgt, prm["p"])
     names = [e["name"] for e in prm["entries"]]
     if names[:1] != ["ToTensor"] or names[-2:] != ["RandCrop", "Normalize"]:
@@ -298,7 +305,9 @@ def _sample(img, gen, tgt, gen_tgt, crop_size, prm, b, out_img, out_tgt, mean, s
             break
         note(name)
     paste = dict(obj_img=None, obj_mask=None, geom=None)
-    if "geom" in prm:
+    if picked is not None:          # slot b of the batch's bank.rescale
+        paste = dict(obj_img=picked[0][b], obj_mask=picked[1][b], geom=prm["geom"])
+    elif "geom" in prm:
         dev = x.device
         paste = dict(obj_img=torch.as_tensor(prm["obj_img"], dtype=torch.float32).contiguous().to(dev),
                      obj_mask=torch.as_tensor(prm["obj_mask"], dtype=torch.uint8).contiguous().to(dev), geom=prm["geom"])
@@ -313,9 +322,9 @@ def _sample(img, gen, tgt, gen_tgt, crop_size, prm, b, out_img, out_tgt, mean, s
                **paste)
 
 
-def make_m2f_pair_batch(img, gen, tgt, gen_tgt, crop_size, params, mean=MEAN, std=STD, trace=None):
+def make_m2f_pair_batch(img, gen, tgt, gen_tgt, crop_size, params, mean=MEAN, std=STD, trace=None, bank=None):
     """img / gen: uint8 [B,H,W,3] device tensors, tgt / gen_tgt: uint8 [B,H,W]; params: one dict per sample as returned by
-    draw_m2f_sample_params. Returns (images float32 [2B,3,h,w], targets int64 [2B,h,w]), originals first
+    draw_m2f_sample_params; bank: the object_bank.ObjectBank the sets were drawn from, when they carry `pick`. Returns (images float32 [2B,3,h,w], targets int64 [2B,h,w]), originals first
     (train_m2f.py:430-433). trace: a list that receives (stage name, x clone, m clone) after every applied entry of every
     sample (the stages then run one by one instead of fused; the results are the same bits)."""
     _gpu(img, gen, tgt, gen_tgt)
@@ -328,6 +337,7 @@ def make_m2f_pair_batch(img, gen, tgt, gen_tgt, crop_size, params, mean=MEAN, st
         raise ValueError(f"{len(params)} parameter sets for a batch of {B}")
     out_img = torch.empty((2 * B, 3, h, w), device=img.device, dtype=torch.float32)
     out_tgt = torch.zeros((2 * B, h, w), device=img.device, dtype=torch.int64)
+    picked = bank_objects(params, bank)
     for b, prm in enumerate(params):
-        _sample(img[b], gen[b], tgt[b], gen_tgt[b], (h, w), prm, b, out_img, out_tgt, mean, std, trace)
+        _sample(img[b], gen[b], tgt[b], gen_tgt[b], (h, w), prm, b, out_img, out_tgt, mean, std, trace, picked)
     return out_img, out_tgt
