@@ -12,7 +12,9 @@
 //   AP    = 1/P sum_pos  #pos>=s / (#pos>=s + #neg>=s)              -- sklearn's sum_k (R_k - R_k-1) P_k: recall only
 //                                                                       moves at thresholds that are positive scores
 //   FPR95 = fps / N at the threshold the reference's argmin |recall - 0.95| picks (ties -> higher recall, the
-//           last threshold of that recall level, metric.py:117-127)
+//           last threshold of that recall level, metric.py:117-127). The recall levels are c/P for c = #pos >= v over the
+//           distinct positive scores v, and 0 iff a negative score lies above the largest positive one (thresholds there
+//           have tps = 0); without such a negative the lowest level is that of the largest positive score.
 // -0.0 is folded onto +0.0 first (NumPy compares them equal, so they are one threshold).
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -182,9 +184,11 @@ __global__ void oodm_finalize_kernel(const uint32_t* __restrict__ pos, long long
   for (int b = 0; b < nparts; ++b) { u2 += u2_part[b]; ap += ap_part[b]; }
   out[0] = (double)u2 / (2.0 * (double)P * (double)N);
   out[1] = ap / (double)P;
-  // recall takes the values c/P for c = #pos >= v over the distinct positive scores v. Candidates around
+  // recall takes the values c/P for c = #pos >= v over the distinct positive scores v, and 0 when some negative lies above
+  // every positive (the reference's thresholds run over all scores: there tps = 0, metric.py:117-127). Candidates around
   // recall_level * P: both ends of the runs holding the floor(t)-th and (floor(t)+1)-th largest positives.
   const double pd = (double)P;
+  const bool zero_ok = N - upper_bound(neg, 0, N, pos[P - 1]) > 0;
   long long i0 = (long long)floor(recall_level * pd);
   long long best_c = -1;
   double best_f = 0.0;
@@ -197,7 +201,7 @@ __global__ void oodm_finalize_kernel(const uint32_t* __restrict__ pos, long long
     const long long c_start = P - upper_bound(pos, 0, P, v); // #pos >  v  (end of the previous run)
     const long long cand[2] = {c_start, c_end};
     for (int j = 0; j < 2; ++j) {
-      if (cand[j] < 1) continue;
+      if (cand[j] < 1 && !zero_ok) continue;
       const double f = fabs((double)cand[j] / pd - recall_level);
       if (best_c < 0 || f < best_f || (f == best_f && cand[j] > best_c)) { best_f = f; best_c = cand[j]; }
     }

@@ -40,7 +40,12 @@ class OODMeter:
     The state is a multiset of 32-bit order-preserving keys per class, and compute() sorts before it measures: the union of two
     meters' keys therefore measures exactly what one meter fed both meters' maps does, whatever the order. merge() forms that
     union in one process, all_gather() over the ranks of a process group; keys() / extend_keys() are the dense form
-    in which keys leave and enter a meter."""
+    in which keys leave and enter a meter.
+
+    Scores are finite or infinite float32 (denormals keep their place, -0.0 and 0.0 are one score). NaN scores are outside the
+    contract: the reference raises on them, and here they would silently sort above +inf or below -inf by their sign bit.
+    `recall_level` is the recall at which the FPR is read (the reference's 0.95); any level in [0, 1] is honoured, recall 0
+    included when inliers score above every OOD pixel."""
 
     def __init__(self, train_id_in=0, train_id_out=1, recall_level=0.95):
         if train_id_in == train_id_out:
